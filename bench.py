@@ -11,10 +11,20 @@ table, dropout 0.2 everywhere (the reference's run-script values), train-mode Ba
 outside the metric (north_star): `sent_vecs` is a random [B, 1024] tensor.  All inputs are resident in HBM before
 the timed region.  One step = zero_grad + QAGNN.forward + cross-entropy over the choices + backward; with N > 1
 every rank runs its own 64 questions (weak scaling) and the step additionally all-reduces the decoder gradients and
-all-gathers the logits over RCCL.  `value` is the MEDIAN of `repeats` (default 3) back-to-back timed regions of exactly K steps
-each (each bracketed by barrier + synchronize, max over ranks); all regions are listed in `repeat_ms_per_step`.
+all-gathers the logits over RCCL.  `value` is the MEDIAN of `repeats` back-to-back timed regions of exactly K steps each (each
+bracketed by barrier + synchronize, max over ranks); all regions are listed in `repeat_ms_per_step`.
 
-Extra objects on the JSON line:
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps (`--repeats` defaults to 1) and prints the headline
+line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds per timed step), the host enqueue time,
+the launch form and the workload (with N > 1 also the collective figures of the timed steps, last item below).  Everything else
+below is measured only with `--full` (which also makes `--repeats` default to 3): those objects are absent from a plain line, and
+`cpu_baseline` is null.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the LAST timed step -- the logits [questions, choices], the
+loss and the gradient of every trainable parameter (`grad.<parameter name>`) -- as float32 DIR/<name>.npy (rank 0), before anything
+else runs.  The inputs and weights are seeded: the same arguments give the same inputs in every run.
+
+Extra objects on the JSON line with --full:
   roofline     the edge stage of GATConvE forward (qagnn_edge_attn_fwd_f32: scores + segment softmax + aggregate), one launch
                per GAT layer, average duration from HIP events on the launch stream around every call inside the timed steps.
                `achieved` / `frac` are PHYSICAL: bytes that cross the HBM interface per launch = max(compulsory bytes,
@@ -55,7 +65,7 @@ Extra objects on the JSON line:
                utils/parser_utils.py:58), timed separately (fp32 and under the reference's --fp16 autocast) and as one
                LM_QAGNN.forward + loss + backward step with the encoder frozen (qagnn.py:240-247); `decoder_share` says what part
                of that step the decoder still is.  Excluded from `value`.
-  N > 1:       `comm_ms_per_step` (gradient all-reduce + logits all-gather, HIP events on the compute stream around the
+  N > 1 (plain runs too):  `comm_ms_per_step` (gradient all-reduce + logits all-gather, HIP events on the compute stream around the
                collectives), `rank_ms_per_step` (min / max over ranks of each rank's own time for the median region).
                `--global-batch Q` switches to STRONG scaling: one global batch of Q questions with skewed subgraph sizes, dealt out to
                the ranks by parallel.balance_questions (sum of E'_g per rank), variable-size logits gather, question order restored.
@@ -280,7 +290,7 @@ def step(model, b, nc, loss_weight, flat_grad_params, comm=None):
     loss.backward()
     if comm is not None:
         comm(logits)
-    return logits
+    return logits.detach(), loss.detach()  # (detached: a step's result held across the next one keeps no autograd graph alive)
 
 
 def make_runner(model, b, nc, loss_weight, params, comm, use_graph):
@@ -306,12 +316,13 @@ def make_runner(model, b, nc, loss_weight, params, comm, use_graph):
     gs = graphed.GraphedStep(model, nc)
 
     def run_local():
-        return gs(b['sent'], b['cids'], b['nt'], b['ns'], b['al'], b['adj'], b['labels'], loss_weight)[0]
+        return gs(b['sent'], b['cids'], b['nt'], b['ns'], b['al'], b['adj'], b['labels'], loss_weight)
 
     def run():
-        logits = run_local()
+        logits, loss = run_local()
         if comm is not None:
             comm(logits.view(-1, nc))  # the collectives stay OUTSIDE the graph, on the same stream, behind the replay
+        return logits, loss
     if picked == 'measured':
         def ms_of(fn, n=6):
             for _ in range(3):
@@ -371,7 +382,7 @@ def measure_edge_traffic(args, N, DP):  # (also leaves the backward stage's byte
     for ctr in ('FETCH_SIZE', 'WRITE_SIZE'):
         td = tempfile.mkdtemp(prefix=f'qagnn_pmc_{ctr}_', dir='/tmp')
         cmd = [rocprof, '--pmc', ctr, '--kernel-trace', '--output-format', 'csv', '-d', td, '-o', 'p', '--', sys.executable,
-               os.path.abspath(__file__), '--steps', '2', '--warmup', '1', '--repeats', '1', '--graphs', '0', '--no-cpu-baseline', '--no-pmc', '--pmc-child',
+               os.path.abspath(__file__), '--full', '--steps', '2', '--warmup', '1', '--repeats', '1', '--graphs', '0', '--no-cpu-baseline', '--no-pmc', '--pmc-child',
                '--questions', str(args.questions), '--n-concept', str(args.n_concept), '--dropout', str(args.dropout)] + \
               (['--edge-lists'] if args.edge_lists else [])
         try:
@@ -419,14 +430,39 @@ def to_device(batch, dev, use_blobs, nc):
 
 
 def timed_steps(run_step, steps, sync):
-    """-> (seconds for `steps` steps incl. the final synchronisation, seconds the HOST needed to enqueue them)."""
+    """-> (seconds for `steps` steps incl. the final synchronisation, seconds the HOST needed to enqueue them).  What the last step
+    returned is left in timed_steps.last."""
+    last = None
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        run_step()
+        last = run_step()
     t1 = time.perf_counter()
     sync()
-    return time.perf_counter() - t0, t1 - t0
+    dt = time.perf_counter() - t0
+    timed_steps.last = last
+    return dt, t1 - t0
+
+
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much array data (64 MB in all with the .npy headers)
+
+
+def dump_outputs(path, logits, loss, model, nc):
+    """--dump-outputs: the logits [questions, nc], the loss and every trainable parameter's gradient as float32 PATH/<name>.npy.
+    Should they exceed DUMP_BYTES, every array is cut to the same fraction of its elements at fixed seeded positions (in order), so
+    two builds still compare element for element.  -> number of arrays written."""
+    import numpy as np
+    arrays = {'logits': logits.reshape(-1, nc), 'loss': loss}
+    arrays.update((f'grad.{name}', p.grad) for name, p in model.named_parameters() if p.requires_grad and p.grad is not None)
+    frac = min(1.0, DUMP_BYTES / max(1, 4 * sum(t.numel() for t in arrays.values())))
+    g = torch.Generator().manual_seed(0)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to('cpu', torch.float32)
+        if frac < 1.0:
+            a = a.flatten()[torch.randperm(a.numel(), generator=g)[:max(1, int(a.numel() * frac))].sort().values]
+        np.save(os.path.join(path, name + '.npy'), a.numpy())
+    return len(arrays)
 
 
 def instrumented_pass(run_step, timed, sync, n_steps):
@@ -709,13 +745,18 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps steps each; the median is the headline')
+    ap.add_argument('--full', action='store_true', help='everything beside the headline: roofline / GEMM / edge-stage figures, CPU '
+                    'baseline, optimizer, the other configurations, the LM encoder leg (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s logits, loss and parameter gradients '
+                    'as float32 DIR/<name>.npy')
+    ap.add_argument('--repeats', type=int, default=None, help='timed regions of --steps steps each; the median is the headline '
+                    '(default 1; 3 with --full)')
     ap.add_argument('--questions', type=int, default=64, help='questions per GPU (x5 choices = subgraphs per GPU)')
     ap.add_argument('--global-batch', type=int, default=0, help='N > 1: strong scaling -- ONE global batch of this many questions (skewed '
                     'subgraph sizes), dealt out to the ranks by parallel.balance_questions')
     ap.add_argument('--n-concept', type=int, default=100000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-configs', action='store_true', help='skip the other single-GPU configurations (configs object)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU oracle legs')
+    ap.add_argument('--no-configs', action='store_true', help='--full without the other single-GPU configurations (configs object)')
     ap.add_argument('--dropout', type=float, default=0.2)
     ap.add_argument('--edge-lists', action='store_true', help='feed the graph as int64 (edge_index, edge_type) (the reference protocol; the '
                     'graph orderings are then re-derived per batch) instead of the load-time blobs of qagnn_amd.data_utils')
@@ -724,9 +765,11 @@ def main():
                          'auto (default): replay where the step is host-bound (fewer than ops.FUSED_HOP_MAX_ROWS node rows)')
     ap.add_argument('--comm-overlap', action='store_true', help='N > 1: gradient all-reduce in two buckets, the first issued from an autograd '
                     'hook under the tail of the backward (parallel.SplitGradBuckets); default: one bucket behind the backward')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the two rocprofv3 --pmc child passes (roofline.traffic)')
+    ap.add_argument('--no-pmc', action='store_true', help='--full without the two rocprofv3 --pmc child passes (roofline.traffic)')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # called the way the N = 1 command is called (`python bench.py --gpus N`, no launcher): spawn the N ranks ourselves
@@ -799,9 +842,11 @@ def main():
     model.train()
     params = [p for p in model.parameters() if p.requires_grad]
     comm = Comm(params, world, assignment=assignment, model=model, overlap=args.comm_overlap)
-    timed = TimedKernels(ops.kernels(), TIMED, work={'gemm_nn': _nn_flops, 'gemm_tn': _tn_flops, 'gemm_tn2': _tn2_flops, 'gemm_tn_h2': _tnh2_flops},
-                         useful={'gemm_nn': _nn_useful, 'gemm_tn': _tn_useful, 'gemm_tn2': _tn2_useful, 'gemm_tn_h2': _tnh2_useful})
-    ops.set_kernels(timed)
+    timed = None
+    if args.full:  # (the per-launch HIP events of the roofline figures)
+        timed = TimedKernels(ops.kernels(), TIMED, work={'gemm_nn': _nn_flops, 'gemm_tn': _tn_flops, 'gemm_tn2': _tn2_flops, 'gemm_tn_h2': _tnh2_flops},
+                             useful={'gemm_nn': _nn_useful, 'gemm_tn': _tn_useful, 'gemm_tn2': _tn2_useful, 'gemm_tn_h2': _tnh2_useful})
+        ops.set_kernels(timed)
     run, run_eager, gs = make_runner(model, b, nc, loss_weight, params, comm, args.graphs)
     headline_choice = make_runner.last_choice
 
@@ -815,10 +860,11 @@ def main():
     for _ in range(args.warmup):
         run()
     sync()
-    # eager: 6 event pairs per step inside the timed regions (the forward edge stage and the graph preparation); under hipGraph replay
-    # there are no per-launch events -- those durations then come from the instrumented eager pass below
-    timed.enabled = gs is None
-    timed.active = {'edge_attn_fwd', 'graph_prep', 'graph_from_blobs'}
+    # --full, eager: 6 event pairs per step inside the timed regions (the forward edge stage and the graph preparation); under hipGraph
+    # replay there are no per-launch events -- those durations then come from the instrumented eager pass below
+    if timed is not None:
+        timed.enabled = gs is None
+        timed.active = {'edge_attn_fwd', 'graph_prep', 'graph_from_blobs'}
     regions = []
     for _ in range(max(1, args.repeats)):
         dt_r, enq_r = timed_steps(run, args.steps, sync)
@@ -831,22 +877,27 @@ def main():
             regions.append((t.item(), enq_r, tmin.item()))
         else:
             regions.append((dt_r, enq_r, dt_r))
-    timed.enabled = False
+    if timed is not None:
+        timed.enabled = False
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before any other step overwrites them
+        n_arrays = dump_outputs(args.dump_outputs, *timed_steps.last, model, nc)
+        print(f'[bench] --dump-outputs: {n_arrays} arrays of the last timed step in {args.dump_outputs}', file=sys.stderr)
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt, enq, dt_min = regions[order[len(order) // 2]]
-    fwd_ms, n_fwd = timed.mean_ms('edge_attn_fwd')
-    prep_ms, _ = timed.mean_ms('graph_prep' if args.edge_lists else 'graph_from_blobs')
     comm_ms = comm.mean_ms(args.steps * len(regions))
-    # the ~72 GEMM launches per step are bracketed in a separate short pass: 144 more event records per step would cost the
-    # headline number ~2 %.  The backward edge stage is timed there too, with the weight-gradient overlap switched off: in the
-    # timed regions above those GEMMs run on a side stream UNDER the edge backward (ops.WGRAD_OVERLAP), so an event pair around
-    # either would measure the co-running kernels, not the kernel.  Host-bound batches take the natively sequenced hop
-    # (ops.use_fused_hop), whose kernels are not visible from Python: the pass composes the hops from the per-kernel entry points.
     GEMM_STEPS = 3
-    ins = instrumented_pass(run_eager, timed, sync, GEMM_STEPS)
-    if n_fwd == 0:
-        fwd_ms, n_fwd = ins['edge_fwd_ms'], ins['n_edge_fwd']
-    bwd_ms, n_bwd = ins['edge_bwd_ms'], ins['n_edge_bwd']
+    if args.full:
+        fwd_ms, n_fwd = timed.mean_ms('edge_attn_fwd')
+        prep_ms, _ = timed.mean_ms('graph_prep' if args.edge_lists else 'graph_from_blobs')
+        # the ~72 GEMM launches per step are bracketed in a separate short pass: 144 more event records per step would cost the
+        # headline number ~2 %.  The backward edge stage is timed there too, with the weight-gradient overlap switched off: in the
+        # timed regions above those GEMMs run on a side stream UNDER the edge backward (ops.WGRAD_OVERLAP), so an event pair around
+        # either would measure the co-running kernels, not the kernel.  Host-bound batches take the natively sequenced hop
+        # (ops.use_fused_hop), whose kernels are not visible from Python: the pass composes the hops from the per-kernel entry points.
+        ins = instrumented_pass(run_eager, timed, sync, GEMM_STEPS)
+        if n_fwd == 0:
+            fwd_ms, n_fwd = ins['edge_fwd_ms'], ins['n_edge_fwd']
+        bwd_ms, n_bwd = ins['edge_bwd_ms'], ins['n_edge_bwd']
     total_subgraphs = my_questions * nc
     if world > 1:
         import torch.distributed as dist
@@ -860,40 +911,42 @@ def main():
         E = b['ei'].size(1)
         h2d = b['blobs'].numel() * 4 if not args.edge_lists else (b['ei'].numel() + b['et'].numel()) * 8
         Ep = E + N
-        gemm_ms, gemm_flops = ins['gemm_ms'], ins['gemm_flops']
-        alg_fwd = Ep * 2410 + N * 800
-        alg_bwd = Ep * 5610 + N * 800
-        DP = 4 * ((D // 4 + 3) // 4 * 4)  # head-padded row width (208 floats at d = 200)
-        # node rows whose only edge is their self loop (PAD rows, isolated nodes): the edge kernels read their M row only
-        deg = torch.bincount(b['ei'][0], minlength=N) + torch.bincount(b['ei'][1], minlength=N)
-        n_lone = int((deg == 0).sum().item())
-        compulsory = (N - n_lone) * 3 * DP * 4 + n_lone * DP * 4 + Ep * 10 + N * DP * 4 + 2 * Ep * 16
-        traffic, traffic_source = None, None
-        measure_edge_traffic.backward = None
-        if world == 1 and not args.no_pmc and not args.pmc_child:
-            traffic, traffic_source = measure_edge_traffic(args, N, DP)
-        bwd_traffic = measure_edge_traffic.backward
-        if traffic is None:
-            why = traffic_source
-            pmc_path = os.path.join(ROOT, 'profiles', 'pmc_edge_fwd.json')
-            if os.path.exists(pmc_path) and B == 320:
-                with open(pmc_path) as f:
-                    pj = json.load(f)
-                traffic = pj['traffic_bytes_per_launch']
-                traffic_source = ('NOT measured in this run' + (f' ({why})' if why else '') + ': committed profiles/pmc_edge_fwd.json'
-                                  + (f" of build {pj['commit']}" if 'commit' in pj else ''))
-        hbm_bytes = max(compulsory, traffic or 0)
-        achieved = hbm_bytes / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
-        achieved_alg = alg_fwd / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
-        gemm_tf = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        bwd_comp = N * 4 * DP * 4 + Ep * 14 + N * 3 * DP * 4 + 4 * Ep * 16
+        if args.full:
+            gemm_ms, gemm_flops = ins['gemm_ms'], ins['gemm_flops']
+            alg_fwd = Ep * 2410 + N * 800
+            alg_bwd = Ep * 5610 + N * 800
+            DP = 4 * ((D // 4 + 3) // 4 * 4)  # head-padded row width (208 floats at d = 200)
+            # node rows whose only edge is their self loop (PAD rows, isolated nodes): the edge kernels read their M row only
+            deg = torch.bincount(b['ei'][0], minlength=N) + torch.bincount(b['ei'][1], minlength=N)
+            n_lone = int((deg == 0).sum().item())
+            compulsory = (N - n_lone) * 3 * DP * 4 + n_lone * DP * 4 + Ep * 10 + N * DP * 4 + 2 * Ep * 16
+            traffic, traffic_source = None, None
+            measure_edge_traffic.backward = None
+            if world == 1 and not args.no_pmc and not args.pmc_child:
+                traffic, traffic_source = measure_edge_traffic(args, N, DP)
+            bwd_traffic = measure_edge_traffic.backward
+            if traffic is None:
+                why = traffic_source
+                pmc_path = os.path.join(ROOT, 'profiles', 'pmc_edge_fwd.json')
+                if os.path.exists(pmc_path) and B == 320:
+                    with open(pmc_path) as f:
+                        pj = json.load(f)
+                    traffic = pj['traffic_bytes_per_launch']
+                    traffic_source = ('NOT measured in this run' + (f' ({why})' if why else '') + ': committed profiles/pmc_edge_fwd.json'
+                                      + (f" of build {pj['commit']}" if 'commit' in pj else ''))
+            hbm_bytes = max(compulsory, traffic or 0)
+            achieved = hbm_bytes / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
+            achieved_alg = alg_fwd / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
+            gemm_tf = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            bwd_comp = N * 4 * DP * 4 + Ep * 14 + N * 3 * DP * 4 + 4 * Ep * 16
         out = {
             'metric': 'QA-subgraphs/sec (batch x num_choice) fwd+bwd', 'value': round(total_subgraphs * args.steps / dt, 1),
             'unit': 'QA-subgraphs/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': scaling, 'vs_baseline': None,
             'dtype': 'f32', 'data': 'synthetic',  # fp32 storage and fp32-accurate arithmetic everywhere (see roofline_mfma.note)
             'repeats': len(regions), 'repeat_ms_per_step': [round(r[0] / args.steps * 1e3, 3) for r in regions],
-            'value_is': f'median of {len(regions)} timed regions of {args.steps} steps each (max over ranks per region)',
+            'value_is': (f'median of {len(regions)} timed regions of {args.steps} steps each (max over ranks per region)' if len(regions) > 1 else
+                         f'one timed region of {args.steps} steps (max over ranks)'),
             'host_enqueue_ms_per_step': round(enq / args.steps * 1e3, 3), 'host_bound': bool(enq > 0.9 * dt),
             'hip_graph': ((f'one hipGraph replay per step ({gs.n_graphs} capture(s): qagnn_amd.graphed.GraphedStep; side streams in the capture: '
                            f'graph preparation {bool(gs.overlap and ops.PREP_OVERLAP)}, weight gradients {bool(gs.overlap and gs.wgrad_overlap and ops.WGRAD_OVERLAP)})'
@@ -904,63 +957,66 @@ def main():
                        'graph_input': ('int64 (edge_index, edge_type), orderings derived per batch' if args.edge_lists else
                                        'load-time int32 blobs (qagnn_graph_from_blobs)') + f', {h2d / max(E, 1):.1f} B/edge on the wire',
                        'parallelism': f'dp{world}' if world > 1 else 'single'},
-            'roofline': {'bound': 'hbm', 'kernel': 'qagnn_edge_attn_fwd_f32 (scores + segment softmax, aggregate), per GAT layer',
-                         'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(min(achieved / HBM_PEAK_GBS, 1.0), 4),
-                         'traffic': traffic, 'traffic_source': traffic_source,
-                         'hbm_bytes_per_launch': hbm_bytes, 'hbm_bytes_are': 'measured traffic' if (traffic or 0) >= compulsory else 'compulsory bytes',
-                         'compulsory_bytes_per_launch': compulsory, 'self_loop_only_rows': n_lone,
-                         'note': 'achieved = max(compulsory bytes, measured fabric traffic) / average launch duration: bytes that physically cross '
-                                 'the HBM interface.  The per-edge row gathers of the SURVEY 8d byte model are re-reads served by L1/L2; they are '
-                                 'reported as achieved_algorithmic and are not an HBM fraction',
-                         'algorithmic_bytes_per_launch': alg_fwd, 'achieved_algorithmic': round(achieved_alg, 1),
-                         'frac_algorithmic': round(achieved_alg / HBM_PEAK_GBS, 4),
-                         'frac_algorithmic_is': 'SURVEY 8d contractual figure: (E\' * 2410 + N * 800) algorithmic bytes / launch duration / 8 TB/s.  '
-                                                'Above 1 it cannot be an HBM fraction: the per-edge row gathers are L1/L2 re-reads (see `frac` for bytes '
-                                                'that cross the HBM interface)',
-                         'avg_launch_ms': round(fwd_ms, 4), 'launches_timed': n_fwd,
-                         'backward': {'algorithmic_bytes_per_launch': alg_bwd, 'avg_launch_ms': round(bwd_ms, 4), 'launches_timed': n_bwd,
-                                      'compulsory_bytes_per_launch': bwd_comp,
-                                      'traffic': bwd_traffic,
-                                      'traffic_source': ('the same two rocprofv3 --pmc passes as the forward figure (mean per launch summed over the '
-                                                         'kernels of qagnn_edge_attn_bwd_f32, FETCH doubled)' if bwd_traffic else None),
-                                      'traffic_over_compulsory': round(bwd_traffic / bwd_comp, 3) if bwd_traffic else None,
-                                      'achieved': round(max(bwd_comp, bwd_traffic or 0) / (bwd_ms * 1e-3) / 1e9, 1) if bwd_ms > 0 else 0.0,
-                                      'frac': round(min(max(bwd_comp, bwd_traffic or 0) / (bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 1.0), 4) if bwd_ms > 0 else 0.0,
-                                      'achieved_algorithmic': round(alg_bwd / (bwd_ms * 1e-3) / 1e9, 1) if bwd_ms > 0 else 0.0,
-                                      'timed_in': 'extra steps after the timed regions, weight-gradient overlap off (see source)'}},
-            # the dense side of the step: every GEMM launch, algorithmic FLOPs of the products over their HIP-event time
-            'roofline_mfma': {'bound': 'mfma', 'kernel': 'all GEMM launches of the step (NN products qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_f32, weight-gradient '
-                                                         'products qagnn_gemm_tn_h2_f32 / qagnn_gemm_tn_f32 / qagnn_gemm_tn2_f32 incl. their chunk sums)',
-                              'achieved': round(gemm_tf, 1), 'unit': 'TFLOP/s',
-                              'peak': round(MFMA_BF16_PEAK_TFLOPS / 3.0, 1), 'frac': round(gemm_tf / (MFMA_BF16_PEAK_TFLOPS / 3.0), 4),
-                              'peak_is': 'fp32-equivalent ceiling of the form the large products run in: dense fp16 MFMA peak 2500 TFLOP/s / 3 MFMAs per product '
-                                         '(scaled two-piece fp16 split); the products without a known operand maximum (input stage, class tables: '
-                                         '~8 % of the FLOPs) run six bf16 MFMAs per product and are held to the same ceiling',
-                              'peak_six_mfma': round(MFMA_BF16_PEAK_TFLOPS / 6.0, 1), 'frac_of_six_mfma_peak': round(gemm_tf / (MFMA_BF16_PEAK_TFLOPS / 6.0), 4),
-                              'peak_fp32_mfma': MFMA_F32_PEAK_TFLOPS, 'frac_of_fp32_mfma_peak': round(gemm_tf / MFMA_F32_PEAK_TFLOPS, 4),
-                              'gflop_per_step': round(gemm_flops / 1e9, 1), 'ms_per_step': round(gemm_ms, 3),
-                              'ms_per_step_nn': round(ins['gemm_nn_ms'], 3) if ins.get('gemm_nn_ms') is not None else None,
-                              'ms_per_step_tn': round(ins['gemm_tn_ms'], 3) if ins.get('gemm_tn_ms') is not None else None,
-                              'ms_per_step_six_mfma_form': round(ins['gemm_ms_composed'], 3),
-                              'useful_gflop_per_step': round(ins['gemm_useful_flops'] / 1e9, 1),
-                              'achieved_useful': round(ins['gemm_useful_flops'] / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms > 0 else 0.0,
-                              'frac_useful': round(ins['gemm_useful_flops'] / (gemm_ms * 1e-3) / 1e12 / (MFMA_BF16_PEAK_TFLOPS / 3.0), 4) if gemm_ms > 0 else 0.0,
-                              'useful_is': 'FLOPs of the same products at the reference\'s tensor widths (d = 200 for the stored 208, K|M|Q 600 for 624, the '
-                                           'score embedding 100 for 112): `achieved` counts what the launches execute on head-padded operands',
-                              'launches_per_step': ins['gemm_launches'],
-                              'timed_in': f'{GEMM_STEPS} extra eager steps after the timed regions on the path the timed regions take (natively sequenced stack), '
-                                          'HIP events on the launch stream around every GEMM entry point INSIDE the library (qagnn_timing_enable), '
-                                          'weight-gradient side stream off; FLOPs and launch count from a composed pass over the same products '
-                                          '(`ms_per_step_six_mfma_form` is that pass: the per-kernel entry points called from Python, every product as six bf16 MFMAs)',
-                              'note': 'fp32-equivalent FLOPs, fp32 storage.  Round 6: every product of the stack whose A operand carries its maximum (left '
-                                      'behind by the kernel that wrote it) runs as THREE fp16 MFMAs on an error-corrected two-piece split with exact '
-                                      'power-of-two operand scales (Ootomo & Yokota 2022): |error| <= 2^-21 sum_k |a_k b_k| + 2^-38 K max|A| max|B col| per '
-                                      'output, below the sqrt(K) 2^-24 accumulation noise of an fp32 dot product at K >= 208 (csrc/gemm_nn2.hip header); '
-                                      'the others as six bf16 MFMAs on the exact 3-way split (<= 2^-23 per product).  QAGNN_GEMM_SPLIT=1 pins the six-MFMA '
-                                      'form everywhere, =0 the fp32-MFMA kernels'},
-            'breakdown_ms_per_step': {'edge_fwd_x5': round(fwd_ms * K_LAYERS, 3), 'edge_bwd_x5': round(bwd_ms * K_LAYERS, 3),
-                                      'graph_prep': round(prep_ms, 3), 'mfma_gemms': round(gemm_ms, 3)},
         }
+        if args.full:
+            out.update({
+                'roofline': {'bound': 'hbm', 'kernel': 'qagnn_edge_attn_fwd_f32 (scores + segment softmax, aggregate), per GAT layer',
+                             'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(min(achieved / HBM_PEAK_GBS, 1.0), 4),
+                             'traffic': traffic, 'traffic_source': traffic_source,
+                             'hbm_bytes_per_launch': hbm_bytes, 'hbm_bytes_are': 'measured traffic' if (traffic or 0) >= compulsory else 'compulsory bytes',
+                             'compulsory_bytes_per_launch': compulsory, 'self_loop_only_rows': n_lone,
+                             'note': 'achieved = max(compulsory bytes, measured fabric traffic) / average launch duration: bytes that physically cross '
+                                     'the HBM interface.  The per-edge row gathers of the SURVEY 8d byte model are re-reads served by L1/L2; they are '
+                                     'reported as achieved_algorithmic and are not an HBM fraction',
+                             'algorithmic_bytes_per_launch': alg_fwd, 'achieved_algorithmic': round(achieved_alg, 1),
+                             'frac_algorithmic': round(achieved_alg / HBM_PEAK_GBS, 4),
+                             'frac_algorithmic_is': 'SURVEY 8d contractual figure: (E\' * 2410 + N * 800) algorithmic bytes / launch duration / 8 TB/s.  '
+                                                    'Above 1 it cannot be an HBM fraction: the per-edge row gathers are L1/L2 re-reads (see `frac` for bytes '
+                                                    'that cross the HBM interface)',
+                             'avg_launch_ms': round(fwd_ms, 4), 'launches_timed': n_fwd,
+                             'backward': {'algorithmic_bytes_per_launch': alg_bwd, 'avg_launch_ms': round(bwd_ms, 4), 'launches_timed': n_bwd,
+                                          'compulsory_bytes_per_launch': bwd_comp,
+                                          'traffic': bwd_traffic,
+                                          'traffic_source': ('the same two rocprofv3 --pmc passes as the forward figure (mean per launch summed over the '
+                                                             'kernels of qagnn_edge_attn_bwd_f32, FETCH doubled)' if bwd_traffic else None),
+                                          'traffic_over_compulsory': round(bwd_traffic / bwd_comp, 3) if bwd_traffic else None,
+                                          'achieved': round(max(bwd_comp, bwd_traffic or 0) / (bwd_ms * 1e-3) / 1e9, 1) if bwd_ms > 0 else 0.0,
+                                          'frac': round(min(max(bwd_comp, bwd_traffic or 0) / (bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 1.0), 4) if bwd_ms > 0 else 0.0,
+                                          'achieved_algorithmic': round(alg_bwd / (bwd_ms * 1e-3) / 1e9, 1) if bwd_ms > 0 else 0.0,
+                                          'timed_in': 'extra steps after the timed regions, weight-gradient overlap off (see source)'}},
+                # the dense side of the step: every GEMM launch, algorithmic FLOPs of the products over their HIP-event time
+                'roofline_mfma': {'bound': 'mfma', 'kernel': 'all GEMM launches of the step (NN products qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_f32, weight-gradient '
+                                                             'products qagnn_gemm_tn_h2_f32 / qagnn_gemm_tn_f32 / qagnn_gemm_tn2_f32 incl. their chunk sums)',
+                                  'achieved': round(gemm_tf, 1), 'unit': 'TFLOP/s',
+                                  'peak': round(MFMA_BF16_PEAK_TFLOPS / 3.0, 1), 'frac': round(gemm_tf / (MFMA_BF16_PEAK_TFLOPS / 3.0), 4),
+                                  'peak_is': 'fp32-equivalent ceiling of the form the large products run in: dense fp16 MFMA peak 2500 TFLOP/s / 3 MFMAs per product '
+                                             '(scaled two-piece fp16 split); the products without a known operand maximum (input stage, class tables: '
+                                             '~8 % of the FLOPs) run six bf16 MFMAs per product and are held to the same ceiling',
+                                  'peak_six_mfma': round(MFMA_BF16_PEAK_TFLOPS / 6.0, 1), 'frac_of_six_mfma_peak': round(gemm_tf / (MFMA_BF16_PEAK_TFLOPS / 6.0), 4),
+                                  'peak_fp32_mfma': MFMA_F32_PEAK_TFLOPS, 'frac_of_fp32_mfma_peak': round(gemm_tf / MFMA_F32_PEAK_TFLOPS, 4),
+                                  'gflop_per_step': round(gemm_flops / 1e9, 1), 'ms_per_step': round(gemm_ms, 3),
+                                  'ms_per_step_nn': round(ins['gemm_nn_ms'], 3) if ins.get('gemm_nn_ms') is not None else None,
+                                  'ms_per_step_tn': round(ins['gemm_tn_ms'], 3) if ins.get('gemm_tn_ms') is not None else None,
+                                  'ms_per_step_six_mfma_form': round(ins['gemm_ms_composed'], 3),
+                                  'useful_gflop_per_step': round(ins['gemm_useful_flops'] / 1e9, 1),
+                                  'achieved_useful': round(ins['gemm_useful_flops'] / (gemm_ms * 1e-3) / 1e12, 1) if gemm_ms > 0 else 0.0,
+                                  'frac_useful': round(ins['gemm_useful_flops'] / (gemm_ms * 1e-3) / 1e12 / (MFMA_BF16_PEAK_TFLOPS / 3.0), 4) if gemm_ms > 0 else 0.0,
+                                  'useful_is': 'FLOPs of the same products at the reference\'s tensor widths (d = 200 for the stored 208, K|M|Q 600 for 624, the '
+                                               'score embedding 100 for 112): `achieved` counts what the launches execute on head-padded operands',
+                                  'launches_per_step': ins['gemm_launches'],
+                                  'timed_in': f'{GEMM_STEPS} extra eager steps after the timed regions on the path the timed regions take (natively sequenced stack), '
+                                              'HIP events on the launch stream around every GEMM entry point INSIDE the library (qagnn_timing_enable), '
+                                              'weight-gradient side stream off; FLOPs and launch count from a composed pass over the same products '
+                                              '(`ms_per_step_six_mfma_form` is that pass: the per-kernel entry points called from Python, every product as six bf16 MFMAs)',
+                                  'note': 'fp32-equivalent FLOPs, fp32 storage.  Round 6: every product of the stack whose A operand carries its maximum (left '
+                                          'behind by the kernel that wrote it) runs as THREE fp16 MFMAs on an error-corrected two-piece split with exact '
+                                          'power-of-two operand scales (Ootomo & Yokota 2022): |error| <= 2^-21 sum_k |a_k b_k| + 2^-38 K max|A| max|B col| per '
+                                          'output, below the sqrt(K) 2^-24 accumulation noise of an fp32 dot product at K >= 208 (csrc/gemm_nn2.hip header); '
+                                          'the others as six bf16 MFMAs on the exact 3-way split (<= 2^-23 per product).  QAGNN_GEMM_SPLIT=1 pins the six-MFMA '
+                                          'form everywhere, =0 the fp32-MFMA kernels'},
+                'breakdown_ms_per_step': {'edge_fwd_x5': round(fwd_ms * K_LAYERS, 3), 'edge_bwd_x5': round(bwd_ms * K_LAYERS, 3),
+                                          'graph_prep': round(prep_ms, 3), 'mfma_gemms': round(gemm_ms, 3)},
+            })
         if world > 1:
             out['comm_ms_per_step'] = round(comm_ms, 4)
             out['comm_fraction_of_step'] = round(comm_ms / (dt / args.steps * 1e3), 4)
@@ -969,7 +1025,7 @@ def main():
             out['rank_ms_per_step'] = {'min': round(dt_min / args.steps * 1e3, 3), 'max': round(dt / args.steps * 1e3, 3)}
             if balance is not None:
                 out['balance'] = balance
-        if world == 1 and not args.pmc_child:
+        if world == 1 and not args.pmc_child and args.full:
             if not args.no_cpu_baseline:
                 out['small_batch'] = gpu_small_batch(wl, args, dev)
                 out['cpu_baseline'] = cpu_oracle(wl, budget_s=10.0)

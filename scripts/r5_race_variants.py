@@ -79,7 +79,7 @@ def poll(self, block=False):
 
 L._ErrWatch.watch, L._ErrWatch.after_replay, L._ErrWatch.poll = watch, after_replay, poll
 import bench
-sys.argv = ['bench.py', '--steps', '5', '--warmup', '2', '--repeats', '1', '--no-cpu-baseline', '--no-pmc', '--no-configs']
+sys.argv = ['bench.py', '--full', '--steps', '5', '--warmup', '2', '--repeats', '1', '--no-cpu-baseline', '--no-pmc', '--no-configs']
 try:
     bench.main()
 except Exception as e:

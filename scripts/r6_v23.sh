@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT
 timeout 600 python -m pytest tests/test_hip_kernels.py -x -q -m gpu -k "gemm_tn or three_mfma or native_hop or fused_hop" 2>&1 | tail -3
 for rep in 1 2; do for lib in tools/bin/libqagnn_hip_tn2rounds.so ""; do
-  QAGNN_LIB=$lib timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-configs 2>/dev/null | python -c "
+  QAGNN_LIB=$lib timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline_mfma']; print('lib=${lib:-default(one round)}', d['value'], d['ms_per_step'], d['repeat_ms_per_step'], 'gemms', r['ms_per_step'], r['ms_per_step_nn'], r['ms_per_step_tn'])"
 done; done | tee gpurun_out/r6_v23_ab.txt

@@ -1,10 +1,11 @@
 cd $GRAFT_REPO_ROOT
-timeout 2400 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 > gpurun_out/r6_v33_tests.txt
-tail -2 gpurun_out/r6_v33_tests.txt | cut -c1-200
-timeout 1200 python bench.py > gpurun_out/r6_v33_bench.json 2> gpurun_out/r6_v33_bench.err; tail -2 gpurun_out/r6_v33_bench.err | cut -c1-300
+OUT=${OUT:-results}; mkdir -p "$OUT"; export OUT  # where this script leaves its logs
+timeout 2400 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 > $OUT/r6_v33_tests.txt
+tail -2 $OUT/r6_v33_tests.txt | cut -c1-200
+timeout 1200 python bench.py --full > $OUT/r6_v33_bench.json 2> $OUT/r6_v33_bench.err; tail -2 $OUT/r6_v33_bench.err | cut -c1-300
 python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r6_v33_bench.json').read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.environ['OUT'] + '/r6_v33_bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['repeat_ms_per_step'], d.get('breakdown_ms_per_step'), d['small_batch']['ms_per_step'])
 print({k:(v.get('value'), v.get('ms_per_step')) for k,v in d['configs'].items()})
 r=d['roofline']; print(r['frac'], r['avg_launch_ms'], r['traffic'], r['backward']['avg_launch_ms'], r['backward'].get('traffic_over_compulsory'))
@@ -13,8 +14,8 @@ print(d['optimizer']['reference_operating_point']['ms_per_optimizer_step'], d['c
 PY
 python __graft_entry__.py smoke 2>&1 | tail -1
 REPO=$PWD; rm -rf /tmp/prof; mkdir -p /tmp/prof
-( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r6 -- python "$REPO/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-configs ) > gpurun_out/r6_v33_prof.log 2>&1
-find /tmp/prof -name "*kernel_stats*.csv" -exec cp {} gpurun_out/r6_v33_kernel_stats.csv \;
-head -12 gpurun_out/r6_v33_kernel_stats.csv | cut -c1-160
+( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r6 -- python "$REPO/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-configs ) > $OUT/r6_v33_prof.log 2>&1
+find /tmp/prof -name "*kernel_stats*.csv" -exec cp {} $OUT/r6_v33_kernel_stats.csv \;
+head -12 $OUT/r6_v33_kernel_stats.csv | cut -c1-160
 bash scripts/r6_prof.sh r6_v33_final 2 > /dev/null 2>&1
-python scripts/sum_by_shape.py gpurun_out/r6_v33_final_by_shape.txt 20
+python scripts/sum_by_shape.py $OUT/r6_v33_final_by_shape.txt 20

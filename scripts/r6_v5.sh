@@ -1,9 +1,10 @@
 cd $GRAFT_REPO_ROOT
-timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -15 > gpurun_out/r6_v5_tests.txt
-cat gpurun_out/r6_v5_tests.txt
-timeout 900 python bench.py > gpurun_out/r6_v5_bench.json 2> gpurun_out/r6_v5_bench.err
+OUT=${OUT:-results}; mkdir -p "$OUT"; export OUT  # where this script leaves its logs
+timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -15 > $OUT/r6_v5_tests.txt
+cat $OUT/r6_v5_tests.txt
+timeout 900 python bench.py --full > $OUT/r6_v5_bench.json 2> $OUT/r6_v5_bench.err
 python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r6_v5_bench.json').read().strip().splitlines()[-1])
+import json, os
+d=json.loads(open(os.environ['OUT'] + '/r6_v5_bench.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('breakdown_ms_per_step'), d['small_batch']['ms_per_step'])
 PY
