@@ -197,6 +197,11 @@ int qagnn_gemm_nn_prepack_f32(const qagnn_pack_desc* d, int32_t n, void* out, in
 int qagnn_gemm_nn_prepack_clear(int64_t tag);
 int qagnn_gemm_nn_split_ws_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
                                void* ws, int64_t ws_bytes, qagnn_stream_t stream);
+/* TESTS AND A/B RUNS ONLY.  The row count from which an NN product takes a packed B image (qagnn_gemm_nn_ws_bytes, the pre-packed
+ * registry) and, given its operand maxima, the three-MFMA form -- in qagnn_gemm_nn_split*_f32 and in the natively sequenced hops
+ * (qagnn_hop_args.amax).  Default 8192.  ONE PROCESS-WIDE VALUE, read at every call on every device and thread: it is not a setting
+ * of a product or a stream.  rows >= 1 sets it (rows below 1 count as 1) and returns the previous value; rows < 0 only returns it. */
+int64_t qagnn_packed_min_rows(int64_t rows);
 
 /* max |x| over n floats (n % 4 == 0, x 16-byte aligned), merged into *slot by an integer atomic max on the bit pattern -- order-independent, hence
  * deterministic; the caller zeroes the word first (qagnn_zero_words).  The operand maxima of the three-MFMA GEMM form (a_amax1 / a_amax2 above,

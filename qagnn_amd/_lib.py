@@ -23,10 +23,10 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_edge_attn_fwd_f32', 'qagnn_edge_attn_bwd_f32',
            'qagnn_hop_fwd_workspace_elems', 'qagnn_hop_bwd_workspace_elems', 'qagnn_hop_fwd_f32', 'qagnn_hop_bwd_f32',
            'qagnn_stack_fwd_f32', 'qagnn_stack_bwd_f32', 'qagnn_absmax_f32', 'qagnn_zero_words', 'qagnn_gemm_tn_h2_f32', 'qagnn_gelu_dropout_fwd_amax_f32', 'qagnn_gelu_dropout_amax_scratch_elems',
-           'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32']
+           'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
-ABI_VERSION = 21  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows)
+ABI_VERSION = 22  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows)
 
 _i32, _i64, _f32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p
 
@@ -113,6 +113,8 @@ def load_library(path=LIB_PATH):
     lib.qagnn_zero_words.argtypes = [_vp, _i64, _vp]
     lib.qagnn_timing_enable.argtypes = [_i32]
     lib.qagnn_timing_read.argtypes = [_vp, _vp]
+    lib.qagnn_packed_min_rows.restype = _i64
+    lib.qagnn_packed_min_rows.argtypes = [_i64]
     lib.qagnn_gemm_tn_colsum_f32.argtypes = [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                                              _vp, _vp]
     lib.qagnn_colreduce_workspace_elems.restype = _i64
@@ -317,7 +319,7 @@ class HipKernels(metaclass=_GuardedMeta):
         # known -- inside the natively sequenced hops; 1 pins the exact 3 x bf16 split everywhere; 3 asks for the REDUCED-PRECISION form
         # (ONE fp16 MFMA per product where 2 takes three: the GEMM arithmetic of the reference under its --fp16 autocast; never a default)
         self.gemm_split = {'0': 0, '1': 1, '3': 3}.get(os.environ.get('QAGNN_GEMM_SPLIT', '2'), 2)
-        self.PACK_MIN_M = 8192  # (the library applies the same threshold: nn2_packed_ok)
+        self.PACK_MIN_M = int(self.lib.qagnn_packed_min_rows(-1))  # (the library's own threshold: nn2_packed_ok, hop_h2; packed_min_rows)
         self._side_streams = {}  # per device: the stream the natively sequenced hops put their weight-gradient products on
 
     # -- helpers -----------------------------------------------------------------------------------------------
@@ -766,6 +768,13 @@ class HipKernels(metaclass=_GuardedMeta):
         assert dK.is_contiguous() and dZ.is_contiguous() and dZ.shape == (B, Cc)
         self._check(self.lib.qagnn_add_row0_f32(dK.data_ptr(), n * Cc, dZ.data_ptr(), B, Cc, self._stream()), 'qagnn_add_row0_f32')
         return dK
+
+    def packed_min_rows(self, rows):
+        """Tests and A/B runs only: the library's row threshold for packed B images and the three-MFMA form (qagnn_packed_min_rows) and this
+        provider's copy of it, together.  Process-wide -- every provider of the process sees it.  Returns the previous value."""
+        old = int(self.lib.qagnn_packed_min_rows(int(rows)))
+        self.PACK_MIN_M = int(self.lib.qagnn_packed_min_rows(-1))
+        return old
 
     def timing_enable(self, on):
         """Library-side HIP-event brackets around the GEMM and edge-stage entry points (qagnn_timing_enable): measurement harnesses only."""

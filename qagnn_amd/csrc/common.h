@@ -25,6 +25,7 @@ bool nn2_ok(const qagnn_gemm_nn_args& a, int ldn1, int ldn2);
 int launch_nn2(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
 // np: the arithmetic form of a packed image -- 3 = exact 3 x bf16 split, 2 = scaled two-piece fp16 split (gemm_nn2.hip, header)
 int64_t nn2_pack_bytes(int No, int K1, int K2, int np = 3);
+int64_t nn2_pack_min_m();  // rows from which products take the packed B image and the three-MFMA form (qagnn_packed_min_rows)
 bool nn2_packed_ok(const qagnn_gemm_nn_args& a, int64_t ws_bytes, int np = 3);
 bool nn2_h2_ok(const qagnn_gemm_nn_args& a);
 const void* nn2_prepack_lookup(const float* B1n, int ldn1, int K1, const float* B2n, int ldn2, int K2, int No, int np = 3);

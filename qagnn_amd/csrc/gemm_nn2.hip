@@ -47,6 +47,8 @@
 // 16-byte stores; bias / row table / accumulate / BatchNorm column statistics).
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "common.h"
 
 namespace qagnn {
@@ -841,10 +843,12 @@ static int walk_tiles(int K1, int K2) {
 }  // namespace nn2
 
 // Which form a product takes (the A/B runs of the forms against each other: profiles/r4_run16_nn2_stagger.txt, r4_run28_round4_switches_ab.txt):
-// B packed once per product (k_pack_b) wherever the caller hands over a workspace and the product has at least NN2_PACK_MIN_M rows, the
+// B packed once per product (k_pack_b) wherever the caller hands over a workspace and the product has at least nn2_pack_min_m() rows, the
 // in-kernel split otherwise; the staggered 8-wave block wherever a packed product has at least one 256-row tile per CU.
-constexpr int NN2_PACK_MIN_M = 8192;
-bool nn2_packed_ok(const qagnn_gemm_nn_args& a, int64_t ws_bytes, int np) { return a.M >= NN2_PACK_MIN_M && ws_bytes >= nn2_pack_bytes(a.No, a.K1, a.K2, np); }
+// The threshold is one process-wide value (qagnn_packed_min_rows: tests lower it to run small products in the packed forms).
+static std::atomic<int64_t> g_pack_min_m{8192};
+int64_t nn2_pack_min_m() { return g_pack_min_m.load(std::memory_order_relaxed); }
+bool nn2_packed_ok(const qagnn_gemm_nn_args& a, int64_t ws_bytes, int np) { return a.M >= nn2_pack_min_m() && ws_bytes >= nn2_pack_bytes(a.No, a.K1, a.K2, np); }
 // Measured at M = 64 000 (tools/nn2_ablate.hip, profiles/r4_run16_nn2_stagger.txt), 4-wave blocks -> staggered block:
 // [208|112] -> 624 141 -> 122 us, 624 -> 208 96..101 -> 79, but 208 -> 208 38 -> 39 and 624 -> 112 (NT = 7) 53 -> 54: with one block per
 // CU nothing runs under a tile's first loads, and the last tiles' stores are a tail at HBM speed, which 10 k-tiles of 13 column tiles
@@ -915,7 +919,7 @@ int64_t nn2_pack_bytes(int No, int K1, int K2, int np) {
   return np <= 2 ? img + (((int64_t)cdiv(No, 16) + 13) * 4 + 15) / 16 * 16 : img;
 }
 // (h2_ok: what the two-piece form additionally asks of a product -- a known maximum of A and a finite-size image)
-bool nn2_h2_ok(const qagnn_gemm_nn_args& a) { return a.a_amax1 != nullptr && (a.K2 == 0 || a.a_amax2 != nullptr) && a.M >= NN2_PACK_MIN_M; }
+bool nn2_h2_ok(const qagnn_gemm_nn_args& a) { return a.a_amax1 != nullptr && (a.K2 == 0 || a.a_amax2 != nullptr) && a.M >= nn2_pack_min_m(); }
 
 // pack B into `ws` (>= nn2_pack_bytes), then the PACKED kernel: two launches
 int launch_nn2_packed(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream, int np) {
@@ -963,6 +967,10 @@ int launch_nn2_prepacked(int nt, const qagnn_gemm_nn_args& a, const void* pk, hi
 }  // namespace qagnn
 
 using namespace qagnn;
+
+extern "C" int64_t qagnn_packed_min_rows(int64_t rows) {
+  return rows < 0 ? g_pack_min_m.load() : g_pack_min_m.exchange(rows > 1 ? rows : 1);
+}
 
 extern "C" int64_t qagnn_gemm_nn_prepack_bytes(const qagnn_pack_desc* d, int32_t n) {
   int64_t tot = 0;

@@ -57,8 +57,8 @@ struct HopAmax {
   uint32_t* y;      // where this hop's GELU / dropout leaves max |y|
   uint32_t* own;    // the hop's own block
 };
-// The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays from NN2_PACK_MIN_M rows on (packed B images)
-static bool hop_h2(const qagnn_hop_args* h) { return h->gemm_split >= 2 && h->amax != nullptr && h->batch_stats && h->N >= 8192; }
+// The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays from nn2_pack_min_m() rows on (packed B images)
+static bool hop_h2(const qagnn_hop_args* h) { return h->gemm_split >= 2 && h->amax != nullptr && h->batch_stats && h->N >= nn2_pack_min_m(); }
 // gemm_split == 3: the reduced-precision form (one fp16 MFMA per product) wherever 2 would take three
 static int hop_pieces(const qagnn_hop_args* h) { return h->gemm_split == 3 ? 1 : 0; }
 typedef int (*tn_scaled_fn)(const float*, int32_t, int32_t, const float*, int32_t, int32_t, const float*, int32_t, float*, int32_t, int32_t, int32_t,

@@ -389,7 +389,13 @@ def graph_prep_async(adj, node_type, n_etype, n_ntype, block_n):
 # the tests still flip GATHER_FUSED to compare the one-launch gather with the cat + index_select form it replaces)
 GATHER_FUSED = True     # GatherPlan through qagnn_gather_multi{,_sum}_f32
 HEAD_FUSED = True       # the head behind the pooling as two kernels each way
-PREPACK_MIN_ROWS = 8192  # = the library's threshold for packed B images (csrc/gemm_nn2.hip: nn2_packed_ok)
+
+
+def pack_min_rows(K):
+    """the row count from which products take packed B images and, with their operand maxima, the three-MFMA form: the library's
+    one process-wide threshold (qagnn_packed_min_rows; csrc/gemm_nn2.hip nn2_packed_ok, csrc/hop.hip hop_h2) as the provider holds it
+    (a provider without it: never)"""
+    return getattr(K, 'PACK_MIN_M', math.inf)
 
 
 _PREPACK_STATE = None  # weakref.WeakKeyDictionary: owner module -> [registry tag, what must stay alive until the next forward]
@@ -404,7 +410,7 @@ def prepack_weights(owner, pairs, rows):
     is cleared when its owner is collected (the tag is a process-wide counter -- id() values are recycled, a counter is not)."""
     global _PREPACK_STATE
     K = kernels()
-    if not (rows >= PREPACK_MIN_ROWS and pairs and pairs[0][0].is_cuda and hasattr(K, 'prepack')):
+    if not (hasattr(K, 'prepack') and rows >= pack_min_rows(K) and pairs and pairs[0][0].is_cuda):
         return
     import weakref
     if _PREPACK_STATE is None:
@@ -621,7 +627,7 @@ def amax_lookup(t):
 
 def _wants_amax(K, X):
     """the provider runs the three-MFMA form and X is large enough for it (the library's own threshold: csrc/hop.hip, hop_h2)"""
-    return getattr(K, 'gemm_split', 1) >= 2 and getattr(K, 'name', '') == 'hip' and X.dim() == 2 and X.size(0) >= 8192
+    return getattr(K, 'gemm_split', 1) >= 2 and getattr(K, 'name', '') == 'hip' and X.dim() == 2 and X.size(0) >= pack_min_rows(K)
 
 
 class GeluDropoutFn(torch.autograd.Function):
@@ -928,6 +934,8 @@ class HopFn(torch.autograd.Function):
         fwd = getattr(K, 'hop_fwd', None)
         args = (graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act)
         y, saved = fwd(*args, running, tab_col) if fwd is not None else hop_fwd_composed(K, *args, running, tab_col)
+        if apply_act and len(saved) > 6 and _wants_amax(K, X) and batch_stats:  # (as StackFn: the library's condition for the form, hop_h2)
+            amax_note(y, saved[6][4:5])  # max |y| (AM_Y), left by the hop's GELU / dropout pass: the next hop or the output layer reads it
         ctx.save_for_backward(X, S, ntype, *prm, *saved)
         ctx.cfg = (graph, HP, qscale, batch_stats, eps, p, seed, apply_act, len(prm))
         ctx.tab_col = tab_col
@@ -1152,7 +1160,7 @@ class ConceptInputFn(torch.autograd.Function):
     def forward(ctx, emb_w, rowidx, Wc_t, bc, ctx_pre, n, p, seed, Wc=None):
         K = kernels()
         # (the frozen table's maximum: the gathered product then runs in the three-MFMA form like the stack's -- csrc/gemm_nn2.hip)
-        tam = table_amax(K, emb_w) if rowidx.numel() >= 8192 else None
+        tam = table_amax(K, emb_w) if rowidx.numel() >= pack_min_rows(K) else None
         pre = K.gemm_nn(emb_w, Wc_t, bias=bc, a_rowidx=rowidx, B1n=Wc if Wc is not None else Wc_t.t().contiguous(),
                         **(dict(a_amax1=tam) if tam is not None else {}))
         B = ctx_pre.size(0)

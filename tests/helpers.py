@@ -856,3 +856,51 @@ class F64Ref:
                            f'{self.n_kinks} kink groups, {n_flips} flips read for this run, {self.flips32} for the fp32 oracle):\n  '
                            + '\n  '.join(fails[:12]))
         return report
+
+
+# The three-MFMA GEMM form at every size -------------------------------------------------------------------------------------------
+# The library switches its packed B images and, where the operand maxima are known, the three-MFMA form on from one process-wide row
+# threshold (qagnn_packed_min_rows, default 8 192); the golden cases have 120 .. 2 000 node rows.  form_everywhere lowers the threshold
+# for the body of a `with` and always puts the old value back: the value is process-wide, a test that leaked it would change the
+# arithmetic of every test after it.
+class form_everywhere:
+    def __init__(self, rows=1):
+        self.rows = rows
+
+    def __enter__(self):
+        from qagnn_amd import ops
+        self.K = ops.kernels()
+        self.old = self.K.packed_min_rows(self.rows)
+        return self.K
+
+    def __exit__(self, *exc):
+        from qagnn_amd import ops
+        self.K.packed_min_rows(self.old)
+        if ops._K is not self.K and hasattr(ops._K, 'packed_min_rows'):  # (a provider the body installed: its copy of the value too)
+            ops._K.packed_min_rows(self.old)
+        return False
+
+
+FORMS = ('default', 'everywhere')
+
+
+def with_forms(values):
+    """pytest params for a test parametrised over `values` (each a scalar or a tuple of its other arguments) x form: the default form
+    keeps the id the test had before the form axis existed, the other form appends '-everywhere'.  The test module's `form` fixture
+    (indirect) applies it."""
+    import pytest
+    out = []
+    for v in values:
+        t = v if isinstance(v, tuple) else (v,)
+        vid = '-'.join(str(x) for x in t)
+        out += [pytest.param(*t, 'default', id=vid), pytest.param(*t, 'everywhere', id=vid + '-everywhere')]
+    return out
+
+
+def apply_form(name):
+    """generator body of a test module's `form` fixture"""
+    if name == 'everywhere':
+        with form_everywhere():
+            yield name
+    else:
+        yield name

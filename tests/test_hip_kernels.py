@@ -2,6 +2,7 @@
 (tests/emu_kernels.py) on the same seeded inputs.  Integer outputs must be bit-exact; fp32 outputs are checked
 against a float64 evaluation with a backward-error bound (|d| <= c * eps32 * sum|terms|).
 """
+import contextlib
 import ctypes
 import os
 
@@ -1018,13 +1019,20 @@ def test_gemm_nn_three_mfma_form(M, K1, K2, No, variant, kind):
         assert (stats[1].double() - got.double().var(0, unbiased=False)).abs().max().item() <= 1e-4 * got.double().var(0).max().item()
 
 
+# shapes the split kernels decline (tn_split_ok, csrc/gemm_split.hip: >= 1024 rows, >= 64 columns of A, >= 104 of B) fall back to the
+# six-MFMA route: asserted bit-identical to it, so that a fallback is never silent
+TN_H2_SHAPES = [pytest.param(*v, id='-'.join(map(str, v[:4])) + ('' if v[4] == 'form' or v[0] == 700 else '-fallback')) for v in (
+    (64000, 208, 112, 624, 'form'), (64000, 208, 0, 208, 'form'), (20000, 208, 0, 624, 'form'), (5000, 112, 0, 624, 'form'),
+    (2049, 208, 0, 208, 'form'), (12800, 208, 208, 208, 'form'), (700, 32, 0, 96, 'fallback: 700 rows, 32 columns of A, 96 of B'),
+    (1, 208, 0, 208, 'fallback: 1 row'), (60, 208, 112, 624, 'fallback: 60 rows'), (257, 624, 0, 208, 'fallback: 257 rows'))]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('R,Ka1,Ka2,No', [(64000, 208, 112, 624), (64000, 208, 0, 208), (20000, 208, 0, 624), (5000, 112, 0, 624), (2049, 208, 0, 208),
-                                          (12800, 208, 208, 208), (700, 32, 0, 96)])
+@pytest.mark.parametrize('R,Ka1,Ka2,No,route', TN_H2_SHAPES)
 @pytest.mark.parametrize('kind', ['plain', 'tiny', 'spread', 'affine'])
-def test_gemm_tn_three_mfma_form(R, Ka1, Ka2, No, kind):
-    """qagnn_gemm_tn_h2_f32: [A1 | A2]^T B with every operand's maximum handed over; shapes the split kernels decline fall back to the
-    six-MFMA route (same bound)."""
+def test_gemm_tn_three_mfma_form(R, Ka1, Ka2, No, route, kind):
+    """qagnn_gemm_tn_h2_f32: [A1 | A2]^T B with every operand's maximum handed over; the form ran where `route` says so (the result
+    differs from the six-MFMA route's in the last bits), the declared fallbacks ARE the six-MFMA route, bit for bit (same bound)."""
     if kind == 'affine' and Ka2:
         pytest.skip('no prologue on the two-operand product')
     g = torch.Generator().manual_seed(R + Ka1 + Ka2 + No)
@@ -1033,6 +1041,8 @@ def test_gemm_tn_three_mfma_form(R, Ka1, Ka2, No, kind):
     A2 = _ranged(g, R, Ka2, 'plain') if Ka2 else None
     kw = dict(a_scale=torch.randn(Ka1, generator=g), a_shift=torch.randn(Ka1, generator=g)) if kind == 'affine' else {}
     A1e = torch.relu(A1 * kw['a_scale'] + kw['a_shift']) if kind == 'affine' else A1
+    if kind == 'affine' and route != 'form':  # (the fallback kernels round a s + b ONCE, fmaf; the form's reference stays as it was)
+        A1e = torch.relu(A1.double() * kw['a_scale'].double() + kw['a_shift'].double()).float()
     K = hip()
     cu = lambda t: None if t is None else t.cuda()  # noqa: E731
     got = K.gemm_tn_h2(cu(A1), cu(B), K.absmax(cu(A1e.contiguous())), K.absmax(cu(B)), A2=cu(A2), amax_a2=K.absmax(cu(A2)) if Ka2 else None,
@@ -1044,6 +1054,11 @@ def test_gemm_tn_three_mfma_form(R, Ka1, Ka2, No, kind):
     err = (got.double() - ref).abs()
     assert torch.isfinite(got).all()
     assert bool((err <= bound).all()), f'max err {err.max().item():.3e}, worst bound ratio {(err / bound).max().item():.2f}'
+    six = (K.gemm_tn2(cu(A1), cu(A2), cu(B)) if Ka2 else K.gemm_tn(cu(A1), cu(B), **{k: cu(v) for k, v in kw.items()})).cpu()
+    if route == 'form' and os.environ.get('QAGNN_GEMM_SPLIT') != '0':  # (0 pins the fp32-MFMA family: every shape falls back)
+        assert not torch.equal(six, got), 'the three-MFMA form did not run: the six-MFMA route answered'
+    else:
+        assert torch.equal(six, got), f'{route}: expected the six-MFMA route'
 
 
 # ---- the REDUCED-PRECISION form (gemm_split = 3, on request only: ONE fp16 MFMA per product, csrc/gemm_nn2.hip / qagnn_gemm_nn_args.pieces) ---
@@ -1114,18 +1129,28 @@ def test_gemm_tn_reduced_precision_form(R, Ka1, Ka2, No, kind, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['big', 'big_pad'])
+@pytest.mark.parametrize('name', ['big', 'big_pad', 'csqa_b10-everywhere', 'small_train-everywhere'])
 def test_native_hop_in_the_three_mfma_form(name, monkeypatch):
     """The natively sequenced hop with gemm_split = 2 (every large product in the three-MFMA form, the operand maxima travelling from the
     producing kernels) against the same hop with the exact 3 x bf16 products: every forward buffer and every gradient within fp32
-    round-off of each other, none bit-identical (the form did run), everything finite; the amax words hold the true maxima."""
-    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, 52, 5)
-    K = hip()
-    HP, dev = 52, 'cuda'
+    round-off of each other, none bit-identical (the form did run), everything finite; the amax words hold the true maxima.
+    *-everywhere: a golden case's graph (2 000 / 120 node rows; d = 200 and d = 32) with the row threshold at 1 (helpers.form_everywhere)."""
+    name, _, form = name.partition('-')
+    hip()
+    with (helpers.form_everywhere() if form else contextlib.nullcontext()):
+        _native_hop_vs_exact(name, bool(form), monkeypatch)
+
+
+def _native_hop_vs_exact(name, small, monkeypatch):
+    from qagnn_amd import ops
+    HP = 8 if name == 'small_train' else 52
+    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5)
+    K = ops.kernels()
+    dev = 'cuda'
     g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
     gen = torch.Generator().manual_seed(78)
-    N, DP, C, SP, dh = nt.numel(), 208, R * T * T + T, 112, 50
-    assert N >= 8192
+    N, DP, C, SP = nt.numel(), 4 * HP, R * T * T + T, 112 if HP == 52 else 16
+    assert (N >= 8192) != small and K.PACK_MIN_M == (1 if small else 8192)
     rnd = lambda *shape, s=0.3: (torch.randn(*shape, generator=gen) * s).to(dev)  # noqa: E731
     Wx_t, Ws_t, W1t, W2t = rnd(DP, 3 * DP, s=0.1), rnd(SP, 3 * DP, s=0.1), rnd(DP, DP, s=0.1), rnd(DP, DP, s=0.1)
     prm = (Wx_t, Wx_t.t().contiguous(), Ws_t, Ws_t.t().contiguous(), rnd(T, 3 * DP), rnd(C, 2 * DP),
@@ -1161,5 +1186,216 @@ def test_native_hop_in_the_three_mfma_form(name, monkeypatch):
     st = f[6].cpu()
     h1n = torch.relu(f[4].cpu() * st[3] + st[4]).abs().max()
     bound = w[3:4].view(torch.float32).item()
-    assert h1n.item() <= bound <= 256 * h1n.item(), (h1n.item(), bound)
-    assert w[5].item() != 0 and w[6].item() != 0 and w[7].item() != 0
+    if DP == 208:
+        assert h1n.item() <= bound <= 256 * h1n.item(), (h1n.item(), bound)
+    else:  # (the bound rides on the fused BatchNorm statistics, 193..208 columns: without it the h1 product stays exact, csrc/hop.hip)
+        assert bound == 0.0
+    assert all(np.isfinite(_word_f(w[j])) and (w[j].item() != 0 or DP != 208) for j in (5, 6, 7))
+    if w[5].item():  # DOUT: max |d out|, out's gradient through GELU / dropout -- rebuilt from the saved `out` and dy
+        assert _word_f(w[5]) >= K.gelu_dropout_bwd(f[5].contiguous(), dy, 0.2, 4321).abs().max().item() > 0
+
+
+# ---- the three-MFMA form below the library's row threshold (qagnn_packed_min_rows lowered to 1: helpers.form_everywhere) ----------------
+# The (K1, K2, No) triples the golden cases launch (logged from their forward + backward): d = 200 -> DP = 208 with the 112-wide S, incl.
+# the straddling k-tile of [208 | 112] and [208 | 208] (208 % 32 = 16: walk_tiles' `mixi` tile); d = 32 -> DP = 32 with S 16 wide;
+# d = 64 (trunc_eval), incl. the hop MLP's (DP, 0, DP) at d = 32 and 64; K1 = 16 < 32 (one partial k-tile).  Row counts around the 128 / 256-row tiles, one row, and one below the default.
+SMALL_M = [1, 60, 255, 256, 257, 2000, 8191]
+GOLDEN_TRIPLES = [(208, 112, 624), (208, 208, 208), (624, 0, 208), (208, 0, 208), (32, 16, 96), (32, 0, 32), (96, 0, 16), (16, 0, 16),
+                  (64, 32, 192), (64, 0, 64)]
+
+
+@pytest.fixture
+def everywhere():
+    hip()
+    with helpers.form_everywhere() as K:
+        assert K.PACK_MIN_M == 1 and K.gemm_split == 2
+        yield K
+
+
+def _h2_bound(A1, B1, A2, B2, ref, w1=None, w2=None):
+    """the three-MFMA form's bound (above H2_SHAPES), the absolute floor written in terms of the operand WORDS the kernel was handed
+    (w1 / w2: the maxima as floats; default the true ones)"""
+    K1, K2 = A1.size(1), (A2.size(1) if A2 is not None else 0)
+    amax = max(w1 if w1 is not None else A1.abs().max().item(), (w2 if w2 is not None else A2.abs().max().item()) if K2 else 0.0)
+    bcol = B1.abs().max(0).values.double() if not K2 else torch.maximum(B1.abs().max(0).values, B2.abs().max(0).values).double()
+    bound = 12 * EPS * (A1.abs().double() @ B1.abs().double()) + 2.0 ** -38 * (K1 + K2) * amax * bcol + 4 * EPS * ref.abs() + 1e-30
+    if K2:
+        bound = bound + 12 * EPS * (A2.abs().double() @ B2.abs().double())
+    return bound
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('K1,K2,No', GOLDEN_TRIPLES)
+@pytest.mark.parametrize('M', SMALL_M)
+@pytest.mark.parametrize('kind', ['plain', 'spread'])
+def test_gemm_nn_three_mfma_form_at_small_m(kind, M, K1, K2, No, everywhere):
+    K = everywhere
+    g = torch.Generator().manual_seed(M * 7 + K1 + K2 + No)
+    A1, B1 = _ranged(g, M, K1, kind), torch.randn(K1, No, generator=g) * torch.pow(10.0, -3 * torch.rand(1, No, generator=g))
+    A2, B2 = (_ranged(g, M, K2, 'plain'), torch.randn(K2, No, generator=g)) if K2 else (None, None)
+    bias = torch.randn(No, generator=g)
+    cu = lambda t: None if t is None else t.cuda()  # noqa: E731
+    nkw = dict(B1n=cu(B1.t().contiguous()), B2n=cu(B2.t().contiguous()) if K2 else None)
+    got = K.gemm_nn(cu(A1), cu(B1), cu(A2), cu(B2), bias=cu(bias), a_amax1=K.absmax(cu(A1)), a_amax2=K.absmax(cu(A2)) if K2 else None, **nkw).cpu()
+    ref = A1.double() @ B1.double() + (A2.double() @ B2.double() if K2 else 0.0) + bias.double()
+    bound = _h2_bound(A1, B1, A2, B2, ref)
+    err = (got.double() - ref).abs()
+    assert torch.isfinite(got).all()
+    assert bool((err <= bound).all()), f'max err {err.max().item():.3e}, worst bound ratio {(err / bound).max().item():.2f}'
+    # ... and it is not the six-MFMA kernel that answered (now on its packed-B route: the same bound holds for it)
+    six = K.gemm_nn(cu(A1), cu(B1), cu(A2), cu(B2), bias=cu(bias), **nkw).cpu()
+    assert ((six.double() - ref).abs() <= bound).all()
+    # (the dropped term, <= 2^-22 |a b|, lies below the rounding of the fp32 accumulation -- csrc/gemm_nn2.hip header -- so a few outputs can
+    # all round alike in both forms: measured, one row x 208 columns did for `spread` and did not for `plain`; from two rows on, no case did)
+    if M * No >= 200 and (M > 1 or kind == 'plain'):
+        assert not torch.equal(six, got), 'the three-MFMA form did not run'
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('M,K1,K2,No', [(60, 208, 112, 624), (257, 32, 16, 96), (2000, 624, 0, 208), (1, 16, 0, 16)])
+@pytest.mark.parametrize('zero', ['A', 'B_tile', 'A_row', 'big_word'])
+def test_three_mfma_form_at_zero_operands_and_an_over_large_word(zero, M, K1, K2, No, everywhere):
+    """A all zero (word 0: the scale field of an empty operand), one 16-column tile of B zero, a zero row of A: finite and within the bound.
+    big_word: A's word 2^8 above its true maximum (as the bound of relu(bn(h1)) may be): within the bound written in the word."""
+    K = everywhere
+    g = torch.Generator().manual_seed(M + K1 + No + len(zero))
+    A1, B1 = torch.randn(M, K1, generator=g), torch.randn(K1, No, generator=g)
+    A2, B2 = (torch.randn(M, K2, generator=g), torch.randn(K2, No, generator=g)) if K2 else (None, None)
+    if zero == 'A':
+        A1.zero_()
+        if K2:
+            A2.zero_()
+    elif zero == 'B_tile':
+        B1[:, 16:32] = 0
+        if K2:
+            B2[:, 16:32] = 0
+    elif zero == 'A_row':
+        A1[M // 2] = 0
+        if K2:
+            A2[M // 2] = 0
+    cu = lambda t: None if t is None else t.cuda()  # noqa: E731
+    w1, w2 = K.absmax(cu(A1)), (K.absmax(cu(A2)) if K2 else None)
+    f1 = f2 = None
+    if zero == 'big_word':
+        f1 = A1.abs().max().item() * 256
+        w1 = torch.tensor([f1, 0, 0, 0], dtype=torch.float32).view(torch.int32).cuda()
+        if K2:
+            f2 = A2.abs().max().item() * 256
+            w2 = torch.tensor([f2, 0, 0, 0], dtype=torch.float32).view(torch.int32).cuda()
+    got = K.gemm_nn(cu(A1), cu(B1), cu(A2), cu(B2), B1n=cu(B1.t().contiguous()), B2n=cu(B2.t().contiguous()) if K2 else None,
+                    a_amax1=w1, a_amax2=w2).cpu()
+    ref = A1.double() @ B1.double() + (A2.double() @ B2.double() if K2 else 0.0)
+    bound = _h2_bound(A1, B1, A2, B2, ref, f1, f2)
+    err = (got.double() - ref).abs()
+    assert torch.isfinite(got).all()
+    assert bool((err <= bound).all()), f'max err {err.max().item():.3e}, worst bound ratio {(err / bound).max().item():.2f}'
+    if zero == 'A':
+        assert (got == 0).all()
+    if zero == 'B_tile':
+        assert (got[:, 16:32] == 0).all()
+    if zero == 'A_row':
+        assert (got[M // 2] == 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('M,V,Kd,No', [(1, 500, 32, 208), (60, 300, 16, 32), (257, 500, 32, 208), (800, 3000, 768, 208), (2000, 2000, 1024, 208)])
+def test_gemm_with_fused_row_gather_in_the_three_mfma_form_at_small_m(M, V, Kd, No, everywhere):
+    """test_gemm_with_fused_row_gather's three-MFMA branch (a_rowidx, rows of -1, the frozen table's maximum as the word) at the row counts
+    and table widths of the golden cases' input stage."""
+    K = everywhere
+    g = torch.Generator().manual_seed(M + V + Kd)
+    table = torch.randn(V, Kd, generator=g)
+    idx = torch.randint(0, V, (M,), generator=g)
+    idx[1::17] = -1  # (not row 0: at M = 1 it is the only row)
+    B = torch.randn(Kd, No, generator=g)
+    bias = torch.randn(No, generator=g)
+    kw = dict(bias=bias.cuda(), a_rowidx=idx.cuda(), B1n=B.t().contiguous().cuda())
+    got3 = K.gemm_nn(table.cuda(), B.cuda(), a_amax1=K.absmax(table.cuda().view(-1)), **kw).cpu()
+    Ag = EMU._gather_rows(table.double(), idx)
+    ref = Ag @ B.double() + bias.double()
+    err3 = (got3.double() - ref).abs()
+    bound3 = 12 * EPS * (Ag.abs() @ B.abs().double()) + 2.0 ** -38 * Kd * table.abs().max().item() * B.abs().max(0).values.double() + 4 * EPS * ref.abs()
+    assert torch.isfinite(got3).all()
+    assert bool((err3 <= bound3).all()), (err3.max().item(), (err3 / bound3).max().item())
+    assert (got3[idx < 0] == bias).all()
+    six = K.gemm_nn(table.cuda(), B.cuda(), **kw).cpu()
+    if M * No >= 200:
+        assert not torch.equal(got3, six), 'the three-MFMA form did not run'
+
+
+AM_X, AM_S, AM_AGGR, AM_H1, AM_Y, AM_DOUT, AM_DH1, AM_DKMQ = range(8)  # word layout of a hop's amax block (csrc/hop.hip)
+
+
+def _bits(t):
+    return t.abs().max().cpu().view(torch.int32).item()
+
+
+def _word_f(w):
+    return torch.tensor([int(w)], dtype=torch.int32).view(torch.float32).item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['csqa_b10', 'small_train'])
+def test_native_stack_in_the_three_mfma_form(name, monkeypatch):
+    """qagnn_stack_{fwd,bwd}_f32 with k = 3 hops, gemm_split = 2 against gemm_split = 1, at a golden case's graph with the row threshold at
+    1 (helpers.form_everywhere).  The stack input is 2^-10 the size of what the hops
+    produce (BatchNorm renormalises): hop l > 0 must take hop l-1's y word as its X word -- the word of any other tensor is off by ~2^10, and
+    the products that use it leave the bound (too small: fp16 overflow; too large: 10 bits lost).  That is how this test sees WHICH word a
+    hop read (csrc/hop.hip, hop_amax_stack): the words in memory are right either way.  Every buffer and gradient within fp32 round-off of
+    the exact run (the one-hop bars of test_native_hop_in_the_three_mfma_form per hop), everything finite, and the words: X (hop 0), S, aggr,
+    y exact, h1 a bound within 2^8, the last hop's DOUT >= max |d out| rebuilt from its saved `out` and dy."""
+    HP = 8 if name == 'small_train' else 52
+    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5)
+    hip()
+    with helpers.form_everywhere():
+        from qagnn_amd import ops
+        K = ops.kernels()
+        g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
+        gen = torch.Generator().manual_seed(79)
+        N, DP, C, SP, k = nt.numel(), 4 * HP, R * T * T + T, 112 if HP == 52 else 16, 3
+        assert N >= K.PACK_MIN_M
+        rnd = lambda *shape, s=0.3: (torch.randn(*shape, generator=gen) * s).cuda()  # noqa: E731
+        prms = []
+        for _ in range(k):
+            Wx_t, Ws_t, W1t, W2t = rnd(DP, 3 * DP, s=0.1), rnd(SP, 3 * DP, s=0.1), rnd(DP, DP, s=0.1), rnd(DP, DP, s=0.1)
+            prms.append((Wx_t, Wx_t.t().contiguous(), Ws_t, Ws_t.t().contiguous(), rnd(T, 3 * DP), rnd(C, 2 * DP), W1t, W1t.t().contiguous(),
+                         rnd(DP), 1 + rnd(DP), 9 + rnd(DP), W2t, W2t.t().contiguous(), rnd(DP), rnd(DP), 0.5 + rnd(DP).abs()))
+        # (beta = 9 +- 1: the ReLU is the identity, the two runs differ by round-off only -- test_native_hop_in_the_three_mfma_form)
+        X, S, dy = rnd(N, DP, s=2.0 ** -10), rnd(N, SP, s=1.0), rnd(N, DP, s=1e-6)
+        args = (g, HP, qs, X, S, nt.cuda(), prms, True, 1e-5, 0.2, [4321 + l for l in range(k)])
+        res = {}
+        for mode in (2, 1):
+            monkeypatch.setattr(K, 'gemm_split', mode)
+            y, saved = K.stack_fwd(*args, [None] * k)
+            dX, dS, per = K.stack_bwd(*args, saved, dy, True, True)
+            torch.cuda.synchronize()
+            flat = [('y', y), ('KMQ', saved[0]), ('rows', saved[2]), ('stats', saved[3]), ('dX', dX), ('dS', dS)]
+            flat += [(f'hop{l}.d{i}', t) for l, gl in enumerate(per) for i, t in enumerate(gl) if t is not None]
+            res[mode] = (flat, saved)
+        differ = 0
+        for (nm, a), (_, b) in zip(res[2][0], res[1][0]):
+            assert torch.isfinite(a).all(), nm
+            scale = b.abs().max().item() + 1e-30
+            err = (a - b).abs().max().item()
+            tol = k * (2e-4 if nm.startswith(('d', 'hop')) else 2e-5)  # (the one-hop bars, per hop of the chain)
+            if nm.endswith('.d5'):  # db1: zero by construction under batch statistics (test_native_hop_in_the_three_mfma_form)
+                continue
+            assert err <= tol * scale, f'{nm}: {err:.3e} of scale {scale:.3e}'
+            differ += int(not torch.equal(a, b))
+        assert differ >= 10, differ
+        _, _, rows, stats, amax = res[2][1][:5]
+        w = amax.cpu()
+        assert w[0, AM_X].item() == _bits(X) and w[0, AM_S].item() == _bits(S)
+        dout = K.gelu_dropout_bwd(rows[k - 1, 2].contiguous(), dy, 0.2, 4321 + k - 1)
+        if w[k - 1, AM_DOUT].item() or DP == 208:  # (below 193 columns the product that reads it stays exact: no word)
+            assert _word_f(w[k - 1, AM_DOUT]) >= dout.abs().max().item() > 0
+        for l in range(k):
+            assert w[l, AM_AGGR].item() == _bits(rows[l, 0]) and w[l, AM_Y].item() == _bits(rows[l, 3]), l
+            st = stats[l].cpu()
+            h1n = torch.relu(rows[l, 1].cpu() * st[3] + st[4]).abs().max().item()
+            if DP == 208:
+                assert h1n <= _word_f(w[l, AM_H1]) <= 256 * h1n, (l, h1n, _word_f(w[l, AM_H1]))
+            else:  # (no fused statistics below 193 columns: no bound, the h1 product stays exact)
+                assert w[l, AM_H1].item() == 0
+            for j in (AM_DOUT, AM_DH1, AM_DKMQ):
+                assert np.isfinite(_word_f(w[l, j])) and (w[l, j].item() != 0 or DP != 208), (l, j)

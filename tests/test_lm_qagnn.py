@@ -93,10 +93,15 @@ def test_lm_qagnn_host_logic_matches_the_reference_lm_qagnn(case, graph_form):
         ops.set_kernels(old)
 
 
+@pytest.fixture
+def form(request):
+    """the GEMM arithmetic (tests/test_hip_parity.py::form): the library's default row threshold, or the three-MFMA form at every size"""
+    yield from helpers.apply_form(request.param)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('graph_form', ['lists', 'blobs'])
-@pytest.mark.parametrize('case', list(helpers.LM_CASES))
-def test_lm_qagnn_on_hip_matches_the_reference_lm_qagnn(case, graph_form):
+@pytest.mark.parametrize('case,graph_form,form', helpers.with_forms([(c, g) for c in helpers.LM_CASES for g in ('lists', 'blobs')]), indirect=['form'])
+def test_lm_qagnn_on_hip_matches_the_reference_lm_qagnn(case, graph_form, form):
     ops.set_kernels(None)
     run_lm_case(case, 'cuda', graph_form)
     assert ops.kernels().name == 'hip'

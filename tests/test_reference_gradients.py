@@ -98,10 +98,15 @@ def run_section(case, section, device, fixed_bar=FIXED_GRAD_BAR):
 MIN_TENSORS = {'grad': 40, 'mpgrad': 30, 'layergrad': 8}
 
 
+@pytest.fixture
+def form(request):
+    """the GEMM arithmetic (tests/test_hip_parity.py::form): the library's default row threshold, or the three-MFMA form at every size"""
+    yield from helpers.apply_form(request.param)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('section', ['grad', 'mpgrad', 'layergrad'])
-@pytest.mark.parametrize('case', CASES)
-def test_hip_gradients_equal_the_reference_gradients(case, section):
+@pytest.mark.parametrize('case,section,form', helpers.with_forms([(c, s) for c in CASES for s in ('grad', 'mpgrad', 'layergrad')]), indirect=['form'])
+def test_hip_gradients_equal_the_reference_gradients(case, section, form):
     ops.set_kernels(None)
     k = helpers.GOLDEN_CASES[case]['cfg']['k']
     n = run_section(case, section, 'cuda', fixed_bar=FIXED_GRAD_BAR_HIP)
