@@ -5,6 +5,7 @@ raw data pointers.  All compute goes through the C ABI.  There is no fallback: i
 or no MI355X is visible, `HipKernels()` raises.
 """
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -162,6 +163,16 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _running_fields(running):
+    """running = (run_mean [d], run_var [d], num_batches_tracked or None, dense_pos [d], momentum, unbias) or None -> the same as the C
+    ABI takes it: four addresses, d, momentum, unbias (None: no running-statistics update)."""
+    if running is None:
+        return None, None, None, None, 0, 0.0, 1.0
+    rm, rv, nbt, pos, mom, unb = running
+    assert rm.is_contiguous() and rv.is_contiguous() and pos.dtype == torch.long and (nbt is None or nbt.dtype == torch.long)
+    return rm.data_ptr(), rv.data_ptr(), _ptr(nbt), pos.data_ptr(), rm.numel(), float(mom), float(unb)
+
+
 def _chk2d(t, name, dtype=torch.float32):
     assert t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.is_contiguous(), \
         f'{name}: need a contiguous 2-D {dtype} device tensor, got {tuple(t.shape)} {t.dtype} {t.device}'
@@ -192,16 +203,11 @@ class _ErrWatch:
             if self.sink is not None:
                 self.sink.append((flags, what, reset))
             return
-        host = torch.empty(4, dtype=torch.int32, pin_memory=True)
-        host.copy_(flags, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.pending.append((ev, host, what, reset))
-        if VALIDATE:
-            self.poll(block=True)
+        self.after_replay([(flags, what, reset)])
 
     def after_replay(self, watched):
-        """Behind graph.replay(): the flag words the replayed launches wrote -> pinned host memory (async) + an event, as watch()."""
+        """The flag words of (flags, what, reset) entries -> pinned host memory (async) + an event each: what watch() does for one eager
+        call, and what a capturing step does behind graph.replay() for the flag words the replayed launches wrote."""
         for flags, what, reset in watched:
             host = torch.empty(4, dtype=torch.int32, pin_memory=True)
             host.copy_(flags, non_blocking=True)
@@ -282,8 +288,6 @@ def _on_operand_device(fn):
     decoder's tensors.  A kernel launched on device 0's stream with device-1 pointers would fault or race with the torch ops
     queued on cuda:1's stream; every entry point of the provider therefore switches to the operands' device first (a no-op
     costing one integer compare when it already is the current one)."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(self, *args, **kwargs):
         dev = _device_of(args, kwargs)
@@ -532,6 +536,15 @@ class HipKernels(metaclass=_GuardedMeta):
         self._check(self.lib.qagnn_gemm_nn_f32(C.byref(a), self._stream()), 'qagnn_gemm_nn_f32')
         return out
 
+    def _tn_out_ws(self, R, Ka, No, out, dev):
+        """the [Ka, No] output of a weight-gradient product over R rows (the caller's `out`, or a fresh one) and its split-K workspace"""
+        if out is None:
+            out = torch.empty((Ka, No), dtype=torch.float32, device=dev)
+        else:
+            _chk2d(out, 'out')
+            assert out.shape == (Ka, No)
+        return out, torch.empty(self.lib.qagnn_gemm_tn_workspace_elems(R, Ka, No), dtype=torch.float32, device=dev)
+
     def gemm_tn(self, A, B, a_scale=None, a_shift=None, out=None, accumulate=False, a_rowidx=None, colsum_groups=0,
                 b_rowidx=None):
         """C = A^T B.  colsum_groups = G > 0 additionally returns bsum [G, No] = per-group column sums of B."""
@@ -539,10 +552,8 @@ class HipKernels(metaclass=_GuardedMeta):
         Ka = A.size(1)
         R, No = B.shape
         assert (A.size(0) == R) if a_rowidx is None else (a_rowidx.numel() == R and a_rowidx.dtype == torch.long)
-        if out is None:
-            assert not accumulate
-            out = torch.empty((Ka, No), dtype=torch.float32, device=A.device)
-        ws = torch.empty(self.lib.qagnn_gemm_tn_workspace_elems(R, Ka, No), dtype=torch.float32, device=A.device)
+        assert out is not None or not accumulate
+        out, ws = self._tn_out_ws(R, Ka, No, out, A.device)
         bsum = None
         if colsum_groups:
             assert b_rowidx is None or (b_rowidx.dtype == torch.long and b_rowidx.numel() == R and b_rowidx.is_contiguous())
@@ -567,9 +578,7 @@ class HipKernels(metaclass=_GuardedMeta):
         _chk2d(A1, 'A1'), _chk2d(B, 'B')
         Ka1, Ka2 = A1.size(1), (A2.size(1) if A2 is not None else 0)
         R, No = B.shape
-        if out is None:
-            out = torch.empty((Ka1 + Ka2, No), dtype=torch.float32, device=B.device)
-        ws = torch.empty(self.lib.qagnn_gemm_tn_workspace_elems(R, Ka1 + Ka2, No), dtype=torch.float32, device=B.device)
+        out, ws = self._tn_out_ws(R, Ka1 + Ka2, No, out, B.device)
         fn = self.lib.qagnn_gemm_tn_h1_f32 if self.gemm_split == 3 else self.lib.qagnn_gemm_tn_h2_f32
         rc = fn(A1.data_ptr(), Ka1, Ka1, _ptr(A2), Ka2, Ka2, B.data_ptr(), No, out.data_ptr(), No, R, No, _ptr(a_scale),
                                            _ptr(a_shift), amax_a1.data_ptr(), _ptr(amax_a2), amax_b.data_ptr(), ws.data_ptr(), self._stream())
@@ -582,12 +591,7 @@ class HipKernels(metaclass=_GuardedMeta):
         Ka1, Ka2 = A1.size(1), A2.size(1)
         R, No = B.shape
         assert A1.size(0) == R and A2.size(0) == R
-        if out is None:
-            out = torch.empty((Ka1 + Ka2, No), dtype=torch.float32, device=B.device)
-        else:
-            _chk2d(out, 'out')
-            assert out.shape == (Ka1 + Ka2, No)
-        ws = torch.empty(self.lib.qagnn_gemm_tn_workspace_elems(R, Ka1 + Ka2, No), dtype=torch.float32, device=B.device)
+        out, ws = self._tn_out_ws(R, Ka1 + Ka2, No, out, B.device)
         rc = self.lib.qagnn_gemm_tn2_f32(A1.data_ptr(), Ka1, Ka1, A2.data_ptr(), Ka2, Ka2, B.data_ptr(), No, out.data_ptr(), No, R, No,
                                          ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_gemm_tn2_f32')
@@ -619,15 +623,9 @@ class HipKernels(metaclass=_GuardedMeta):
         scale 0 / shift 1, i.e. relu(bn(h)) carries a column of ones there (see qagnn_bn_finalize_f32)."""
         Cc = mean.numel()
         out = torch.empty((3, Cc), dtype=torch.float32, device=mean.device)
-        rm = rv = nbt = pos = None
-        d, mom, unb = 0, 0.0, 1.0
-        if running is not None:
-            rm, rv, nbt, pos, mom, unb = running
-            d = rm.numel()
-            assert rm.is_contiguous() and rv.is_contiguous() and pos.dtype == torch.long and (nbt is None or nbt.dtype == torch.long)
         rc = self.lib.qagnn_bn_finalize_f32(mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), Cc, _ptr(rm), _ptr(rv), _ptr(nbt),
-                                            _ptr(pos), d, float(mom), float(unb), int(ones_col), self._stream())
+                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), Cc, *_running_fields(running),
+                                            int(ones_col), self._stream())
         self._check(rc, 'qagnn_bn_finalize_f32')
         return out[0], out[1], out[2]
 
@@ -637,14 +635,8 @@ class HipKernels(metaclass=_GuardedMeta):
         nt, _, Cc = part.shape
         assert part.is_contiguous() and nt == -(-rows // self.STAT_TILE)
         stats = torch.empty((5, Cc), dtype=torch.float32, device=part.device)
-        rm = rv = nbt = pos = None
-        d, mom, unb = 0, 0.0, 1.0
-        if running is not None:
-            rm, rv, nbt, pos, mom, unb = running
-            d = rm.numel()
-            assert rm.is_contiguous() and rv.is_contiguous() and (nbt is None or nbt.dtype == torch.long)
         rc = self.lib.qagnn_bn_stats_finalize_f32(part.data_ptr(), nt, int(rows), Cc, gamma.data_ptr(), beta.data_ptr(), float(eps), stats.data_ptr(),
-                                                  _ptr(rm), _ptr(rv), _ptr(nbt), _ptr(pos), d, float(mom), float(unb), int(ones_col), self._stream())
+                                                  *_running_fields(running), int(ones_col), self._stream())
         self._check(rc, 'qagnn_bn_stats_finalize_f32')
         return stats
 
@@ -786,14 +778,18 @@ class HipKernels(metaclass=_GuardedMeta):
         self._check(self.lib.qagnn_timing_read(ms, calls), 'qagnn_timing_read')
         return {k: (ms[i], calls[i]) for i, k in enumerate(('gemm_nn', 'gemm_tn', 'edge_attn_fwd', 'edge_attn_bwd'))}
 
+    def _amax_word_scratch(self, numel, dev):
+        """a zeroed int32 [4] maximum word and the scratch of the GELU / dropout passes that leave max |.| of their output in it"""
+        word = torch.empty(4, dtype=torch.int32, device=dev)
+        self._check(self.lib.qagnn_zero_words(word.data_ptr(), 4, self._stream()), 'qagnn_zero_words')
+        return word, torch.empty(self.lib.qagnn_gelu_dropout_amax_scratch_elems(numel), dtype=torch.float32, device=dev)
+
     def gelu_dropout_fwd(self, X, p, seed, amax=False):
         """amax=True: -> (Y, word) with word = int32 [4], [0] = the bit pattern of max |Y| (qagnn_gelu_dropout_fwd_amax_f32)"""
         assert X.is_contiguous() and X.dtype == torch.float32
         Y = torch.empty_like(X)
         if amax:
-            word = torch.empty(4, dtype=torch.int32, device=X.device)
-            self._check(self.lib.qagnn_zero_words(word.data_ptr(), 4, self._stream()), 'qagnn_zero_words')
-            scratch = torch.empty(self.lib.qagnn_gelu_dropout_amax_scratch_elems(X.numel()), dtype=torch.float32, device=X.device)
+            word, scratch = self._amax_word_scratch(X.numel(), X.device)
             self._check(self.lib.qagnn_gelu_dropout_fwd_amax_f32(X.data_ptr(), Y.data_ptr(), X.numel(), float(p), int(seed), word.data_ptr(),
                                                                  scratch.data_ptr(), self._stream()), 'qagnn_gelu_dropout_fwd_amax_f32')
             return Y, word
@@ -806,9 +802,7 @@ class HipKernels(metaclass=_GuardedMeta):
         assert X.is_contiguous() and dY.is_contiguous()
         dX = torch.empty_like(X)
         if amax:
-            word = torch.empty(4, dtype=torch.int32, device=X.device)
-            self._check(self.lib.qagnn_zero_words(word.data_ptr(), 4, self._stream()), 'qagnn_zero_words')
-            scratch = torch.empty(self.lib.qagnn_gelu_dropout_amax_scratch_elems(X.numel()), dtype=torch.float32, device=X.device)
+            word, scratch = self._amax_word_scratch(X.numel(), X.device)
             self._check(self.lib.qagnn_gelu_dropout_bwd_amax_f32(X.data_ptr(), dY.data_ptr(), dX.data_ptr(), X.numel(), float(p), int(seed),
                                                                  word.data_ptr(), scratch.data_ptr(), self._stream()), 'qagnn_gelu_dropout_bwd_amax_f32')
             return dX, word
@@ -870,7 +864,7 @@ class HipKernels(metaclass=_GuardedMeta):
         return dKMQ, dEkEm
 
     # -- one GATConvE hop per call (csrc/hop.hip) ---------------------------------------------------------------------------
-    def _hop_struct(self, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, tab_col=-1, side=False):
+    def _hop_struct(self, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, tab_col=-1, side=False, running=None):
         Wx_t, Wx, Ws_t, Ws, TT, EkEm, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean_p, run_var_p = prm
         DP = 4 * HP
         _chk2d(X, 'X'), _chk2d(Wx_t, 'Wx_t'), _chk2d(Wx, 'Wx'), _chk2d(TT, 'TT'), _chk2d(EkEm, 'EkEm')
@@ -894,6 +888,8 @@ class HipKernels(metaclass=_GuardedMeta):
         h.W2t, h.W2, h.b2 = W2t.data_ptr(), W2.data_ptr(), b2.data_ptr()
         h.batch_stats, h.eps = (1 if batch_stats else 0), float(eps)
         h.run_mean_p, h.run_var_p = run_mean_p.data_ptr(), run_var_p.data_ptr()
+        # (forward only: the train-mode update of the module's running statistics; the hop derives the unbiased-variance factor from N)
+        h.run_mean, h.run_var, h.num_batches_tracked, h.dense_pos, h.d, h.momentum, _unb = _running_fields(running)
         h.apply_act, h.p_drop, h.seed = (1 if apply_act else 0), float(p), int(seed)
         h.gemm_split = int(self.gemm_split)
         tc, oc = tab_col if isinstance(tab_col, tuple) else (tab_col, -1)  # (type-indicator column of S, ones column of relu(bn(h1)))
@@ -902,26 +898,56 @@ class HipKernels(metaclass=_GuardedMeta):
         h.side_stream = self._side_stream() if side else None  # backward only (qagnn_hop_args.side_stream)
         return h
 
+    @staticmethod
+    def _set_saved(h, p_kmq, p_aa, p_rows, p_stats, p_amax, Ep, row_b):
+        """One hop's saved arrays from the ADDRESSES of its KMQ [N, 3DP], aa [2, Ep, 4] = a | alpha, rows [4, N, DP] = aggr | h1 | out | y,
+        stats [5, DP] and maximum words; row_b = the bytes of one [N, DP] matrix.  Addresses by arithmetic: a view tensor per pointer
+        costs the host-bound batches ~0.3 ms per step in the stack."""
+        h.KMQ, h.stats, h.amax = p_kmq, p_stats, p_amax
+        h.a, h.alpha = p_aa, p_aa + Ep * 16
+        h.aggr, h.h1, h.out, h.y = (p_rows + i * row_b for i in range(4))
+
+    @staticmethod
+    def _grad_sizes(DP, SP, T, n_cls):
+        """element counts of dWx_t | dWs_t | dTT | dEkEm | dW1t | db1 | dbn | dW2t | db2 in a hop's flat gradient buffer (each a multiple
+        of 4: 16-byte aligned views), and their running offsets"""
+        sizes = [DP * 3 * DP, SP * 3 * DP, T * 3 * DP, n_cls * 2 * DP, DP * DP, DP, 2 * DP, DP * DP, DP]
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        return sizes, offs
+
+    @staticmethod
+    def _carve_grads(h, fl, sizes, offs, n_cls):
+        """fl: one hop's flat gradient buffer -> the hop's output pointers, and the ten gradients handed to autograd:
+        (dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dgamma, dbeta, dW2t, db2)."""
+        DP, SP, T, base = h.DP, h.SP, h.T, fl.data_ptr()
+        h.dWx_t, pdWs_t, h.dTT, h.dEkEm, h.dW1t, h.db1, h.dbn, h.dW2t, h.db2 = (base + o * 4 for o in offs[:9])
+        dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dbn, dW2t, db2 = fl.split(sizes)
+        if h.ones_col >= 0:  # the bias gradient IS that row of dW2t, the type-table gradient those rows of dWs_t: views, no copies
+            db2 = dW2t.view(DP, DP)[h.ones_col]
+            h.db2 = h.dW2t + h.ones_col * DP * 4
+        if SP:
+            h.dWs_t = pdWs_t
+            if h.tab_col >= 0:
+                dTT = dWs_t.view(SP, 3 * DP)[h.tab_col:h.tab_col + T]
+                h.dTT = pdWs_t + h.tab_col * 3 * DP * 4
+        return (dWx_t.view(DP, 3 * DP), dWs_t.view(SP, 3 * DP) if SP else None, dTT.view(T, 3 * DP), dEkEm.view(n_cls, 2 * DP),
+                dW1t.view(DP, DP), db1, dbn[DP:], dbn[:DP], dW2t.view(DP, DP), db2)
+
     def hop_fwd(self, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, running, cols=-1):
         """-> (y, saved) with saved = (KMQ, aa [2, Ep, 4] = a | alpha, aggr, h1, out, stats [5, DP]); y is `out` when not apply_act."""
-        h = self._hop_struct(graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, cols)
+        h = self._hop_struct(graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, cols, running=running)
         N, DP, dev = graph.N, 4 * HP, X.device
         KMQ = torch.empty((N, 3 * DP), dtype=torch.float32, device=dev)
         aa = torch.empty((2, graph.Ep, 4), dtype=torch.float32, device=dev)
         rows = torch.empty((4 if apply_act else 3, N, DP), dtype=torch.float32, device=dev)  # aggr, h1, out (, y)
         stats = torch.empty((5, DP), dtype=torch.float32, device=dev)
         amax = torch.empty(HOP_AMAX_WORDS, dtype=torch.int32, device=dev)  # operand maxima of the three-MFMA form (zeroed by the library)
-        h.amax = amax.data_ptr()
         ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, graph.Ep, DP), dtype=torch.float32, device=dev)
-        h.KMQ, h.a, h.alpha, h.stats = KMQ.data_ptr(), aa[0].data_ptr(), aa[1].data_ptr(), stats.data_ptr()
-        h.aggr, h.h1, h.out = rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr()
-        if apply_act:
-            h.y = rows[3].data_ptr()
-        if running is not None:
-            rm, rv, nbt, pos, mom, _unb = running
-            assert rm.is_contiguous() and rv.is_contiguous() and pos.dtype == torch.long and (nbt is None or nbt.dtype == torch.long)
-            h.run_mean, h.run_var, h.num_batches_tracked, h.dense_pos = rm.data_ptr(), rv.data_ptr(), _ptr(nbt), pos.data_ptr()
-            h.d, h.momentum = rm.numel(), float(mom)
+        self._set_saved(h, KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), graph.Ep, N * DP * 4)
+        if not apply_act:
+            h.y = None  # (rows has no fourth matrix)
         h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
         self._check(self.lib.qagnn_hop_fwd_f32(C.byref(h), self._stream()), 'qagnn_hop_fwd_f32')
         return rows[3 if apply_act else 2], (KMQ, aa, rows[0], rows[1], rows[2], stats, amax)
@@ -930,76 +956,51 @@ class HipKernels(metaclass=_GuardedMeta):
                 dX_acc=None, dS_acc=None, tab_col=-1, overlap=True):
         """-> (dX, dS, dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dgamma, dbeta, dW2t, db2); overlap: the weight-gradient products on a side stream"""
         h = self._hop_struct(graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, tab_col, side=overlap)
-        KMQ, aa, aggr, h1, out, stats = saved[:6]
+        KMQ, aa, aggr, h1, out, stats = saved[:6]  # (tensors of their own, e.g. hop_fwd_composed's: no common base to do arithmetic on)
         h.amax = saved[6].data_ptr() if len(saved) > 6 else None
-        N, DP, dev, SP, T = graph.N, 4 * HP, X.device, h.SP, h.T
+        N, DP, dev, SP = graph.N, 4 * HP, X.device, h.SP
         _chk2d(dy, 'dy')
         h.KMQ, h.a, h.alpha, h.stats = KMQ.data_ptr(), aa[0].data_ptr(), aa[1].data_ptr(), stats.data_ptr()
         h.aggr, h.h1, h.out, h.y = aggr.data_ptr(), h1.data_ptr(), out.data_ptr(), out.data_ptr()
         h.dy = dy.data_ptr()
-        sizes = [DP * 3 * DP, SP * 3 * DP, T * 3 * DP, graph.C * 2 * DP, DP * DP, DP, 2 * DP, DP * DP, DP]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)  # every size is a multiple of 4: 16-byte aligned views
-        parts, off = [], 0
-        for n in sizes:
-            parts.append(flat[off:off + n])
-            off += n
-        dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dbn, dW2t, db2 = parts
-        h.dWx_t, h.dTT, h.dEkEm, h.dW1t, h.db1 = dWx_t.data_ptr(), dTT.data_ptr(), dEkEm.data_ptr(), dW1t.data_ptr(), db1.data_ptr()
-        h.dbn, h.dW2t, h.db2 = dbn.data_ptr(), dW2t.data_ptr(), db2.data_ptr()
-        if h.ones_col >= 0:  # the bias gradient IS that row of dW2t: hand out the view, no copy
-            db2 = dW2t.view(DP, DP)[h.ones_col]
-            h.db2 = db2.data_ptr()
-        if SP and h.tab_col >= 0:  # likewise the type-table gradient: rows of dWs_t
-            dTT = dWs_t.view(SP, 3 * DP)[h.tab_col:h.tab_col + T]
-            h.dTT = dTT.data_ptr()
+        sizes, offs = self._grad_sizes(DP, SP, h.T, graph.C)
+        grads = self._carve_grads(h, torch.empty(offs[-1], dtype=torch.float32, device=dev), sizes, offs, graph.C)
         dX = dS = None
         if need_dX:  # *_acc: an existing running total of this gradient, added to in place (GEMM epilogue accumulate)
             dX = dX_acc if dX_acc is not None else torch.empty((N, DP), dtype=torch.float32, device=dev)
             assert dX.shape == (N, DP) and dX.is_contiguous()
             h.dX, h.accumulate_dX = dX.data_ptr(), (1 if dX_acc is not None else 0)
-        if SP:
-            h.dWs_t = dWs_t.data_ptr()
-            if need_dS:
-                dS = dS_acc if dS_acc is not None else torch.empty((N, SP), dtype=torch.float32, device=dev)
-                assert dS.shape == (N, SP) and dS.is_contiguous()
-                h.dS, h.accumulate_dS = dS.data_ptr(), (1 if dS_acc is not None else 0)
+        if SP and need_dS:
+            dS = dS_acc if dS_acc is not None else torch.empty((N, SP), dtype=torch.float32, device=dev)
+            assert dS.shape == (N, SP) and dS.is_contiguous()
+            h.dS, h.accumulate_dS = dS.data_ptr(), (1 if dS_acc is not None else 0)
         ws = torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(N, graph.Ep, DP, SP, graph.max_chunks + CLS_SLICES * graph.C), dtype=torch.float32, device=dev)
         h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
         self._check(self.lib.qagnn_hop_bwd_f32(C.byref(h), self._stream()), 'qagnn_hop_bwd_f32')
-        return (dX, dS, dWx_t.view(DP, 3 * DP), dWs_t.view(SP, 3 * DP) if SP else None, dTT.view(T, 3 * DP), dEkEm.view(graph.C, 2 * DP),
-                dW1t.view(DP, DP), db1, dbn[DP:], dbn[:DP], dW2t.view(DP, DP), db2)
+        return (dX, dS, *grads)
 
     # -- the whole k-hop stack per call (csrc/hop.hip: qagnn_stack_{fwd,bwd}_f32) -------------------------------------------------------
     def stack_fwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, cols=-1, x_amax=None, s_amax=None):
         """k hops with GELU + dropout after each; prms / seeds / runnings: per-layer lists.  -> (y [N, DP], saved)."""
         k = len(prms)
-        N, DP, dev = graph.N, 4 * HP, X.device
+        N, DP, Ep, dev = graph.N, 4 * HP, graph.Ep, X.device
         KMQ = torch.empty((k, N, 3 * DP), dtype=torch.float32, device=dev)
-        aa = torch.empty((k, 2, graph.Ep, 4), dtype=torch.float32, device=dev)
+        aa = torch.empty((k, 2, Ep, 4), dtype=torch.float32, device=dev)
         rows = torch.empty((k, 4, N, DP), dtype=torch.float32, device=dev)  # per hop: aggr, h1, out, y
         stats = torch.empty((k, 5, DP), dtype=torch.float32, device=dev)
         amax = torch.empty((k, HOP_AMAX_WORDS), dtype=torch.int32, device=dev)  # one array: the library zeroes it with one launch
-        p_amax = amax.data_ptr()
-        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, graph.Ep, DP), dtype=torch.float32, device=dev)
+        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP), dtype=torch.float32, device=dev)
         hops = (qagnn_hop_args * k)()
         x = X
-        # addresses by arithmetic: a view tensor per pointer costs the host-bound batches ~0.3 ms per step
-        p_kmq, p_aa, p_rows, p_stats, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), N * DP * 4
+        p_kmq, p_aa, p_rows, p_stats, p_amax, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), N * DP * 4
         for l in range(k):
-            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], batch_stats, eps, p, seeds[l], True, cols)
-            h.KMQ, h.stats = p_kmq + l * 3 * row_b, p_stats + l * 5 * DP * 4
-            h.a, h.alpha = p_aa + (2 * l) * graph.Ep * 16, p_aa + (2 * l + 1) * graph.Ep * 16
-            h.aggr, h.h1, h.out, h.y = (p_rows + (4 * l + i) * row_b for i in range(4))
-            h.amax = p_amax + l * HOP_AMAX_WORDS * 4
+            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], batch_stats, eps, p, seeds[l], True, cols, running=runnings[l])
+            self._set_saved(h, p_kmq + l * 3 * row_b, p_aa + 2 * l * Ep * 16, p_rows + 4 * l * row_b, p_stats + l * 5 * DP * 4,
+                            p_amax + l * HOP_AMAX_WORDS * 4, Ep, row_b)
             if l == 0 and x_amax is not None:  # max |X| from X's producer (ops.amax_lookup): no reduction pass over the stack input
                 h.x_amax = x_amax.data_ptr()
             if s_amax is not None:
                 h.s_amax = s_amax.data_ptr()
-            if runnings[l] is not None:
-                rm, rv, nbt, pos, mom, _unb = runnings[l]
-                assert rm.is_contiguous() and rv.is_contiguous() and pos.dtype == torch.long and (nbt is None or nbt.dtype == torch.long)
-                h.run_mean, h.run_var, h.num_batches_tracked, h.dense_pos = rm.data_ptr(), rv.data_ptr(), _ptr(nbt), pos.data_ptr()
-                h.d, h.momentum = rm.numel(), float(mom)
             h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
             hops[l] = h
             x = rows[l, 3]
@@ -1015,61 +1016,42 @@ class HipKernels(metaclass=_GuardedMeta):
         KMQ, aa, rows, stats = saved[:4]
         p_amax = saved[4].data_ptr() if len(saved) > 4 else None
         x_amax, s_amax = (saved[5], saved[6]) if len(saved) > 6 else (None, None)
-        N, DP, dev = graph.N, 4 * HP, X.device
+        N, DP, Ep, dev = graph.N, 4 * HP, graph.Ep, X.device
         SP = S.size(1) if S is not None else 0
-        T = prms[0][4].size(0)
         _chk2d(dy, 'dy')
-        sizes = [DP * 3 * DP, SP * 3 * DP, T * 3 * DP, graph.C * 2 * DP, DP * DP, DP, 2 * DP, DP * DP, DP]
-        per = sum(sizes)
-        flat = torch.empty(k * per, dtype=torch.float32, device=dev)  # every size is a multiple of 4: 16-byte aligned views
+        sizes, offs = self._grad_sizes(DP, SP, prms[0][4].size(0), graph.C)
+        per = offs[-1]
+        flat = torch.empty(k * per, dtype=torch.float32, device=dev)
         dxs = torch.empty((max(k - 1, 1), N, DP), dtype=torch.float32, device=dev)  # gradient handed from hop l to hop l-1
         dS = torch.empty((N, SP), dtype=torch.float32, device=dev) if (SP and need_dS) else None
         dX = None
         if need_dX:
             dX = dX_acc if dX_acc is not None else torch.empty((N, DP), dtype=torch.float32, device=dev)
             assert dX.shape == (N, DP) and dX.is_contiguous()
-        ws = torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(N, graph.Ep, DP, SP, graph.max_chunks + CLS_SLICES * graph.C), dtype=torch.float32, device=dev)
+        ws = torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(N, Ep, DP, SP, graph.max_chunks + CLS_SLICES * graph.C), dtype=torch.float32, device=dev)
         hops = (qagnn_hop_args * k)()
         grads = []
         p_kmq, p_aa, p_rows, p_stats, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), N * DP * 4
-        p_flat, p_dxs = flat.data_ptr(), dxs.data_ptr()
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + n)
+        p_dxs = dxs.data_ptr()
         for l in range(k):
             x = X if l == 0 else rows[l - 1, 3]
             h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], batch_stats, eps, p, seeds[l], True, tab_col, side=overlap)
-            h.KMQ, h.stats = p_kmq + l * 3 * row_b, p_stats + l * 5 * DP * 4
-            h.a, h.alpha = p_aa + (2 * l) * graph.Ep * 16, p_aa + (2 * l + 1) * graph.Ep * 16
-            h.aggr, h.h1, h.out = (p_rows + (4 * l + i) * row_b for i in range(3))
-            h.y = p_rows + (4 * l + 3) * row_b  # (what the forward wrote: the chain hops[l + 1].X == hops[l].y is what shares the amax words)
-            h.amax = p_amax + l * HOP_AMAX_WORDS * 4 if p_amax else None
+            # (h.y = what the forward wrote: the chain hops[l + 1].X == hops[l].y is what shares the amax words)
+            self._set_saved(h, p_kmq + l * 3 * row_b, p_aa + 2 * l * Ep * 16, p_rows + 4 * l * row_b, p_stats + l * 5 * DP * 4,
+                            p_amax + l * HOP_AMAX_WORDS * 4 if p_amax else None, Ep, row_b)
             if l == 0 and x_amax is not None and x_amax.numel():
                 h.x_amax = x_amax.data_ptr()
             if s_amax is not None and s_amax.numel():
                 h.s_amax = s_amax.data_ptr()
             h.dy = dy.data_ptr() if l == k - 1 else p_dxs + l * row_b
-            base = p_flat + l * per * 4
-            h.dWx_t, pdWs_t, h.dTT, h.dEkEm, h.dW1t, h.db1, h.dbn, h.dW2t, h.db2 = (base + o * 4 for o in offs[:9])
-            fl = flat[l * per:(l + 1) * per]
-            dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dbn, dW2t, db2 = fl.split(sizes)
-            if h.ones_col >= 0:  # the bias gradient IS that row of dW2t, the type-table gradient those rows of dWs_t: views, no copies
-                db2 = dW2t.view(DP, DP)[h.ones_col]
-                h.db2 = h.dW2t + h.ones_col * DP * 4
-            if SP and h.tab_col >= 0:
-                dTT = dWs_t.view(SP, 3 * DP)[h.tab_col:h.tab_col + T]
-                h.dTT = pdWs_t + h.tab_col * 3 * DP * 4
+            grads.append(self._carve_grads(h, flat[l * per:(l + 1) * per], sizes, offs, graph.C))
             if l > 0:
                 h.dX, h.accumulate_dX = p_dxs + (l - 1) * row_b, 0
             elif dX is not None:
                 h.dX, h.accumulate_dX = dX.data_ptr(), (1 if dX_acc is not None else 0)
-            if SP:
-                h.dWs_t = pdWs_t
-                if dS is not None:
-                    h.dS, h.accumulate_dS = dS.data_ptr(), (0 if l == k - 1 else 1)  # hop k-1's backward runs first
+            if dS is not None:
+                h.dS, h.accumulate_dS = dS.data_ptr(), (0 if l == k - 1 else 1)  # hop k-1's backward runs first
             h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
             hops[l] = h
-            grads.append((dWx_t.view(DP, 3 * DP), dWs_t.view(SP, 3 * DP) if SP else None, dTT.view(T, 3 * DP), dEkEm.view(graph.C, 2 * DP),
-                          dW1t.view(DP, DP), db1, dbn[DP:], dbn[:DP], dW2t.view(DP, DP), db2))
         self._check(self.lib.qagnn_stack_bwd_f32(hops, k, self._stream()), 'qagnn_stack_bwd_f32')
         return dX, dS, grads

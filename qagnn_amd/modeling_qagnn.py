@@ -71,6 +71,15 @@ def bn_momentum(bn):
     return bn.momentum
 
 
+def bn_running(bn, L, rows, training):
+    """The `running` operand of the BatchNorm bookkeeping kernels for a hop's mlp over `rows` node rows: (running_mean, running_var,
+    num_batches_tracked, dense_pos, momentum, unbiased-variance factor), or None where no buffer is updated."""
+    if not (training and bn.track_running_stats):
+        return None
+    R = float(rows)
+    return (bn.running_mean, bn.running_var, bn.num_batches_tracked, L.dense_pos, bn_momentum(bn), R / max(R - 1.0, 1.0))
+
+
 def edge_class_features(n_etype, n_ntype, device, dtype=torch.float32):
     key = (n_etype, n_ntype, str(device), dtype)
     if key not in _CLASS_FEATS:
@@ -295,28 +304,19 @@ class GATConvE(nn.Module):
             if ops.use_fused_hop(Xp.size(0)):
                 # the whole hop (projection, attention, mlp, GELU + dropout, and its backward) as one native call each way
                 bn = self.mlp[1]
-                running = None
-                if self.training and bn.track_running_stats:
-                    R = float(Xp.size(0))
-                    running = (bn.running_mean, bn.running_var, bn.num_batches_tracked, L.dense_pos,
-                               bn_momentum(bn), R / max(R - 1.0, 1.0))
                 W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p = packed[8:]
                 return ops.gat_hop(Xp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.dim_per_head),
                                    (Wx_t, Wx, Ws_t, Ws, TT, ekem, W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p),
                                    self.training or not bn.track_running_stats, bn.eps, p_drop if self.training else 0.0, apply_act,
-                                   running, acc=acc, tab_col=cols)
+                                   bn_running(bn, L, Xp.size(0), self.training), acc=acc, tab_col=cols)
             KMQ = ops.linear_nn(Xp, Wx_t, Wx, S, Ws_t, Ws, rowtab=TT, rowidx=ntype, acc=acc, tabcol=tab_col)
             mlp_ops = packed[8:]
         aggr, a = ops.edge_attention(KMQ, ekem, graph, L.HP, 1.0 / math.sqrt(self.dim_per_head))
         bn = self.mlp[1]
         use_batch_stats = self.training or not bn.track_running_stats
-        running = None
-        if self.training and bn.track_running_stats:  # train-mode buffer update, done inside the BN bookkeeping kernel
-            R = float(Xp.size(0))
-            running = (bn.running_mean, bn.running_var, bn.num_batches_tracked, L.dense_pos,
-                       bn_momentum(bn), R / max(R - 1.0, 1.0))
+        # (running: the train-mode buffer update, done inside the BN bookkeeping kernel)
         y, mean_p, var_p = ops.gat_mlp(aggr, *mlp_ops, use_batch_stats, bn.eps, p_drop if self.training else 0.0,
-                                       apply_act, running, ones_col=L.ones_col)
+                                       apply_act, bn_running(bn, L, Xp.size(0), self.training), ones_col=L.ones_col)
         return y, a
 
     @_fp32_region
@@ -416,7 +416,7 @@ class QAGNN_Message_Passing(nn.Module):
         S = ops.gelu_dropout(pre, 0.0, False)
         # room in S's zero padding for the node-type indicators: the type-table gradients then fall out of the S^T dKMQ products
         h = self.hidden_size // 2
-        self._tab_col = h if (S.size(1) - h >= self.n_ntype and ops.BYPRODUCT_GRADS) else -1
+        self._tab_col = h if S.size(1) - h >= self.n_ntype else -1
         if self._tab_col >= 0:
             S = ops.type_indicators(S, node_type_flat, h, self.n_ntype)
         return temb, S
@@ -471,7 +471,7 @@ class QAGNN_Message_Passing(nn.Module):
             # one running total each (ops.GradAcc) instead of leaving k (2) gradients for autograd to add; hop 0's backward runs
             # last and returns the totals
             accS, accX = (ops.GradAcc(), ops.GradAcc()) if self.k > 0 else (None, None)
-            if self.k > 0 and ops.use_fused_hop(Hp.size(0)) and hasattr(ops.kernels(), 'stack_fwd') and ops.FUSED_STACK:
+            if stack_native:
                 # host-bound batches: all k hops as ONE native call and one autograd node each way (csrc/hop.hip)
                 prms, runnings = [], []
                 for l, (layer, pk) in enumerate(zip(self.gnn_layers, per_layer)):
@@ -479,10 +479,7 @@ class QAGNN_Message_Passing(nn.Module):
                     Wx_t, Wx, Ws_t, Ws = pk[:4]
                     W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p = pk[8:]
                     prms.append((Wx_t, Wx, Ws_t, Ws, TT[l], ekem[l], W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p))
-                    R = float(Hp.size(0))
-                    runnings.append((bn.running_mean, bn.running_var, bn.num_batches_tracked, L.dense_pos, bn_momentum(bn),
-                                     R / max(R - 1.0, 1.0)) if (self.training and bn.track_running_stats) else None)
-                bn0 = self.gnn_layers[0].mlp[1]
+                    runnings.append(bn_running(bn, L, Hp.size(0), self.training))
                 Xp = ops.gat_stack(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms,
                                    self.training or not bn0.track_running_stats, bn0.eps, self.dropout_rate if self.training else 0.0,
                                    runnings, accX=accX, tab_col=(self._tab_col, L.ones_col))

@@ -9,6 +9,8 @@ Internal layout ("head-padded"): a feature row of d = H*dh floats is stored as H
 floats, DP = H*HP per row, pads are zero.  All matrices handed to the kernels are contiguous 2-D fp32.
 """
 import math
+import os
+import weakref
 
 import torch
 from torch.amp import custom_bwd, custom_fwd
@@ -37,11 +39,6 @@ def set_kernels(k):
 
 H_HEADS = 4  # GATConvE hard-codes head_count=4 (reference modeling_qagnn.py:387)
 
-# bias / type-table gradients as rows of weight-gradient products that are computed anyway (type indicators in S's padding, a column
-# of ones in relu(bn(h1))) wherever the layout has a padding column for them; the stand-alone column reductions remain for layouts
-# without padding (dim_per_head a multiple of 4).  (A/B of round 3: profiles/r3_run9_byproduct_grads_ab.txt)
-BYPRODUCT_GRADS = True
-
 
 def roundup(x, m):
     return (x + m - 1) // m * m
@@ -61,8 +58,11 @@ class HeadLayout:
         h, i = j // self.HP, j % self.HP
         self.dense_pos = torch.nonzero(i < self.dh).flatten().to(device)  # [d] padded position of dense index k (ascending)
         # a padding column (exactly 0 in every activation, zero row / column in every packed weight), or -1 when dh needs no padding:
-        # where relu(bn(h1)) is made to carry a column of ones (see GatMlpFn)
-        self.ones_col = self.dh if (self.HP > self.dh and BYPRODUCT_GRADS) else -1
+        # where relu(bn(h1)) is made to carry a column of ones (see GatMlpFn).  Bias / type-table gradients are rows of weight-gradient
+        # products that are computed anyway (type indicators in S's padding, this column of ones) wherever the layout has a padding
+        # column for them; the stand-alone column reductions remain for layouts without padding (dim_per_head a multiple of 4).
+        # (A/B of round 3: profiles/r3_run9_byproduct_grads_ab.txt)
+        self.ones_col = self.dh if self.HP > self.dh else -1
 
     def pad(self, x):
         """[*, d] -> [*, DP] (zeros in the pads): one constant-pad of the [*, H, dh] view (its backward is a slice, no scatter)."""
@@ -72,6 +72,16 @@ class HeadLayout:
     def unpad(self, xp):
         lead = xp.shape[:-1]
         return xp.reshape(*lead, H_HEADS, self.HP)[..., :self.dh].reshape(*lead, self.d)
+
+
+def _split_by_shape(flat, shapes):
+    """consecutive pieces of the flat tensor, viewed in the given shapes"""
+    out, off = [], 0
+    for shape in shapes:
+        n = math.prod(shape)
+        out.append(flat[off:off + n].view(shape))
+        off += n
+    return tuple(out)
 
 
 class _PlanGatherFn(torch.autograd.Function):
@@ -99,14 +109,7 @@ class _PlanGatherFn(torch.autograd.Function):
         K = plan.kernels_for(grads)
         if K is not None and any(g is not None for g in grads):  # one launch: every source element sums its packed copies' gradients
             gsrc = K.gather_multi_sum([None if g is None else g.contiguous() for g in grads], plan.inv_tid, plan.inv_off)
-            out, off = [], 0
-            for shape in ctx.src_shapes:
-                n = 1
-                for v in shape:
-                    n *= v
-                out.append(gsrc[off:off + n].view(shape))
-                off += n
-            return (None,) + tuple(out)
+            return (None,) + _split_by_shape(gsrc, ctx.src_shapes)
         parts = []
         z = plan.zeros  # cached zeros: operands that received no gradient (the non-transposed weight copies) cost no fill kernel
         for g, (a, n, shape), n4 in zip(grads, plan.slices, plan.padded):
@@ -118,14 +121,7 @@ class _PlanGatherFn(torch.autograd.Function):
         gsrc = gflat.index_select(0, plan.inv[0])
         for k in range(1, len(plan.inv)):
             gsrc = gsrc + gflat.index_select(0, plan.inv[k])
-        out, off = [], 0
-        for shape in ctx.src_shapes:
-            n = 1
-            for v in shape:
-                n *= v
-            out.append(gsrc[off:off + n].view(shape))
-            off += n
-        return (None,) + tuple(out)
+        return (None,) + _split_by_shape(gsrc, ctx.src_shapes)
 
 
 class GatherPlan:
@@ -212,8 +208,6 @@ class GatherPlan:
 
 
 # ------------------------------------------------------------------------------------------------------------------
-import os as _os
-
 _SIDE_STREAMS = {}
 # (Bias gradients as a by-product of the weight-gradient GEMM's k-loop -- the colsum_groups form of qagnn_gemm_tn_colsum_f32 -- measured
 # slower than the separate column sums, profiles/r1_run21_fused_colsum_ab.txt, and is no longer wired into the operators.)
@@ -231,14 +225,15 @@ _SIDE_STREAMS = {}
 # gradients, GatherPlan's backward (plus an end-of-backward engine callback as a safety net).  Rules that make this safe:
 #   * only operators created inside `wgrad_scope()` defer, and the stack guarantees that every weight operand there comes
 #     straight out of GatherPlan, so nothing on the main stream reads a deferred gradient before the join;
-#   * a gradient consumed inside the graph is either computed on the main stream (the grouped column reduction over dC when
-#     `BYPRODUCT_GRADS` is off) or -- the default -- handed out as a VIEW of a deferred weight-gradient product (the node-type-table
+#   * a gradient consumed inside the graph is either computed on the main stream (the grouped column reduction over dC where S
+#     has no padding columns for the type indicators) or handed out as a VIEW of a deferred weight-gradient product (the node-type-table
 #     gradient = rows [tab_col, tab_col + T) of S^T dC, LinearNNFn.tabcol) whose ONE consumer, SplitColsFn.backward, joins the side
 #     stream before it reads; hop() refuses the combination "table gradient as a by-product" + "tables computed inside the hop"
 #     (torch.addmm would read the view without a join);
-#   * outputs are allocated on the main stream up front; every input of a queued launch is kept alive until the join, so
-#     the caching allocator cannot hand its memory to a main-stream kernel while the side stream still reads it.
-WGRAD_OVERLAP = _os.environ.get('QAGNN_WGRAD_OVERLAP', '1') == '1'
+#   * outputs are allocated on the main stream up front; every input of a queued launch -- its operand-maximum words included -- is
+#     kept alive until the join, so the caching allocator cannot hand its memory to a main-stream kernel while the side stream still
+#     reads it (_wgrad below is the one place that allocates, queues and keeps).
+WGRAD_OVERLAP = os.environ.get('QAGNN_WGRAD_OVERLAP', '1') == '1'
 _DEFER = [False]
 
 
@@ -258,12 +253,7 @@ class wgrad_scope:
 
 
 # QAGNN_WGRAD_POISON=1 (tests): deferred outputs start as NaN, so a reader that runs before the queued launch shows up
-WGRAD_POISON = _os.environ.get('QAGNN_WGRAD_POISON', '0') == '1'
-
-
-def _wg_empty(ref, shape):
-    t = ref.new_empty(shape)
-    return t.fill_(float('nan')) if WGRAD_POISON else t
+WGRAD_POISON = os.environ.get('QAGNN_WGRAD_POISON', '0') == '1'
 
 
 class _WgradQueue:
@@ -303,6 +293,20 @@ def defer_wgrads(jobs, keep):
     if not q.callback_queued:  # whatever happens, the queue is issued and joined before backward() returns
         torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
         q.callback_queued = True
+
+
+def _wgrad(defer, ref, shape, launch, reads):
+    """One weight-gradient product (or column sum) of a backward: launch(out) -> out, where out=None lets the provider allocate.
+    Not `defer`: launched here and now.  `defer` (the operator was built inside a wgrad_scope): the [*shape] output is allocated here,
+    on the main stream, and the launch is queued (defer_wgrads) with `reads` -- EVERY tensor it reads, operand-maximum words included --
+    on the keep list."""
+    if not defer:
+        return launch(None)
+    out = ref.new_empty(shape)
+    if WGRAD_POISON:
+        out.fill_(float('nan'))
+    defer_wgrads([lambda: launch(out)], reads)
+    return out
 
 
 def flush_wgrads(ref=None):
@@ -346,7 +350,7 @@ def join_wgrads(ref=None):
 # is one MFMA-bound gather-GEMM (entity table x cpt_transform, ~0.28 ms).  QAGNN.forward therefore issues the preparation on a
 # second stream first and joins it right before the stack.  No autograd node runs on that stream; the graph storage is
 # allocated there and only read elsewhere after the join (and freed after the step, i.e. before the next fork).
-PREP_OVERLAP = _os.environ.get('QAGNN_PREP_OVERLAP', '1') == '1'
+PREP_OVERLAP = os.environ.get('QAGNN_PREP_OVERLAP', '1') == '1'
 _PREP_STREAMS = {}
 
 
@@ -388,7 +392,6 @@ def graph_prep_async(adj, node_type, n_etype, n_ntype, block_n):
 # (module attributes, not environment switches: the A/B runs that set them are recorded in profiles/r4_run28_round4_switches_ab.txt;
 # the tests still flip GATHER_FUSED to compare the one-launch gather with the cat + index_select form it replaces)
 GATHER_FUSED = True     # GatherPlan through qagnn_gather_multi{,_sum}_f32
-HEAD_FUSED = True       # the head behind the pooling as two kernels each way
 
 
 def pack_min_rows(K):
@@ -412,7 +415,6 @@ def prepack_weights(owner, pairs, rows):
     K = kernels()
     if not (hasattr(K, 'prepack') and rows >= pack_min_rows(K) and pairs and pairs[0][0].is_cuda):
         return
-    import weakref
     if _PREPACK_STATE is None:
         _PREPACK_STATE = weakref.WeakKeyDictionary()
     st = _PREPACK_STATE.get(owner)
@@ -486,72 +488,38 @@ class LinearNNFn(torch.autograd.Function):
         has_bias, has_tab, G = ctx.has
         dbias = drowtab = None
         want_tab, want_bias = has_tab and need[7], has_bias and need[6]
-        am1, am2 = getattr(ctx, 'am', (None, None))
+        am1, am2 = ctx.am
         nn_kw = dict(a_amax1=amc) if amc is not None else {}
         tn_h2 = amc is not None and am1 is not None and (A2 is None or am2 is not None)
-        if ctx.defer:  # weight gradients queued for the next edge backward (see defer_wgrads)
-            jobs, dB1t, dB2t = [], None, None
-            if need[1] and A2 is not None and need[4]:
-                # both weight gradients share dC: ONE split-K launch and one chunk sum into one [K1 + K2, No] buffer (qagnn_gemm_tn2_f32)
-                joint = _wg_empty(dC, (A1.size(1) + A2.size(1), dC.size(1)))
-                dB1t, dB2t = joint[:A1.size(1)], joint[A1.size(1):]
-                jobs.append((lambda: K.gemm_tn_h2(A1, dC, am1, amc, A2=A2, amax_a2=am2, out=joint)) if tn_h2 else (lambda: K.gemm_tn2(A1, A2, dC, out=joint)))
-            else:
-                if need[1]:
-                    dB1t = _wg_empty(dC, (A1.size(1), dC.size(1)))
-                    jobs.append(lambda: K.gemm_tn(A1, dC, out=dB1t))
-                if A2 is not None and need[4]:
-                    dB2t = _wg_empty(dC, (A2.size(1), dC.size(1)))
-                    jobs.append(lambda: K.gemm_tn(A2, dC, out=dB2t))
-            if want_tab and ctx.tabcol >= 0 and dB2t is not None and not want_bias:
-                drowtab = dB2t[ctx.tabcol:ctx.tabcol + G]  # (deferred with dB2t: its consumer, SplitColsFn.backward, joins the side stream)
-            elif want_tab:  # consumed inside the graph (table GEMM backward): stays on the main stream
-                drowtab = K.colsum(dC, rowidx, G)
-                if want_bias:
-                    dbias = drowtab.sum(0)
-            elif want_bias:
-                cs = _wg_empty(dC, (1, dC.size(1)))
-                jobs.append(lambda: K.colsum(dC, out=cs))
-                dbias = cs[0]
-            defer_wgrads(jobs, (A1, A2, dC))
-            acc1, last1, acc2, last2 = ctx.acc
-            dA1 = dA2 = None
-            if need[0]:
-                if acc1 is None and A2 is None and dC.size(0) <= 2048 and dC.size(1) >= 512 and dC.size(0) % 4 == 0:
-                    dA1 = K.gemm_tn(dC.t().contiguous(), B1)  # few rows, long reduction: see below
-                else:
-                    dA1 = _acc_grad(acc1, last1, lambda out, accu: K.gemm_nn(dC, B1, out=out, accumulate=accu, B1n=B1t, **nn_kw))
-            if A2 is not None and need[3]:
-                dA2 = _acc_grad(acc2, last2, lambda out, accu: K.gemm_nn(dC, B2, out=out, accumulate=accu, B1n=B2t, **nn_kw))
-            return dA1, dB1t, None, dA2, dB2t, None, dbias, drowtab, None, None, None
-        cs = None
-        joint = None
-        if need[1] and A2 is not None and need[4]:  # (see the deferred path)
-            joint = K.gemm_tn_h2(A1, dC, am1, amc, A2=A2, amax_a2=am2) if tn_h2 else K.gemm_tn2(A1, A2, dC)
-        dB1t = joint[:A1.size(1)] if joint is not None else (K.gemm_tn(A1, dC) if need[1] else None)
+        defer, No = ctx.defer, dC.size(1)  # defer: weight gradients queued for the next edge backward (see defer_wgrads)
+        dB1t = dB2t = joint = None
+        if need[1] and A2 is not None and need[4]:
+            # both weight gradients share dC: ONE split-K launch and one chunk sum into one [K1 + K2, No] buffer (qagnn_gemm_tn2_f32)
+            launch = (lambda out: K.gemm_tn_h2(A1, dC, am1, amc, A2=A2, amax_a2=am2, out=out)) if tn_h2 else (lambda out: K.gemm_tn2(A1, A2, dC, out=out))
+            joint = _wgrad(defer, dC, (A1.size(1) + A2.size(1), No), launch, (A1, A2, dC, am1, am2, amc))
+            dB1t, dB2t = joint[:A1.size(1)], joint[A1.size(1):]
+        elif need[1]:
+            dB1t = _wgrad(defer, dC, (A1.size(1), No), lambda out: K.gemm_tn(A1, dC, out=out), (A1, dC))
+        # the row-table gradient as rows of dB2t (deferred with it: its consumer, SplitColsFn.backward, joins the side stream)
         tab_from_wgrad = want_tab and not want_bias and ctx.tabcol >= 0 and A2 is not None and need[4]
-        if (want_tab or want_bias) and not tab_from_wgrad:
-            cs = K.colsum(dC, rowidx if want_tab else None, G if want_tab else 1)
-        if joint is not None:
-            dB2t = joint[A1.size(1):]
-        else:
-            dB2t = K.gemm_tn(A2, dC) if (A2 is not None and need[4]) else None
-        if want_tab and ctx.tabcol >= 0 and dB2t is not None and cs is None:
-            cs = dB2t[ctx.tabcol:ctx.tabcol + G]
-        if want_tab:
-            drowtab = cs
+        if want_tab and not tab_from_wgrad:  # consumed inside the graph (table GEMM backward): stays on the main stream
+            drowtab = K.colsum(dC, rowidx, G)
             if want_bias:
-                dbias = cs.sum(0)
+                dbias = drowtab.sum(0)
         elif want_bias:
-            dbias = cs[0]
+            dbias = _wgrad(defer, dC, (1, No), lambda out: K.colsum(dC, out=out), (dC,))[0]
+        if joint is None and A2 is not None and need[4]:
+            dB2t = _wgrad(defer, dC, (A2.size(1), No), lambda out: K.gemm_tn(A2, dC, out=out), (A2, dC))
+        if tab_from_wgrad:
+            drowtab = dB2t[ctx.tabcol:ctx.tabcol + G]
         acc1, last1, acc2, last2 = ctx.acc
-        if need[0] and acc1 is None and A2 is None and dC.size(0) <= 2048 and dC.size(1) >= 512 and dC.size(0) % 4 == 0:
+        dA1 = dA2 = None
+        if need[0] and acc1 is None and A2 is None and dC.size(0) <= 2048 and No >= 512 and dC.size(0) % 4 == 0:
             # few rows, long reduction (the class tables: 612 x 2080): an NN launch would be 5 blocks walking 130 k-tiles one
             # after the other; the split-K weight-gradient kernel computes the same product as (dC^T)^T B1 in parallel chunks
             dA1 = K.gemm_tn(dC.t().contiguous(), B1)
-        else:
-            dA1 = _acc_grad(acc1, last1, lambda out, accu: K.gemm_nn(dC, B1, out=out, accumulate=accu, B1n=B1t, **nn_kw)) if need[0] else None
-        dA2 = None
+        elif need[0]:
+            dA1 = _acc_grad(acc1, last1, lambda out, accu: K.gemm_nn(dC, B1, out=out, accumulate=accu, B1n=B1t, **nn_kw))
         if A2 is not None and need[3]:
             dA2 = _acc_grad(acc2, last2, lambda out, accu: K.gemm_nn(dC, B2, out=out, accumulate=accu, B1n=B2t, **nn_kw))
         return dA1, dB1t, None, dA2, dB2t, None, dbias, drowtab, None, None, None
@@ -602,17 +570,16 @@ def split_cols(X, k):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# ------------------------------------------------------------------------------------------------------------------
 # Operand maxima for the three-MFMA GEMM form (csrc/gemm_nn2.hip), where a tensor is produced by one operator and read by another: the
 # producer leaves max |.| in a 4-word int32 tensor and NOTES it against the tensor object; the consumer (the natively sequenced stack)
 # looks it up and hands the word to the library (qagnn_hop_args.x_amax / s_amax), which then skips its own reduction pass.  An entry is
 # valid for exactly the tensor object it was noted for, at the version it had (an in-place op invalidates it); anything else -- no entry,
-# a dead tensor, a view, a modified tensor -- is a miss, and a miss only costs the reduction pass.
+# a dead tensor, a view, a modified tensor -- is a miss, and a miss only costs the reduction pass.  (A key built from the address of the
+# DATA would not do: the allocator hands a freed address to the next tensor, which would inherit a stranger's maximum.)
 _AMAX_NOTES = {}
 
 
 def amax_note(t, word):
-    import weakref
     key = id(t)
     _AMAX_NOTES[key] = (weakref.ref(t, lambda _r, k=key: _AMAX_NOTES.pop(k, None)), t._version, word)
     return t
@@ -669,7 +636,7 @@ def _rank():
         if dist.is_available() and dist.is_initialized():
             _rank_salt[0] = dist.get_rank()
         else:
-            return int(_os.environ.get('RANK', '0'))  # not cached: the group may be initialised later
+            return int(os.environ.get('RANK', '0'))  # not cached: the group may be initialised later
     return _rank_salt[0]
 
 
@@ -752,6 +719,58 @@ def edge_attention(KMQ, EkEm, graph, HP, qscale):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# The mlp half of a hop (GATConvE.mlp: Lin1 -> BatchNorm -> ReLU -> Lin2), stated once against the provider interface: GatMlpFn and
+# hop_{fwd,bwd}_composed below run these.
+def _colstats_ok(K, rows, k1, no):
+    fn = getattr(K, 'colstats_supported', None)
+    return fn is not None and fn(rows, k1, no)
+
+
+def _mlp_fwd(K, aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean, run_var, batch_stats, eps, running, ones_col, row_weight=None):
+    """-> (h1, out, stats) with stats = mean | var | invstd | scale | shift: a [5, C] tensor or a 5-tuple of [C] tensors.
+    row_weight [R] (sums to 1): rows enter the batch statistics with these weights instead of 1/R."""
+    R = aggr.size(0)
+    if batch_stats and row_weight is None and _colstats_ok(K, R, aggr.size(1), W1t.size(1)):
+        # batch statistics as a by-product of the first Linear's GEMM epilogue (per-tile partials) + ONE launch that combines
+        # them and does the BatchNorm bookkeeping, instead of two more passes over h1 and five launches
+        h1, part = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1, colstats=True)
+        stats = K.bn_stats_finalize(part, R, gamma, beta, eps, running, ones_col)
+    else:
+        h1 = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1)
+        if batch_stats:
+            sc = 1.0 / R if row_weight is None else 1.0
+            mean = K.colsum(h1, scale=sc, roww=row_weight)[0]
+            var = K.colvar_sum(h1, mean, scale=sc, roww=row_weight)  # biased
+        else:
+            mean, var = run_mean, run_var
+        # invstd / scale / shift and (train mode) the module's running-statistics update: one launch
+        stats = (mean, var, *K.bn_finalize(mean, var, gamma, beta, eps, running, ones_col))
+    out = K.gemm_nn(h1, W2t, bias=b2, a_scale=stats[3], a_shift=stats[4], B1n=W2)
+    return h1, out, stats
+
+
+def _mlp_bwd(K, defer, aggr, h1, dout, mean, invstd, scale, shift, gamma, W1t, W1, W2t, W2, ones_col, batch_stats, row_weight=None,
+             need_daggr=True, db2=None):
+    """-> (daggr, dW1t, db1, dgamma, dbeta, dW2t, db2); `defer`: the two weight-gradient products are queued (_wgrad).
+    ones_col >= 0: relu(bn(h1)) carries a column of ones there, so row ones_col of dW2t = relu(bn(h1))^T dout IS colsum(dout) (a view,
+    deferred with dW2t: its only reader is GatherPlan's backward, which joins the side stream); else the column sum the caller
+    passed as `db2`, or one taken here."""
+    R = aggr.size(0)
+    dW2t = _wgrad(defer, dout, (h1.size(1), dout.size(1)), lambda out: K.gemm_tn(h1, dout, a_scale=scale, a_shift=shift, out=out),
+                  (h1, dout, scale, shift))
+    if ones_col >= 0:
+        db2 = dW2t[ones_col]
+    elif db2 is None:
+        db2 = K.colsum(dout)[0]
+    dr = K.gemm_nn(dout, W2, B1n=W2t)
+    red = K.bn_bwd_reduce(dr, h1, mean, invstd, scale, shift)  # [sum dy, sum dy*hhat] = dbeta, dgamma
+    dh1, db1 = K.bn_relu_bwd_colsum(dr, h1, mean, invstd, scale, shift, gamma, red, 1.0 / R if batch_stats else 0.0,
+                                    roww=row_weight if batch_stats else None)
+    dW1t = _wgrad(defer, dout, (aggr.size(1), h1.size(1)), lambda out: K.gemm_tn(aggr, dh1, out=out), (aggr, dh1))
+    daggr = K.gemm_nn(dh1, W1, B1n=W1t) if need_daggr else None
+    return daggr, dW1t, db1, red[1], red[0], dW2t, db2
+
+
 class GatMlpFn(torch.autograd.Function):
     """GATConvE.mlp + activation of one hop, fused:  X' = dropout(gelu(Lin2(relu(BN(Lin1(aggr))))))
 
@@ -766,27 +785,12 @@ class GatMlpFn(torch.autograd.Function):
     def forward(ctx, aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean, run_var, training, eps, p, seed, apply_act, running,
                 row_weight, ones_col=-1):
         K = kernels()
-        R = aggr.size(0)
-        if training and row_weight is None and _colstats_ok(K, R, aggr.size(1), W1t.size(1)):
-            # batch statistics as a by-product of the first Linear's GEMM epilogue (per-tile partials) + ONE launch that combines
-            # them and does the BatchNorm bookkeeping, instead of two more passes over h1 and five launches
-            h1, part = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1, colstats=True)
-            mean, var, invstd, scale, shift = K.bn_stats_finalize(part, R, gamma, beta, eps, running, ones_col).unbind(0)
-        else:
-            h1 = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1)
-            if training:
-                sc = 1.0 / R if row_weight is None else 1.0  # row_weight [R] (sums to 1): weighted statistics
-                mean = K.colsum(h1, scale=sc, roww=row_weight)[0]
-                var = K.colvar_sum(h1, mean, scale=sc, roww=row_weight)  # biased
-            else:
-                mean, var = run_mean, run_var
-            # invstd / scale / shift and (train mode) the module's running-statistics update: one launch
-            invstd, scale, shift = K.bn_finalize(mean, var, gamma, beta, eps, running, ones_col)
-        out = K.gemm_nn(h1, W2t, bias=b2, a_scale=scale, a_shift=shift, B1n=W2)
+        h1, out, stats = _mlp_fwd(K, aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean, run_var, training, eps, running, ones_col, row_weight)
+        mean, var, invstd, scale, shift = stats
         y = K.gelu_dropout_fwd(out, p, seed) if apply_act else out
         ctx.ones_col = ones_col
         ctx.save_for_backward(aggr, h1, out, mean, invstd, scale, shift, W1, W2, gamma, row_weight, W1t, W2t)
-        ctx.cfg = (training, p, seed, R, apply_act)
+        ctx.cfg = (training, p, seed, apply_act)
         ctx.defer = _DEFER[0]
         ctx.mark_non_differentiable(mean, var)
         ctx.set_materialize_grads(False)  # (no zero-filled stand-ins for the gradients of mean / var)
@@ -799,40 +803,14 @@ class GatMlpFn(torch.autograd.Function):
             return (None,) * 19
         K = kernels()
         aggr, h1, out, mean, invstd, scale, shift, W1, W2, gamma, row_weight, W1t, W2t = ctx.saved_tensors
-        training, p, seed, R, apply_act = ctx.cfg
+        training, p, seed, apply_act = ctx.cfg
         dout = K.gelu_dropout_bwd(out, dy.contiguous(), p, seed) if apply_act else dy.contiguous()
-        oc = ctx.ones_col  # >= 0: relu(bn(h1)) carries a column of ones there, so row oc of dW2t = relu(bn(h1))^T dout IS colsum(dout)
-        db2 = K.colsum(dout)[0] if oc < 0 else None
-        if ctx.defer:  # weight gradients of both Linears queued for the next edge backward (see defer_wgrads)
-            Cc = dout.size(1)
-            dW2t = _wg_empty(dout, (h1.size(1), Cc))
-            if oc >= 0:
-                db2 = dW2t[oc]  # deferred with dW2t; its only reader is GatherPlan's backward, which joins the side stream
-            dr = K.gemm_nn(dout, W2, B1n=W2t)
-            red = K.bn_bwd_reduce(dr, h1, mean, invstd, scale, shift)
-            dh1, db1 = K.bn_relu_bwd_colsum(dr, h1, mean, invstd, scale, shift, gamma, red, 1.0 / R if training else 0.0,
-                                            roww=row_weight if training else None)
-            dW1t = _wg_empty(dout, (aggr.size(1), h1.size(1)))
-            defer_wgrads([lambda: K.gemm_tn(h1, dout, a_scale=scale, a_shift=shift, out=dW2t), lambda: K.gemm_tn(aggr, dh1, out=dW1t)],
-                         (h1, dout, scale, shift, aggr, dh1))
-            daggr = K.gemm_nn(dh1, W1, B1n=W1t) if ctx.needs_input_grad[0] else None
-            return (daggr, dW1t, None, db1, red[1], red[0], dW2t, None, db2, None, None, None, None, None, None, None, None, None, None)
-        dW2t = K.gemm_tn(h1, dout, a_scale=scale, a_shift=shift)
-        if oc >= 0:
-            db2 = dW2t[oc]
-        dr = K.gemm_nn(dout, W2, B1n=W2t)
-        red = K.bn_bwd_reduce(dr, h1, mean, invstd, scale, shift)  # [sum dy, sum dy*hhat]
-        dbeta, dgamma = red[0], red[1]
-        dh1, db1 = K.bn_relu_bwd_colsum(dr, h1, mean, invstd, scale, shift, gamma, red, 1.0 / R if training else 0.0,
-                                        roww=row_weight if training else None)
-        dW1t = K.gemm_tn(aggr, dh1)
-        daggr = K.gemm_nn(dh1, W1, B1n=W1t) if ctx.needs_input_grad[0] else None
+        # (defer: weight gradients of both Linears queued for the next edge backward; the bias column sum, where the layout has no
+        # ones column, goes out first and on the main stream either way)
+        db2 = K.colsum(dout)[0] if ctx.ones_col < 0 else None
+        daggr, dW1t, db1, dgamma, dbeta, dW2t, db2 = _mlp_bwd(K, ctx.defer, aggr, h1, dout, mean, invstd, scale, shift, gamma, W1t, W1, W2t, W2,
+                                                              ctx.ones_col, training, row_weight, ctx.needs_input_grad[0], db2)
         return daggr, dW1t, None, db1, dgamma, dbeta, dW2t, None, db2, None, None, None, None, None, None, None, None, None, None
-
-
-def _colstats_ok(K, rows, k1, no):
-    fn = getattr(K, 'colstats_supported', None)
-    return fn is not None and fn(rows, k1, no)
 
 
 def gat_mlp(aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean, run_var, batch_stats, eps, p, apply_act=True, running=None,
@@ -860,14 +838,16 @@ def gat_mlp(aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean, run_var, batc
 # at EVERY size -- it is where the operand maxima of the three-MFMA GEMM form travel from the kernel that produces a tensor to the product
 # that reads it (qagnn_hop_args.amax), and the weight-gradient overlap that favoured the composed path is worth 0.5 % since the kernels
 # fill the chip on their own (DESIGN.md, round 5 visits 8-9; the native stack forks its weight gradients onto a side stream itself).
-_fh = _os.environ.get('QAGNN_FUSED_HOP', 'auto')
+_fh = os.environ.get('QAGNN_FUSED_HOP', 'auto')
 FUSED_HOP = {'1': True, '0': False}.get(_fh, None)  # None = auto
-FUSED_HOP_MAX_ROWS = None  # (auto: no row limit)
 FUSED_STACK = True  # where the native hop is taken, take all k hops in one call (a module attribute: the tests compare the two forms)
 
 
 def use_fused_hop(n_rows):
-    return FUSED_HOP if FUSED_HOP is not None else (FUSED_HOP_MAX_ROWS is None or n_rows < FUSED_HOP_MAX_ROWS)
+    """(auto: at every row count, see above)"""
+    return FUSED_HOP if FUSED_HOP is not None else True
+
+
 HOP_PARAMS = ('Wx_t', 'Wx', 'Ws_t', 'Ws', 'TT', 'EkEm', 'W1t', 'W1', 'b1', 'gamma', 'beta', 'W2t', 'W2', 'b2', 'run_mean_p', 'run_var_p')
 
 
@@ -876,20 +856,8 @@ def hop_fwd_composed(K, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p
     ones_col = cols[1] if isinstance(cols, tuple) else -1
     KMQ = K.gemm_nn(X, Wx_t, S, Ws_t, rowtab=TT, rowidx=ntype, B1n=Wx, B2n=Ws)
     aggr, a, alpha = K.edge_attn_fwd(graph, KMQ, EkEm, HP, qscale)
-    if batch_stats and _colstats_ok(K, aggr.size(0), aggr.size(1), W1t.size(1)):
-        h1, part = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1, colstats=True)
-        stats = K.bn_stats_finalize(part, aggr.size(0), gamma, beta, eps, running, ones_col)
-    else:
-        h1 = K.gemm_nn(aggr, W1t, bias=b1, B1n=W1)
-        if batch_stats:
-            sc = 1.0 / aggr.size(0)
-            mean = K.colsum(h1, scale=sc)[0]
-            var = K.colvar_sum(h1, mean, scale=sc)
-        else:
-            mean, var = run_mean_p, run_var_p
-        invstd, scale, shift = K.bn_finalize(mean, var, gamma, beta, eps, running, ones_col)
-        stats = torch.stack([mean, var, invstd, scale, shift])
-    out = K.gemm_nn(h1, W2t, bias=b2, a_scale=stats[3], a_shift=stats[4], B1n=W2)
+    h1, out, stats = _mlp_fwd(K, aggr, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean_p, run_var_p, batch_stats, eps, running, ones_col)
+    stats = torch.stack(stats) if isinstance(stats, tuple) else stats
     y = K.gelu_dropout_fwd(out, p, seed) if apply_act else out
     return y, (KMQ, torch.stack([a, alpha]), aggr, h1, out, stats)
 
@@ -899,16 +867,10 @@ def hop_bwd_composed(K, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p
     Wx_t, Wx, Ws_t, Ws, TT, EkEm, W1t, W1, b1, gamma, beta, W2t, W2, b2, run_mean_p, run_var_p = prm
     KMQ, aa, aggr, h1, out, stats = saved
     mean, invstd, scale, shift = (stats[0] if batch_stats else run_mean_p), stats[2], stats[3], stats[4]
-    R = aggr.size(0)
     tab_col, ones_col = tab_col if isinstance(tab_col, tuple) else (tab_col, -1)
     dout = K.gelu_dropout_bwd(out, dy, p, seed) if apply_act else dy
-    dW2t = K.gemm_tn(h1, dout, a_scale=scale, a_shift=shift)
-    db2 = K.colsum(dout)[0] if ones_col < 0 else dW2t[ones_col]  # (a view: the bias gradient IS that row)
-    dr = K.gemm_nn(dout, W2, B1n=W2t)
-    red = K.bn_bwd_reduce(dr, h1, mean, invstd, scale, shift)
-    dh1, db1 = K.bn_relu_bwd_colsum(dr, h1, mean, invstd, scale, shift, gamma, red, 1.0 / R if batch_stats else 0.0)
-    dW1t = K.gemm_tn(aggr, dh1)
-    daggr = K.gemm_nn(dh1, W1, B1n=W1t)
+    daggr, dW1t, db1, dgamma, dbeta, dW2t, db2 = _mlp_bwd(K, False, aggr, h1, dout, mean, invstd, scale, shift, gamma, W1t, W1, W2t, W2,
+                                                          ones_col, batch_stats)
     dKMQ, dEkEm = K.edge_attn_bwd(graph, KMQ, EkEm, HP, qscale, aa[0], aa[1], daggr)
     if S is not None:  # one launch for both (qagnn_gemm_tn2_f32), like qagnn_hop_bwd_f32 when its two outputs are adjacent
         joint = K.gemm_tn2(X, S, dKMQ)
@@ -921,7 +883,7 @@ def hop_bwd_composed(K, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p
         dTT = K.colsum(dKMQ, ntype, TT.size(0))
     dX = K.gemm_nn(dKMQ, Wx, out=dX_acc, accumulate=dX_acc is not None, B1n=Wx_t) if need_dX else None
     dS = K.gemm_nn(dKMQ, Ws, out=dS_acc, accumulate=dS_acc is not None, B1n=Ws_t) if (S is not None and need_dS) else None
-    return dX, dS, dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, red[1], red[0], dW2t, db2
+    return dX, dS, dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dgamma, dbeta, dW2t, db2
 
 
 class HopFn(torch.autograd.Function):
@@ -1108,7 +1070,7 @@ def head_supported(nh, dv, width, n):
     K = kernels()
     lim = getattr(K, 'HEAD_LIMITS', None)
     # (k_head_post_{fwd,bwd} index the GNN output as H_HEADS = 4 groups of width / 4 floats: the head-padded layout of HeadLayout)
-    return (HEAD_FUSED and lim is not None and H_HEADS == 4 and nh <= lim[0] and nh * dv <= lim[1] and width <= lim[2] and width % 4 == 0
+    return (lim is not None and H_HEADS == 4 and nh <= lim[0] and nh * dv <= lim[1] and width <= lim[2] and width % 4 == 0
             and pool_attention_supported(nh, width, n))
 
 
@@ -1124,24 +1086,21 @@ def pool_attention_supported(nh, width, n):
     return lim is not None and nh <= lim[0] and width <= lim[1] and width % 4 == 0 and n <= lim[2]
 
 
-_TABLE_AMAX = {}
-
-
 def table_amax(K, table):
     """max |.| of a FROZEN entity table as the device word the three-MFMA GEMM form wants (an upper bound of the maximum over any batch's
-    gathered rows): one reduction pass per table and version, cached -- the first call must not fall inside a stream capture (GraphedStep's
-    warm-up steps are eager).  None where the form does not apply (table not 16-byte / 4-element aligned, provider without the form)."""
+    gathered rows): one reduction pass per table object and version, noted like every other operand maximum (amax_note) -- the first
+    call must not fall inside a stream capture (GraphedStep's warm-up steps are eager).  An in-place update (copy_, load_state_dict)
+    bumps the version and costs a new pass; an edit through `.data` bumps nothing and cannot be seen.  None where the form does not
+    apply (table not 16-byte / 4-element aligned, provider without the form)."""
     if not (getattr(K, 'gemm_split', 1) >= 2 and getattr(K, 'name', '') == 'hip') or table.requires_grad or table.numel() % 4 != 0 \
             or table.data_ptr() % 16 != 0 or not table.is_contiguous():
         return None
-    key = (table.data_ptr(), table._version, table.numel())
-    w = _TABLE_AMAX.get(key)
+    w = amax_lookup(table)
     if w is None:
-        if torch.cuda.is_current_stream_capturing():
+        if table.is_cuda and torch.cuda.is_current_stream_capturing():
             return None
-        if len(_TABLE_AMAX) > 8:
-            _TABLE_AMAX.clear()
-        w = _TABLE_AMAX[key] = K.absmax(table.detach().view(-1))
+        w = K.absmax(table.detach().view(-1))
+        amax_note(table, w)
     return w
 
 

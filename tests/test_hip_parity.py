@@ -722,7 +722,8 @@ def test_operand_maxima_of_the_stack_are_the_true_maxima(case, monkeypatch):
 
 def test_module_level_operand_notes():
     """ops' notes outside the stack: GeluDropoutFn forward / backward with dropout on (max |Y|, max |dX|, exact), table_amax (max |table|, a
-    bound of any gathered rows), and a note invalidated by an in-place op is a miss."""
+    bound of any gathered rows), and a note invalidated by an in-place op is a miss.  The table's word belongs to the tensor object:
+    a later table in the freed block of an earlier one gets its own maximum, and an in-place update of a table costs a new pass."""
     with helpers.form_everywhere() as K:
         g = torch.Generator().manual_seed(9)
         X = (torch.randn(300, 64, generator=g) * 3).cuda().requires_grad_(True)
@@ -744,6 +745,13 @@ def test_module_level_operand_notes():
         tw = ops.table_amax(K, table)
         idx = torch.randint(0, 500, (60,), generator=g).cuda()
         assert tw[0].item() == _bits(table) and _wf(tw[0].item()) >= table[idx].abs().max().item()
+        assert ops.table_amax(K, table) is tw  # (noted: no second pass)
+        del table, idx
+        big = torch.randn(500, 32, generator=g) * 100.0
+        table2 = big.cuda()  # (same size, right after the free: the caching allocator hands out the block the first table lay in)
+        assert ops.table_amax(K, table2)[0].item() == _bits(table2) != tw[0].item()
+        table2.copy_(big.cuda() * 0.01)  # (in place: the version counter moves)
+        assert ops.table_amax(K, table2)[0].item() == _bits(table2)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

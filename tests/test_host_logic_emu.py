@@ -200,11 +200,18 @@ def test_unsupported_shapes_raise():
         ops.HeadLayout(4 * 68, 'cpu')
 
 
-@pytest.mark.parametrize('fused_hop', [False, True])
-def test_deferred_weight_gradients_are_joined_before_any_reader(monkeypatch, fused_hop):
+_HOST_MODE_GRADS = {}  # the gradients of the first host mode the test below ran: every other mode must reproduce them bit for bit
+
+
+# (FUSED_STACK = True is the module's default: those two cases keep the ids they had before the stack form became a parameter)
+@pytest.mark.parametrize('fused_hop, fused_stack', [pytest.param(False, True, id='False'), pytest.param(True, True, id='True'),
+                                                    pytest.param(False, False, id='False-hop_by_hop'), pytest.param(True, False, id='True-hop_by_hop')])
+def test_deferred_weight_gradients_are_joined_before_any_reader(monkeypatch, fused_hop, fused_stack):
     """QAGNN_WGRAD_OVERLAP: inside the stack the weight-gradient launches are queued and issued later (on the GPU: on a side
     stream under the edge backward).  With the queued outputs poisoned (NaN until the launch runs) the gradients must still
-    equal those of the immediate path -- i.e. nobody reads a deferred gradient before GatherPlan's backward joins."""
+    equal those of the immediate path -- i.e. nobody reads a deferred gradient before GatherPlan's backward joins.
+    All eight host modes (FUSED_HOP x FUSED_STACK x WGRAD_OVERLAP) sequence the same provider calls on the same operands: on the
+    emulation their gradients are equal bit for bit, across the parameters of this test too."""
     case = dict(shape='csqa', nq=2, nc=3, n=20, n_rel=17, std=0.3, train=True, seed=5,
                 cfg=helpers.model_cfg(d=32, k=3, sent_dim=24, n_concept=200, concept_in_dim=16))
     inp = helpers.make_case_inputs(case)
@@ -214,6 +221,7 @@ def test_deferred_weight_gradients_are_joined_before_any_reader(monkeypatch, fus
     old = ops.set_kernels(EmuKernels())
     try:
         monkeypatch.setattr(ops, 'FUSED_HOP', fused_hop)  # False: the hops are composed from LinearNNFn / EdgeAttnFn / GatMlpFn
+        monkeypatch.setattr(ops, 'FUSED_STACK', fused_stack)  # (with FUSED_HOP: one StackFn node, else k HopFn nodes)
         for overlap in (False, True):
             monkeypatch.setattr(ops, 'WGRAD_OVERLAP', overlap)
             monkeypatch.setattr(ops, 'WGRAD_POISON', overlap)
@@ -236,6 +244,46 @@ def test_deferred_weight_gradients_are_joined_before_any_reader(monkeypatch, fus
     for k in grads[True]:
         assert torch.isfinite(grads[True][k]).all(), k
         assert torch.equal(grads[True][k], grads[False][k]), k
+    ref = _HOST_MODE_GRADS.setdefault('grads', grads[False])
+    assert ref.keys() == grads[False].keys()
+    for k in ref:
+        assert torch.equal(grads[False][k], ref[k]), k
+
+
+def test_table_amax_is_noted_for_the_tensor_object_not_for_its_address():
+    """ops.table_amax caches the maximum word of a frozen table.  A second table that comes to lie at the address of a dead one (same
+    data_ptr, same numel, a fresh version counter -- what the caching allocator does with a freed block) must get ITS maximum, not the
+    first table's; and an in-place update of a table (copy_, load_state_dict) must cost a new reduction.  No GPU: a stub provider
+    whose absmax is torch's."""
+    class Stub:
+        name, gemm_split, calls = 'hip', 2, 0
+
+        def absmax(self, x):
+            self.calls += 1
+            return x.abs().max().reshape(1).view(torch.int32).repeat(4)
+
+    def as_float(word):
+        return word[:1].view(torch.float32).item()
+
+    raw = np.zeros(64 * 8 + 4, dtype=np.float32)
+    off = (-raw.ctypes.data % 16) // 4  # a 16-byte aligned window of the buffer
+    buf = raw[off:off + 64 * 8].reshape(64, 8)
+    buf[:] = np.random.default_rng(0).uniform(-1.0, 1.0, buf.shape)
+    K = Stub()
+    A = torch.from_numpy(buf)
+    wa = ops.table_amax(K, A)
+    assert as_float(wa) == float(np.abs(buf).max())
+    assert ops.table_amax(K, A) is wa and K.calls == 1  # (noted: no second pass)
+    ptr = A.data_ptr()
+    del A
+    buf *= 100.0
+    B = torch.from_numpy(buf)
+    assert B.data_ptr() == ptr and B.numel() == 64 * 8 and B._version == 0
+    wb = ops.table_amax(K, B)
+    assert as_float(wb) == B.abs().max().item() == float(np.abs(buf).max()), (as_float(wa), as_float(wb))
+    B.copy_(B * 0.25)  # (in place: the version counter moves)
+    assert as_float(ops.table_amax(K, B)) == B.abs().max().item() and K.calls == 3
+    assert ops.table_amax(K, B[:, :4]) is None  # (a strided view: the form does not apply)
 
 
 @pytest.mark.parametrize('k', [1, 3])
