@@ -4,33 +4,102 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/qagnn_hip.h"
 
 namespace qagnn {
 
 void set_error(const char* fmt, ...);
 
-// weight-gradient products on the bf16 matrix cores (gemm_split.hip), used by qagnn_gemm_tn_f32's dispatch in gemm.hip
-bool tn_split_ok(int R, int Ka, int No, int lda, int ldb, bool gather, bool affine);
-int tn_split_chunk_rows(int R, int Ka, int No, int lo);
-// amax (both launchers): nullptr, or {max|A1|, max|A2|, max|B|} device words -> the three-MFMA form (gemm_nn2.hip, header)
-int launch_tn_split(const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No, const float* sc, const float* sh,
-                    const int64_t* a_rowidx, int chunk_rows, hipStream_t stream, const uint32_t* const* amax = nullptr, int np = 2);
-int tn_split2_chunk_rows(int R, int Ka1, int Ka2, int No, int lo);
-int launch_tn_split2(const float* A1, int lda1, int Ka1, const float* A2, int lda2, int Ka2, const float* B, int ldb, float* P, int R, int No,
-                     int chunk_rows, hipStream_t stream, const uint32_t* const* amax = nullptr, int np = 2);
+// ---- the dense products (gemm_dispatch.hip) -------------------------------------------------------------------
+// A product's ROUTE -- kernel family, tile shape, arithmetic form, where B comes from, chunking, grid, scratch -- is decided once, by
+// nn_route() / tn_route(), and travels as a value: the launchers below (one per kernel template, next to their kernels), the scratch
+// queries of the C ABI and hop.hip all read it.
+struct NnProduct {  // C = [A1|A2] [B1;B2] + epilogue: the ABI's argument block + B as [No][K] (the bf16 / fp16 kernels) + pack scratch
+  const qagnn_gemm_nn_args* a;
+  bool split;  // false: the fp32-MFMA kernel on a->B1 / a->B2 (qagnn_gemm_nn_f32)
+  const float* B1n; int ldn1; const float* B2n; int ldn2;
+  void* ws; int64_t ws_bytes;
+};
+enum class NnFamily { FP32, SPLIT, NN2 };         // k_gemm_nn (gemm.hip), k_gemm_nn_split (gemm_split.hip), k_gemm_nn2 (gemm_nn2.hip)
+enum class NnB { IN_KERNEL, PACK, IMAGE };        // B split inside the kernel / packed into the scratch per call / a registered image
+struct NnRoute {
+  NnFamily family;
+  int nt, np, wv;             // column tiles per block; pieces per operand (3 = exact 3 x bf16 split, 2 = scaled fp16 pair, 1 = fp16); waves
+  bool affine, flat, stats;   // scale / shift prologue; 64-bit flat operand addressing (SPLIT); column statistics in the epilogue
+  NnB b; const void* image;   // NN2
+  int64_t ws_bytes;           // scratch the route writes (PACK), else 0
+  int ntiles, grid;
+};
+inline int num_cus() {  // of the current device at first use; 256 (an MI355X) where there is none
+  static int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    return v;
+  }();
+  return n;
+}
+static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// persistent launch shape: tiles of rows_per_tile x nt * 16 outputs walked by at most per_cu blocks per CU (a multiple of 8: the
+// block -> XCD mapping survives the tile walk)
+inline void nn_grid(NnRoute& r, int M, int No, int rows_per_tile, int per_cu) {
+  r.ntiles = cdiv(No, r.nt * 16) * cdiv(M, rows_per_tile);
+  const int cap = (num_cus() * per_cu) & ~7;
+  r.grid = r.ntiles < cap ? r.ntiles : cap;
+}
+NnRoute nn_route(const NnProduct& p);
+bool nn_rows_packed(int64_t M);  // rows from which products take packed B images and the scaled forms (qagnn_packed_min_rows)
+int gemm_nn(const NnProduct& p, hipStream_t stream);
+int launch_nn(const NnRoute& r, const qagnn_gemm_nn_args& a, hipStream_t stream);
+int launch_nn_split(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
+// (b != IN_KERNEL: B1n = the image, ldn1 = its column tiles per k-tile)
+int launch_nn2(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
+int launch_pack_b(int np, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream);
+namespace nn2 { int walk_tiles(int K1, int K2); }  // k-tiles of 32 that k_gemm_nn2 walks over the two segments
+int64_t nn2_pack_bytes(int No, int K1, int K2, int np);
+const void* nn2_prepack_lookup(const float* B1n, int ldn1, int K1, const float* B2n, int ldn2, int K2, int No, int np);
 
-// NN products, second kernel generation (gemm_nn2.hip): A fragments straight from global memory, B double-buffered in LDS
-bool nn2_ok(const qagnn_gemm_nn_args& a, int ldn1, int ldn2);
-int launch_nn2(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
-// np: the arithmetic form of a packed image -- 3 = exact 3 x bf16 split, 2 = scaled two-piece fp16 split (gemm_nn2.hip, header)
-int64_t nn2_pack_bytes(int No, int K1, int K2, int np = 3);
-int64_t nn2_pack_min_m();  // rows from which products take the packed B image and the three-MFMA form (qagnn_packed_min_rows)
-bool nn2_packed_ok(const qagnn_gemm_nn_args& a, int64_t ws_bytes, int np = 3);
-bool nn2_h2_ok(const qagnn_gemm_nn_args& a);
-const void* nn2_prepack_lookup(const float* B1n, int ldn1, int K1, const float* B2n, int ldn2, int K2, int No, int np = 3);
-int launch_nn2_prepacked(int nt, const qagnn_gemm_nn_args& a, const void* pk, hipStream_t stream, int np = 3);
-int launch_nn2_packed(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream, int np = 3);
+struct TnProduct {  // C [Ka1 (+ Ka2), No] (+)= [A1 | A2]^T B over R rows, through split-K partials in ws
+  const float* A1; int lda1, Ka1;
+  const float* A2; int lda2, Ka2; bool two;        // two: the two-operand product (A2's rows of C follow A1's)
+  const float* B; int ldb;
+  float* C; int ldc, R, No;
+  const float* a_scale; const float* a_shift; const int64_t* a_rowidx; int accumulate;
+  float* bsum; const int64_t* b_rowidx; int groups;  // column sums of B per group, by-product of the same pass
+  const uint32_t* amax[3]; int np;                   // {max|A1|, max|A2|, max|B|} device words + the scaled form they ask for (2 or 1)
+  float* ws;
+};
+// (one operand: A2 == nullptr or Ka2 <= 0)
+inline TnProduct tn_product(const float* A1, int lda1, int Ka1, const float* A2, int lda2, int Ka2, const float* B, int ldb, float* C, int ldc, int R,
+                            int No, const float* a_scale, const float* a_shift, float* ws, const uint32_t* amax_a1 = nullptr,
+                            const uint32_t* amax_a2 = nullptr, const uint32_t* amax_b = nullptr, int np = 3) {
+  TnProduct p = {};
+  p.A1 = A1; p.lda1 = lda1; p.Ka1 = Ka1;
+  if (A2 && Ka2 > 0) { p.A2 = A2; p.lda2 = lda2; p.Ka2 = Ka2; p.two = true; }
+  p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.R = R; p.No = No; p.a_scale = a_scale; p.a_shift = a_shift; p.ws = ws;
+  p.amax[0] = amax_a1; p.amax[1] = amax_a2; p.amax[2] = amax_b; p.np = np;
+  return p;
+}
+enum class TnFamily { RUNTIME, STRIP, SPLIT, WS, PAIR };  // k_gemm_tn, k_gemm_tn_strip (gemm.hip); k_gemm_tn_split, k_gemm_tn_ws (gemm_split.hip);
+                                                          // PAIR: a two-operand product as two single ones
+struct TnRoute {
+  TnFamily family;
+  int kt, nt, waves, np;      // 16-row / 16-column output tiles per block (kt: SPLIT / WS; waves: RUNTIME / STRIP); pieces
+  bool affine, gather, colsum;
+  int chunk_rows, nchunks;
+  bool sum_by4;               // the chunk sum in float4 steps
+  dim3 grid;
+  int64_t ws_elems;           // floats of ws the route writes
+};
+TnRoute tn_route(const TnProduct& p);
+int gemm_tn(const TnProduct& p, hipStream_t stream);
+int launch_tn(const TnRoute& r, const TnProduct& p, float* Pcs, hipStream_t stream);        // Pcs: the column-sum partials (colsum)
+int launch_tn_strip(const TnRoute& r, const TnProduct& p, float* Pcs, hipStream_t stream);
+int launch_tn_split(const TnRoute& r, const TnProduct& p, hipStream_t stream);
+int launch_tn_ws(const TnRoute& r, const TnProduct& p, hipStream_t stream);
+// C (+)= the chunks' partials P [nchunks][rows][No], summed in order (by4: float4 steps -- ldc, No multiples of 4, C 16-byte aligned)
+int launch_sum_chunks(const float* P, float* C, int ldc, int rows, int No, int nchunks, int accumulate, bool by4, hipStream_t stream);
 
 // producers that can leave max |output| behind for the three-MFMA GEMM form (elementwise.hip; amax = nullptr: plain launch)
 int launch_gelu_dropout(const float* X, const float* dY, float* out, int64_t n, float p, uint64_t seed, uint32_t* amax, float* amax_part,
@@ -79,7 +148,33 @@ struct TimedScope {
     }                                                                          \
   } while (0)
 
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// Register budget of k_gemm_nn (gemm.hip): QAGNN_NN_OCC co-resident blocks per CU, which is also what its persistent grid is sized for
+#ifndef QAGNN_NN_OCC
+#define QAGNN_NN_OCC 2  // 0 = leave it to the compiler (it takes ~300 registers for NT = 13: one block per CU)
+#endif
+
+// run-time value -> compile-time constant: f(std::integral_constant<int, V>{}) for the V of the list that equals v (the last V if none does)
+template <int V0, int... Vs, class F>
+inline int dispatch_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
+}
+template <class F>
+inline int dispatch_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+// a kernel that needs more than the default 64 KB of dynamic LDS has its limit raised, once per device
+template <auto KERNEL>
+inline int raise_lds_limit(int bytes, const char* name) {
+  static bool raised[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  if (bytes <= 64 * 1024 || raised[dev & 63]) return QAGNN_OK;
+  hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) { set_error("%s: cannot raise the dynamic LDS limit: %s", name, hipGetErrorString(e)); return QAGNN_EHIP; }
+  raised[dev & 63] = true;
+  return QAGNN_OK;
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // MI355X: 8 XCDs, workgroup b is observed to run on XCD b % 8 (speed only, never correctness).

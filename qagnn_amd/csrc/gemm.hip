@@ -53,9 +53,6 @@ __device__ __forceinline__ void sched_ktile_pipeline() {
 
 // Register budget: QAGNN_NN_OCC co-resident blocks per CU (LDS allows 2).  The budget is a trade: 2 blocks per CU let one
 // block's epilogue stores overlap the other's MFMAs, but cap a wave at 512 / (OCC * WAVES / 4) registers.
-#ifndef QAGNN_NN_OCC
-#define QAGNN_NN_OCC 2  // 0 = leave it to the compiler (it takes ~300 registers for NT = 13: one block per CU)
-#endif
 #if QAGNN_NN_OCC > 0
 #define QAGNN_NN_ATTR __attribute__((amdgpu_waves_per_eu(QAGNN_NN_OCC * WAVES / 4, QAGNN_NN_OCC * WAVES / 4)))
 #else
@@ -239,16 +236,6 @@ __global__ __launch_bounds__(WAVES * 64) QAGNN_NN_ATTR void k_gemm_nn(qagnn_gemm
 // spent on tile padding (the previous fixed 64-row tile wasted 19 % on 208).  With BM = 16*NW the A k-tile is exactly
 // one float4 per thread.  k-tiles of 16 rows, double-buffered, one barrier per tile.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int TN_RC = 256;  // minimum rows per chunk (and the chunking the workspace query assumes): >= 1 block per CU for the
-                            // 208 x 208 gradients at N = 64 000; launches with several tiles per chunk use longer chunks
-constexpr int TN_RC_SMALL = 64;  // ... and for reductions over <= 4096 rows (class tables, C = 612): the k-loop of a chunk is serial
-__host__ __device__ constexpr int tn_min_chunk(int R) { return R <= 4096 ? TN_RC_SMALL : TN_RC; }
-// the bf16-split weight-gradient kernel over <= 4096 rows (10 subgraphs = 2 000 node rows): one 32-row k-tile per chunk puts twice the
-// blocks on the idle chip (2 000 x 208 x 208: 126 instead of 64) and halves each block's serial work (A/B against 64-row chunks:
-// profiles/r3_run18_small_batch_ab.txt).  The workspace query sizes for 32-row chunks there.
-constexpr int TN_RC_SPLIT_SMALL = 32;
-static int tn_split_min_chunk(int R) { return R > 4096 ? TN_RC : TN_RC_SPLIT_SMALL; }
-
 __host__ __device__ constexpr int pitch16(int w) { return (w % 32 == 16) ? w : w + 16; }  // rows k, k+1 land 16 banks apart
 
 template <int NT, bool AFFINE>
@@ -577,273 +564,53 @@ __global__ __launch_bounds__(SC_G * 64) void k_sum_chunks4(const float* __restri
   }
 }
 
-// NN launch shape: 8-wave blocks walking the tiles persistently, QAGNN_NN_OCC (= 2) blocks per CU.  Measured at M = 64000
-// (profiles/r1_gemm_micro.txt): 10-18 % faster than one 128-row tile per 4-wave block; the other forms were removed in round 5.
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
-template <int NT>
-static int launch_nn(const qagnn_gemm_nn_args& a, hipStream_t stream) {
-  // persistent 8-wave blocks, one per CU (QAGNN_NN_OCC per CU in the micro-benchmark builds), XCD-aware tile order: the forms these
-  // replaced (4-wave two-row-tile blocks, one block per tile, launch-order tiles) were A/B-ed in profiles/r1_run23_nn_xcd_ab.txt, r1_run32_gemm_ab.txt
-  constexpr int per_cu = QAGNN_NN_OCC > 0 ? QAGNN_NN_OCC : 1;
+// ---- launchers: one per kernel template, shaped by the product's route (gemm_dispatch.hip) ----------------------------------------
+// NN: 8-wave blocks walking the tiles persistently, QAGNN_NN_OCC (= 2) blocks per CU, XCD-aware tile order.  Measured at M = 64000
+// (profiles/r1_gemm_micro.txt, r1_run23_nn_xcd_ab.txt, r1_run32_gemm_ab.txt): 10-18 % faster than one 128-row tile per 4-wave block.
+int launch_nn(const NnRoute& r, const qagnn_gemm_nn_args& a, hipStream_t stream) {
   qagnn_gemm_nn_args b = a;
   b.xcd_remap = 1;
-  const int ntiles = cdiv(a.No, NT * 16) * cdiv(a.M, NN_BM);
-  const int cap = (num_cus() * per_cu) & ~7;  // multiple of 8: block -> XCD mapping survives the tile walk
-  const int grid = ntiles < cap ? ntiles : cap;
-  if (a.a_scale) k_gemm_nn<NT, true, 8, 1><<<grid, 512, 0, stream>>>(b, ntiles);
-  else k_gemm_nn<NT, false, 8, 1><<<grid, 512, 0, stream>>>(b, ntiles);
-  QAGNN_LAUNCH_CHECK("k_gemm_nn");
+  return dispatch_int<13, 8, 7, 4, 2>(r.nt, [&](auto nt) {
+    return dispatch_bool(r.affine, [&](auto aff) {
+      k_gemm_nn<nt.value, aff.value, 8, 1><<<r.grid, 512, 0, stream>>>(b, r.ntiles);
+      QAGNN_LAUNCH_CHECK("k_gemm_nn");
+      return QAGNN_OK;
+    });
+  });
+}
+
+#define QAGNN_TN_ARGS p.A1, p.lda1, p.B, p.ldb, p.ws, p.R, p.Ka1, p.No, p.a_scale, p.a_shift, p.a_rowidx
+int launch_tn(const TnRoute& r, const TnProduct& p, float* Pcs, hipStream_t stream) {
+  return dispatch_int<13, 8, 7, 4, 2>(r.nt, [&](auto nt) {
+    return dispatch_bool(r.affine, [&](auto aff) {
+      // B tile loop covers B_IT * nthreads float4: needs (NT + 3) / 4 * waves * 64 >= 16 * NT * 4  <=>  waves >= 4  (tn_route)
+      const size_t lds = 2 * (size_t)(BK * pitch16(r.waves * 16) + BK * pitch_b(nt.value * 16) + BK) * sizeof(float);
+      k_gemm_tn<nt.value, aff.value><<<r.grid, r.waves * 64, lds, stream>>>(QAGNN_TN_ARGS, Pcs, p.b_rowidx, p.groups, r.chunk_rows);
+      QAGNN_LAUNCH_CHECK("k_gemm_tn");
+      return QAGNN_OK;
+    });
+  });
+}
+// compile-time strip (NT = 13 and 7 / 13 / 16 waves: every weight gradient of the stack at d = 200)
+int launch_tn_strip(const TnRoute& r, const TnProduct& p, float* Pcs, hipStream_t stream) {
+  return dispatch_int<7, 13, 16>(r.waves, [&](auto nw) {
+    return dispatch_bool(r.colsum, [&](auto cs) {
+      return dispatch_bool(r.affine, [&](auto aff) {
+        k_gemm_tn_strip<13, nw.value, aff.value, cs.value><<<r.grid, nw.value * 64, 0, stream>>>(QAGNN_TN_ARGS, r.chunk_rows, Pcs, p.b_rowidx, p.groups);
+        QAGNN_LAUNCH_CHECK("k_gemm_tn_strip");
+        return QAGNN_OK;
+      });
+    });
+  });
+}
+#undef QAGNN_TN_ARGS
+
+int launch_sum_chunks(const float* P, float* C, int ldc, int rows, int No, int nchunks, int accumulate, bool by4, hipStream_t stream) {
+  const int64_t tot = (int64_t)rows * No;
+  if (by4) k_sum_chunks4<<<cdiv(tot / 4, 64), SC_G * 64, 0, stream>>>(P, C, ldc, rows, No, nchunks, accumulate);
+  else k_sum_chunks<<<cdiv(tot, 256), 256, 0, stream>>>(P, C, ldc, rows, No, nchunks, accumulate);
+  QAGNN_LAUNCH_CHECK("k_sum_chunks");
   return QAGNN_OK;
-}
-
-// waves per block = 16-row output tiles per block: the count in [4, 16] that wastes the fewest rows of Ka (ties -> more waves)
-static int pick_tn_waves(int Ka) {
-  int best = 4, best_waste = INT32_MAX;
-  for (int nw = 16; nw >= 4; --nw) {
-    const int bm = nw * 16, waste = cdiv(Ka, bm) * bm - Ka;
-    if (waste < best_waste) { best_waste = waste; best = nw; }
-  }
-  return best;
-}
-
-template <int NT>
-static int launch_tn(const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No, const float* sc,
-                     const float* sh, const int64_t* ridx, int chunk_rows, float* Pcs, const int64_t* bidx, int groups,
-                     hipStream_t stream) {
-  const int nw = pick_tn_waves(Ka), bm = nw * 16, nchunks = cdiv(R, chunk_rows);
-  // B tile loop covers B_IT * nthreads float4: needs (NT + 3) / 4 * nw * 64 >= 16 * NT * 4  <=>  nw >= 4  (guaranteed)
-  dim3 grid(cdiv(No, NT * 16), cdiv(Ka, bm), nchunks);
-  const size_t lds = 2 * (size_t)(BK * pitch16(bm) + BK * pitch_b(NT * 16) + BK) * sizeof(float);
-  if (sc) k_gemm_tn<NT, true><<<grid, nw * 64, lds, stream>>>(A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, Pcs, bidx, groups, chunk_rows);
-  else k_gemm_tn<NT, false><<<grid, nw * 64, lds, stream>>>(A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, Pcs, bidx, groups, chunk_rows);
-  QAGNN_LAUNCH_CHECK("k_gemm_tn");
-  return QAGNN_OK;
-}
-
-static bool tn_strip_enabled() { return true; }  // (the run-time-shaped k_gemm_tn serves the widths the strip kernel is not compiled for)
-
-// compile-time strip launch (NT = 13 and 7 / 13 / 16 waves: every weight gradient of the stack at d = 200)
-template <int NWT>
-static void launch_tn_strip_i(dim3 grid, hipStream_t stream, const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No,
-                              const float* sc, const float* sh, const int64_t* ridx, int chunk_rows, float* Pcs, const int64_t* bidx,
-                              int groups) {
-#define QAGNN_STRIP_GO(AFF, CS) \
-  k_gemm_tn_strip<13, NWT, AFF, CS><<<grid, NWT * 64, 0, stream>>>(A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, chunk_rows, Pcs, bidx, groups)
-  if (Pcs) {
-    if (sc) QAGNN_STRIP_GO(true, true);
-    else QAGNN_STRIP_GO(false, true);
-  } else {
-    if (sc) QAGNN_STRIP_GO(true, false);
-    else QAGNN_STRIP_GO(false, false);
-  }
-#undef QAGNN_STRIP_GO
-}
-static bool tn_strip_ok(int Ka) { const int nw = pick_tn_waves(Ka); return nw == 7 || nw == 13 || nw == 16; }
-static int launch_tn_strip(const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No, const float* sc,
-                           const float* sh, const int64_t* ridx, int chunk_rows, float* Pcs, const int64_t* bidx, int groups,
-                           hipStream_t stream) {
-  const int nw = pick_tn_waves(Ka);
-  dim3 grid(cdiv(No, 13 * 16), cdiv(Ka, nw * 16), cdiv(R, chunk_rows));
-  if (nw == 7) launch_tn_strip_i<7>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, chunk_rows, Pcs, bidx, groups);
-  else if (nw == 13) launch_tn_strip_i<13>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, chunk_rows, Pcs, bidx, groups);
-  else launch_tn_strip_i<16>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, ridx, chunk_rows, Pcs, bidx, groups);
-  QAGNN_LAUNCH_CHECK("k_gemm_tn_strip");
-  return QAGNN_OK;
-}
-
-// Rows per split-K chunk.  Every chunk costs one Ka x No partial (written, then re-read by k_sum_chunks), so a launch whose
-// chunk already spans several blocks (column blocks x row blocks) takes longer chunks: just enough blocks to fill the CUs
-// once (twice for blocks of <= 8 waves).  Never below TN_RC, which is what qagnn_gemm_tn_workspace_elems() sizes for.
-static int pick_tn_chunk_rows(int R, int Ka, int No, int nt) {
-  const int lo = tn_min_chunk(R);
-  const int rb = pick_tn_waves(Ka), nw = rb;
-  const int blocks_per_chunk = cdiv(No, nt * 16) * cdiv(Ka, rb * 16);
-  const int target = (num_cus() * (nw <= 8 ? 2 : 1)) / blocks_per_chunk;
-  const int rows = (cdiv(R, target > 0 ? target : 1) + 15) & ~15;
-  return rows > lo ? rows : lo;
-}
-
-// column-tile count per block: the widest instantiation that divides No, else the one wasting the least
-static int pick_nt(int No) {
-  const int cands[5] = {13, 7, 8, 4, 2};
-  for (int c : cands)
-    if (No % (c * 16) == 0) return c;
-  int best = 4;
-  int64_t best_cost = INT64_MAX;
-  for (int c : cands) {
-    const int64_t cost = (int64_t)cdiv(No, c * 16) * c * 16;
-    if (cost < best_cost) { best_cost = cost; best = c; }
-  }
-  return best;
 }
 
 }  // namespace qagnn
-
-using namespace qagnn;
-
-extern "C" int qagnn_gemm_nn_f32(const qagnn_gemm_nn_args* a, qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TimedScope timed(0, stream);
-  QAGNN_REQUIRE(a && a->A1 && a->B1 && a->C, QAGNN_EINVAL, "gemm_nn: null pointer");
-  QAGNN_REQUIRE(a->M > 0 && a->No > 0 && a->K1 > 0, QAGNN_EINVAL, "gemm_nn: bad sizes M=%d No=%d K1=%d", a->M, a->No, a->K1);
-  QAGNN_REQUIRE(a->K1 % BK == 0 && a->K2 % BK == 0 && a->K2 >= 0, QAGNN_EINVAL, "gemm_nn: K1=%d K2=%d must be multiples of %d",
-                a->K1, a->K2, BK);
-  QAGNN_REQUIRE(a->No % 4 == 0, QAGNN_EINVAL, "gemm_nn: No=%d must be a multiple of 4", a->No);
-  QAGNN_REQUIRE(a->lda1 % 4 == 0 && a->ldb1 % 4 == 0 && aligned16(a->A1) && aligned16(a->B1), QAGNN_EINVAL,
-                "gemm_nn: operand 1 must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(a->K2 == 0 || (a->A2 && a->B2 && a->lda2 % 4 == 0 && a->ldb2 % 4 == 0 && aligned16(a->A2) && aligned16(a->B2)),
-                QAGNN_EINVAL, "gemm_nn: operand 2 must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a->rowtab || a->rowidx, QAGNN_EINVAL, "gemm_nn: rowtab without rowidx");
-  QAGNN_REQUIRE(a->ldc % 4 == 0 && aligned16(a->C) && (!a->bias || aligned16(a->bias)) &&
-                    (!a->rowtab || (aligned16(a->rowtab) && a->ldt % 4 == 0)),
-                QAGNN_EINVAL, "gemm_nn: C / bias / rowtab must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a->a_scale || (a->a_shift && aligned16(a->a_scale) && aligned16(a->a_shift)), QAGNN_EINVAL,
-                "gemm_nn: a_scale/a_shift must both be given and 16-byte aligned");
-  switch (pick_nt(a->No)) {
-    case 13: return launch_nn<13>(*a, stream);
-    case 8: return launch_nn<8>(*a, stream);
-    case 7: return launch_nn<7>(*a, stream);
-    case 4: return launch_nn<4>(*a, stream);
-    default: return launch_nn<2>(*a, stream);
-  }
-}
-
-extern "C" int64_t qagnn_gemm_tn_workspace_elems(int32_t R, int32_t Ka, int32_t No) {
-  return (int64_t)cdiv(R, R <= 4096 ? TN_RC_SPLIT_SMALL : tn_min_chunk(R)) * ((int64_t)Ka * No + 4 * (int64_t)No);
-}
-
-extern "C" int qagnn_gemm_tn_colsum_f32(const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, int32_t R,
-                                        int32_t Ka, int32_t No, const float* a_scale, const float* a_shift, const int64_t* a_rowidx,
-                                        int32_t accumulate, float* bsum, const int64_t* b_rowidx, int32_t groups, float* workspace,
-                                        qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TimedScope timed(1, stream);
-  QAGNN_REQUIRE(A && B && C && workspace, QAGNN_EINVAL, "gemm_tn: null pointer");
-  QAGNN_REQUIRE(R > 0 && Ka > 0 && No > 0 && Ka % 4 == 0 && No % 4 == 0, QAGNN_EINVAL,
-                "gemm_tn: bad sizes R=%d Ka=%d No=%d (Ka, No multiples of 4)", R, Ka, No);
-  QAGNN_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && aligned16(A) && aligned16(B), QAGNN_EINVAL,
-                "gemm_tn: operands must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a_scale || (a_shift && aligned16(a_scale) && aligned16(a_shift)), QAGNN_EINVAL,
-                "gemm_tn: a_scale/a_shift must both be given and 16-byte aligned");
-  QAGNN_REQUIRE(!bsum || (groups >= 1 && groups <= 4 && (groups == 1 || b_rowidx)), QAGNN_EINVAL, "gemm_tn: colsum groups=%d (1..4)", groups);
-  const int nt = pick_nt(No);
-  const bool split = !bsum && tn_split_ok(R, Ka, No, lda, ldb, a_rowidx != nullptr, a_scale != nullptr);
-  const bool strip = nt == 13 && tn_strip_enabled() && tn_strip_ok(Ka);
-  const int crows = split ? tn_split_chunk_rows(R, Ka, No, tn_split_min_chunk(R)) : pick_tn_chunk_rows(R, Ka, No, nt);
-  const int nchunks = cdiv(R, crows);
-  float* Pcs = bsum ? workspace + (int64_t)nchunks * Ka * No : nullptr;
-  int rc;
-  if (split) rc = launch_tn_split(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, stream);
-  else if (strip) rc = launch_tn_strip(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream);
-  else switch (nt) {
-    case 13: rc = launch_tn<13>(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream); break;
-    case 8: rc = launch_tn<8>(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream); break;
-    case 7: rc = launch_tn<7>(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream); break;
-    case 4: rc = launch_tn<4>(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream); break;
-    default: rc = launch_tn<2>(A, lda, B, ldb, workspace, R, Ka, No, a_scale, a_shift, a_rowidx, crows, Pcs, b_rowidx, groups, stream); break;
-  }
-  if (rc != QAGNN_OK) return rc;
-  const int64_t tot = (int64_t)Ka * No;
-  if (ldc % 4 == 0 && aligned16(C)) k_sum_chunks4<<<cdiv(tot / 4, 64), SC_G * 64, 0, stream>>>(workspace, C, ldc, Ka, No, nchunks, accumulate);
-  else k_sum_chunks<<<cdiv(tot, 256), 256, 0, stream>>>(workspace, C, ldc, Ka, No, nchunks, accumulate);
-  QAGNN_LAUNCH_CHECK("k_sum_chunks");
-  if (bsum) {
-    k_sum_chunks<<<cdiv((int64_t)groups * No, 256), 256, 0, stream>>>(Pcs, bsum, No, groups, No, nchunks, 0);
-    QAGNN_LAUNCH_CHECK("k_sum_chunks(colsum)");
-  }
-  return QAGNN_OK;
-}
-
-// C [Ka1 + Ka2, No] = [A1 | A2]^T B: the two weight gradients that share their B operand (X^T dK|dM|dQ and S^T dK|dM|dQ of a hop) as ONE
-// split-K launch and ONE chunk sum where the bf16-split kernel takes the shapes; otherwise two qagnn_gemm_tn_f32 calls.
-extern "C" int qagnn_gemm_tn2_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
-                                  int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, float* workspace, qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TimedScope timed(1, stream);
-  QAGNN_REQUIRE(A1 && A2 && B && C && workspace, QAGNN_EINVAL, "gemm_tn2: null pointer");
-  QAGNN_REQUIRE(R > 0 && Ka1 > 0 && Ka2 > 0 && No > 0 && Ka1 % 4 == 0 && Ka2 % 4 == 0 && No % 4 == 0, QAGNN_EINVAL,
-                "gemm_tn2: bad sizes R=%d Ka1=%d Ka2=%d No=%d (Ka, No multiples of 4)", R, Ka1, Ka2, No);
-  QAGNN_REQUIRE(lda1 % 4 == 0 && lda2 % 4 == 0 && ldb % 4 == 0 && aligned16(A1) && aligned16(A2) && aligned16(B), QAGNN_EINVAL,
-                "gemm_tn2: operands must be 16-byte aligned with pitches multiple of 4");
-  const bool merged = tn_split_ok(R, Ka1, No, lda1, ldb, false, false) && tn_split_ok(R, Ka2, No, lda2, ldb, false, false) && ldc % 4 == 0 &&
-                      aligned16(C);
-  if (!merged) {
-    int rc = qagnn_gemm_tn_f32(A1, lda1, B, ldb, C, ldc, R, Ka1, No, nullptr, nullptr, nullptr, 0, workspace, stream_);
-    if (rc != QAGNN_OK) return rc;
-    return qagnn_gemm_tn_f32(A2, lda2, B, ldb, C + (int64_t)Ka1 * ldc, ldc, R, Ka2, No, nullptr, nullptr, nullptr, 0, workspace, stream_);
-  }
-  const int crows = tn_split2_chunk_rows(R, Ka1, Ka2, No, tn_split_min_chunk(R));
-  const int nchunks = cdiv(R, crows), Ka = Ka1 + Ka2;
-  int rc = launch_tn_split2(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, workspace, R, No, crows, stream);
-  if (rc != QAGNN_OK) return rc;
-  const int64_t tot = (int64_t)Ka * No;
-  k_sum_chunks4<<<cdiv(tot / 4, 64), SC_G * 64, 0, stream>>>(workspace, C, ldc, Ka, No, nchunks, 0);
-  QAGNN_LAUNCH_CHECK("k_sum_chunks");
-  return QAGNN_OK;
-}
-
-extern "C" int qagnn_gemm_tn_f32(const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, int32_t R,
-                                 int32_t Ka, int32_t No, const float* a_scale, const float* a_shift, const int64_t* a_rowidx,
-                                 int32_t accumulate, float* workspace, qagnn_stream_t stream_) {
-  return qagnn_gemm_tn_colsum_f32(A, lda, B, ldb, C, ldc, R, Ka, No, a_scale, a_shift, a_rowidx, accumulate, nullptr, nullptr, 0,
-                                  workspace, stream_);
-}
-
-// The weight-gradient products in the three-MFMA form (scaled two-piece fp16 split: gemm_nn2.hip's header, gemm_split.hip's NP = 2 kernels).
-// Same chunking, same ordered chunk sum as the six-MFMA route; shapes the split kernels do not take fall back to it (amax unused).
-static int gemm_tn_scaled(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
-                          int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,
-                          const uint32_t* amax_a1, const uint32_t* amax_a2, const uint32_t* amax_b, float* workspace, int np,
-                          qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TimedScope timed(1, stream);
-  const bool two = A2 != nullptr && Ka2 > 0;
-  QAGNN_REQUIRE(A1 && B && C && workspace, QAGNN_EINVAL, "gemm_tn_h2: null pointer");
-  QAGNN_REQUIRE(!two || !a_scale, QAGNN_EINVAL, "gemm_tn_h2: the two-operand product has no BatchNorm prologue");
-  const bool have = amax_a1 && amax_b && (!two || amax_a2);
-  const bool ok = have && ldc % 4 == 0 && aligned16(C) && tn_split_ok(R, Ka1, No, lda1, ldb, false, a_scale != nullptr) &&
-                  (!two || tn_split_ok(R, Ka2, No, lda2, ldb, false, false));
-  if (!ok) {
-    if (two) return qagnn_gemm_tn2_f32(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, workspace, stream_);
-    return qagnn_gemm_tn_f32(A1, lda1, B, ldb, C, ldc, R, Ka1, No, a_scale, a_shift, nullptr, 0, workspace, stream_);
-  }
-  QAGNN_REQUIRE(R > 0 && Ka1 % 4 == 0 && No % 4 == 0 && (!two || Ka2 % 4 == 0), QAGNN_EINVAL, "gemm_tn_h2: bad sizes");
-  QAGNN_REQUIRE(lda1 % 4 == 0 && ldb % 4 == 0 && aligned16(A1) && aligned16(B) && (!two || (lda2 % 4 == 0 && aligned16(A2))), QAGNN_EINVAL,
-                "gemm_tn_h2: operands must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a_scale || (a_shift && aligned16(a_scale) && aligned16(a_shift)), QAGNN_EINVAL, "gemm_tn_h2: a_scale/a_shift must both be given");
-  const uint32_t* am[3] = {amax_a1, amax_a2, amax_b};
-  const int Ka = Ka1 + (two ? Ka2 : 0);
-  const int crows = two ? tn_split2_chunk_rows(R, Ka1, Ka2, No, tn_split_min_chunk(R)) : tn_split_chunk_rows(R, Ka1, No, tn_split_min_chunk(R));
-  const int nchunks = cdiv(R, crows);
-  int rc = two ? launch_tn_split2(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, workspace, R, No, crows, stream, am, np)
-               : launch_tn_split(A1, lda1, B, ldb, workspace, R, Ka1, No, a_scale, a_shift, nullptr, crows, stream, am, np);
-  if (rc != QAGNN_OK) return rc;
-  k_sum_chunks4<<<cdiv((int64_t)Ka * No / 4, 64), SC_G * 64, 0, stream>>>(workspace, C, ldc, Ka, No, nchunks, 0);
-  QAGNN_LAUNCH_CHECK("k_sum_chunks");
-  return QAGNN_OK;
-}
-
-extern "C" int qagnn_gemm_tn_h2_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
-                                    int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,
-                                    const uint32_t* amax_a1, const uint32_t* amax_a2, const uint32_t* amax_b, float* workspace,
-                                    qagnn_stream_t stream_) {
-  return gemm_tn_scaled(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, a_scale, a_shift, amax_a1, amax_a2, amax_b, workspace, 2, stream_);
-}
-
-// The reduced-precision form of the same products (ONE fp16 MFMA per product, operands rounded to fp16 under the same scales: see
-// qagnn_gemm_nn_args.pieces); on request only -- qagnn_hop_args.gemm_split == 3
-extern "C" int qagnn_gemm_tn_h1_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
-                                    int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,
-                                    const uint32_t* amax_a1, const uint32_t* amax_a2, const uint32_t* amax_b, float* workspace,
-                                    qagnn_stream_t stream_) {
-  return gemm_tn_scaled(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, a_scale, a_shift, amax_a1, amax_a2, amax_b, workspace, 1, stream_);
-}

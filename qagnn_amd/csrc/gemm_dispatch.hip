@@ -1,0 +1,348 @@
+// Host side of the dense products: what stands between the GEMM entry points of include/qagnn_hip.h and the kernels of gemm.hip (fp32
+// MFMA, weight gradients at run-time shapes, chunk sums), gemm_split.hip (3 x bf16 split, first generation; split weight gradients) and
+// gemm_nn2.hip (second-generation NN kernel, B images).  No kernel lives here.
+//
+// An entry point fills a product description (NnProduct / TnProduct, common.h) and calls gemm_nn() / gemm_tn(): validate, ask
+// nn_route() / tn_route() for the product's route, hand route and product to the one launcher of the kernel template it names.  The
+// route is the only place where a kernel family, a tile shape, an arithmetic form, a chunking or a scratch size is chosen; the
+// scratch queries below return what the route says, and hop.hip calls gemm_nn() / gemm_tn() like the entry points do.
+#include <stdlib.h>
+
+#include <atomic>
+#include <initializer_list>
+
+#include "common.h"
+
+namespace qagnn {
+
+// column-tile count per block: the widest instantiation that divides No, else the one wasting the least (k_gemm_nn, k_gemm_tn)
+static int pick_nt(int No) {
+  const int cands[5] = {13, 7, 8, 4, 2};
+  for (int c : cands)
+    if (No % (c * 16) == 0) return c;
+  int best = 4;
+  int64_t best_cost = INT64_MAX;
+  for (int c : cands) {
+    const int64_t cost = (int64_t)cdiv(No, c * 16) * c * 16;
+    if (cost < best_cost) { best_cost = cost; best = c; }
+  }
+  return best;
+}
+
+// ---- NN -----------------------------------------------------------------------------------------------------------------------------
+// One process-wide threshold (qagnn_packed_min_rows: tests lower it to run small products in the packed forms): from that many rows on
+// B is packed once per product wherever the caller hands over scratch, and the scaled fp16 forms pay (they need a packed image).
+static std::atomic<int64_t> g_pack_min_m{8192};
+bool nn_rows_packed(int64_t M) { return M >= g_pack_min_m.load(std::memory_order_relaxed); }
+
+// what the second-generation kernel takes: 32-bit operand offsets, segments that are multiples of 8
+static bool nn2_ok(const qagnn_gemm_nn_args& a, int ldn1, int ldn2) {
+  const int64_t lim = (int64_t)0x7FFFFFFF;
+  // (a gathered A1: the table's extent must be known and addressable with the kernels' 32-bit offsets; one segment)
+  if (a.a_rowidx && !(a.a_rows > 0 && a.a_rows * (int64_t)a.lda1 * 4 < lim && a.K2 == 0)) return false;
+  if (a.K1 % 8 != 0 || a.K2 % 8 != 0) return false;
+  if ((int64_t)a.M * a.lda1 * 4 >= lim || (int64_t)a.No * ldn1 * 4 >= lim || (int64_t)a.M * a.ldc * 4 >= lim) return false;
+  if (a.K2 > 0 && ((int64_t)a.M * a.lda2 * 4 >= lim || (int64_t)a.No * ldn2 * 4 >= lim)) return false;
+  if (a.K2 > 0 && (a.K1 & 31) != 0 && a.K2 < 32 - (a.K1 & 31)) return false;  // (the straddling tile must lie inside segment 2)
+  if (a.a_scale && a.K1 > 256) return false;  // (the scale / shift vectors live in LDS next to the two B images)
+  return true;
+}
+// The staggered 8-wave block wherever a six-MFMA product on an image has at least one 256-row tile per CU.  Measured at M = 64 000
+// (tools/nn2_ablate.hip, profiles/r4_run16_nn2_stagger.txt), 4-wave blocks -> staggered block: [208|112] -> 624 141 -> 122 us, 624 -> 208
+// 96..101 -> 79, but 208 -> 208 38 -> 39 and 624 -> 112 (NT = 7) 53 -> 54: with one block per CU nothing runs under a tile's first loads,
+// and the last tiles' stores are a tail at HBM speed, which 10 k-tiles of 13 column tiles amortise and 7 k-tiles or 7 column tiles do not.
+static bool nn2_staggered(int nt, const qagnn_gemm_nn_args& a) {
+  return nt >= 8 && nn2::walk_tiles(a.K1, a.K2) >= 10 && (int64_t)cdiv(a.No, nt * 16) * cdiv(a.M, 256) * 10 >= num_cus() * 9;
+}
+
+NnRoute nn_route(const NnProduct& p) {
+  const qagnn_gemm_nn_args& a = *p.a;
+  NnRoute r = {};
+  r.np = 3;
+  r.affine = a.a_scale != nullptr;
+  if (!p.split) {  // exact fp32 MFMA: persistent 8-wave blocks on 128-row tiles
+    r.family = NnFamily::FP32;
+    r.nt = pick_nt(a.No);
+    r.wv = 8;
+    nn_grid(r, a.M, a.No, 128, QAGNN_NN_OCC > 0 ? QAGNN_NN_OCC : 1);
+    return r;
+  }
+  const int nt16 = cdiv(a.No, 16);
+  r.nt = nt16 >= 13 ? 13 : nt16 >= 8 ? 8 : nt16 >= 7 ? 7 : nt16 >= 4 ? 4 : 2;
+  // Few row tiles (the host-bound configurations: 10 subgraphs are 16 row tiles, a 64-subgraph MedQA shard 100, on 256 CUs): a
+  // block's time is its own serial k-loop, which scales with the column tiles it carries, and the other CUs idle -- so the column
+  // tile narrows until there are about 1.5 blocks per CU (or it is 32 columns wide).  Measured, rocprofv3 kernel durations
+  // (profiles/r3_run5_nn_small_m.txt): 2 000 x 208 x 208 25.3 -> 9.4 us at 32 columns; 12 800 rows 27.3 -> 16.3 us at 64 columns
+  // (18.6 at 32); 624 -> 208 at 12 800 rows 63 -> 37 us.  The arithmetic per output element does not depend on the tile shape:
+  // results are bit-identical.
+  for (int c : {7, 4, 2})
+    if (cdiv(a.M, 128) * cdiv(a.No, r.nt * 16) < num_cus() * 3 / 2 && c < r.nt) r.nt = c;
+  r.wv = 4;
+  r.stats = a.colstat_part != nullptr;
+  if (!nn2_ok(a, p.ldn1, p.ldn2)) {  // first generation: 4-wave blocks on 128-row tiles, two per CU
+    const int64_t lim = (int64_t)0x7FFFFFFF;
+    r.family = NnFamily::SPLIT;
+    r.flat = a.a_rowidx || (int64_t)a.M * a.lda1 * 4 >= lim || (int64_t)a.M * a.lda2 * 4 >= lim || (int64_t)a.No * p.ldn1 * 4 >= lim ||
+             (int64_t)a.No * p.ldn2 * 4 >= lim;
+    nn_grid(r, a.M, a.No, 128, 2);
+    return r;
+  }
+  r.family = NnFamily::NN2;
+  // B in `np` pieces: a registered image (qagnn_gemm_nn_prepack_f32: one launch for all weights of a step), or one packed into the
+  // caller's scratch (the scaled forms pass a misaligned scratch by, the six-MFMA form reports it)
+  auto image = [&](int np) {
+    const int64_t need = nn2_pack_bytes(a.No, a.K1, a.K2, np);
+    if ((r.image = nn2_prepack_lookup(p.B1n, p.ldn1, a.K1, p.B2n, p.ldn2, a.K2, a.No, np))) r.b = NnB::IMAGE;
+    else if (p.ws && nn_rows_packed(a.M) && p.ws_bytes >= need && (np == 3 || aligned16(p.ws))) { r.b = NnB::PACK; r.ws_bytes = need; }
+    else return false;
+    r.np = np;
+    return true;
+  };
+  // the scaled forms where the operand maxima are known: three MFMAs per product, or one on request (pieces == 1: reduced precision);
+  // 4-wave blocks at every shape (tools/nn2_ablate.hip, profiles/r6_run1_three_product_ablation.txt)
+  const bool scaled = nn_rows_packed(a.M) && a.a_amax1 && (a.K2 == 0 || a.a_amax2);
+  if (!(scaled && image(a.pieces == 1 ? 1 : 2)) && !image(3)) r.b = NnB::IN_KERNEL;
+  if (r.b != NnB::IN_KERNEL && r.np == 3 && nn2_staggered(r.nt, a)) r.wv = 8;
+  nn_grid(r, a.M, a.No, r.wv * 32, r.wv == 8 ? 1 : 2);
+  return r;
+}
+
+static int nn_validate(const NnProduct& p) {
+  QAGNN_REQUIRE(p.a, QAGNN_EINVAL, "gemm_nn: null pointer");
+  const qagnn_gemm_nn_args& a = *p.a;
+  const float* B1 = p.split ? p.B1n : a.B1, *B2 = p.split ? p.B2n : a.B2;
+  const int ldb1 = p.split ? p.ldn1 : a.ldb1, ldb2 = p.split ? p.ldn2 : a.ldb2, km = p.split ? 4 : 16;  // (fp32 kernel: k-tiles of 16)
+  QAGNN_REQUIRE(a.A1 && B1 && a.C, QAGNN_EINVAL, "gemm_nn: null pointer");
+  QAGNN_REQUIRE(a.M > 0 && a.No > 0 && a.K1 > 0, QAGNN_EINVAL, "gemm_nn: bad sizes M=%d No=%d K1=%d", a.M, a.No, a.K1);
+  QAGNN_REQUIRE(a.K1 % km == 0 && a.K2 % km == 0 && a.K2 >= 0, QAGNN_EINVAL, "gemm_nn: K1=%d K2=%d must be multiples of %d", a.K1, a.K2, km);
+  QAGNN_REQUIRE(a.No % 4 == 0, QAGNN_EINVAL, "gemm_nn: No=%d must be a multiple of 4", a.No);
+  QAGNN_REQUIRE(a.lda1 % 4 == 0 && ldb1 % 4 == 0 && (!p.split || ldb1 >= a.K1) && aligned16(a.A1) && aligned16(B1), QAGNN_EINVAL,
+                "gemm_nn: operand 1 must be 16-byte aligned with pitches multiple of 4");
+  QAGNN_REQUIRE(a.K2 == 0 || (a.A2 && B2 && a.lda2 % 4 == 0 && ldb2 % 4 == 0 && (!p.split || ldb2 >= a.K2) && aligned16(a.A2) && aligned16(B2)),
+                QAGNN_EINVAL, "gemm_nn: operand 2 must be 16-byte aligned with pitches multiple of 4");
+  QAGNN_REQUIRE(!a.rowtab || a.rowidx, QAGNN_EINVAL, "gemm_nn: rowtab without rowidx");
+  QAGNN_REQUIRE(a.ldc % 4 == 0 && aligned16(a.C) && (!a.bias || aligned16(a.bias)) && (!a.rowtab || (aligned16(a.rowtab) && a.ldt % 4 == 0)),
+                QAGNN_EINVAL, "gemm_nn: C / bias / rowtab must be 16-byte aligned with pitches multiple of 4");
+  QAGNN_REQUIRE(!a.a_scale || (a.a_shift && aligned16(a.a_scale) && aligned16(a.a_shift)), QAGNN_EINVAL,
+                "gemm_nn: a_scale/a_shift must both be given and 16-byte aligned");
+  if (p.split && a.colstat_part) {
+    const int64_t lim = (int64_t)0x7FFFFFFF;
+    QAGNN_REQUIRE(cdiv(a.No, 16) == 13 && !a.a_scale && !a.a_rowidx && !a.rowtab && !a.accumulate && a.K2 == 0, QAGNN_EUNSUPPORTED,
+                  "gemm_nn: column statistics need 193..208 output columns and a bias-only epilogue (No=%d)", a.No);
+    QAGNN_REQUIRE((int64_t)a.M * a.lda1 * 4 < lim && (int64_t)a.No * ldb1 * 4 < lim, QAGNN_EUNSUPPORTED,
+                  "gemm_nn: column statistics with operands of 2 GB and more");
+  }
+  return QAGNN_OK;
+}
+
+int gemm_nn(const NnProduct& p, hipStream_t stream) {
+  TimedScope timed(0, stream);
+  if (int rc = nn_validate(p)) return rc;
+  const qagnn_gemm_nn_args& a = *p.a;
+  const NnRoute r = nn_route(p);
+  if (r.family == NnFamily::FP32) return launch_nn(r, a, stream);
+  if (r.family == NnFamily::SPLIT) return launch_nn_split(r, a, p.B1n, p.ldn1, p.B2n, p.ldn2, stream);
+  if (r.b == NnB::IN_KERNEL) return launch_nn2(r, a, p.B1n, p.ldn1, p.B2n, p.ldn2, stream);
+  if (r.b == NnB::PACK) {
+    QAGNN_REQUIRE(aligned16(p.ws), QAGNN_EINVAL, "gemm_nn: the pack workspace must be 16-byte aligned");
+    if (int rc = launch_pack_b(r.np, a, p.B1n, p.ldn1, p.B2n, p.ldn2, p.ws, stream)) return rc;
+  }
+  return launch_nn2(r, a, static_cast<const float*>(r.b == NnB::PACK ? p.ws : r.image), cdiv(a.No, 16), nullptr, 0, stream);
+}
+
+// ---- TN (weight gradients): split-K over row chunks, partials summed in order ------------------------------------------------------
+// Rows per chunk.  Every chunk costs one Ka x No partial (written, then re-read by the chunk sum), so a launch whose chunk already
+// spans several blocks takes longer chunks: just enough blocks for `per_cu` per CU; a multiple of the kernel's k-tile, never below `lo`.
+static int tn_chunk_rows(int R, int blocks_per_chunk, int per_cu, int ktile, int lo) {
+  const int target = num_cus() * per_cu / blocks_per_chunk;
+  const int rows = cdiv(cdiv(R, target > 0 ? target : 1), ktile) * ktile, lo_k = cdiv(lo, ktile) * ktile;
+  return rows > lo_k ? rows : lo_k;
+}
+// The shortest chunk: 256 rows (>= 1 block per CU for the 208 x 208 gradients at N = 64 000); for reductions over <= 4096 rows (class
+// tables; 10 subgraphs = 2 000 node rows) the k-loop of a chunk is serial and the chip idle: 64 rows, and ONE 32-row k-tile in the split
+// kernels (2 000 x 208 x 208: 126 blocks instead of 64, half the serial work each: profiles/r3_run18_small_batch_ab.txt).
+static int tn_min_chunk(int R, bool split) { return R > 4096 ? 256 : split ? 32 : 64; }
+// the scratch every route fits in (tn_route's chunks are never shorter than the shortest split chunk; up to 4 groups of column sums)
+static int64_t tn_ws_bound(int R, int Ka, int No) { return (int64_t)cdiv(R, tn_min_chunk(R, true)) * ((int64_t)Ka * No + 4 * (int64_t)No); }
+// chunks of that many 32-row k-tiles and more run k_gemm_tn_ws (one 8-wave block per CU leaves a block's first loads and its
+// partial-sum stores uncovered, which only a long chunk amortises).  Measured with 8 - 24 k-tiles per block (tools/tn_ablate.hip,
+// profiles/r4_run17_tn_ws.txt): 208 x 624 115 -> 126 us, 208 x 208 43 -> 57, 112 x 624 72 -> 74; at 36 per block 201 -> 171 us; at the
+// 2-tile chunks of a 10-subgraph batch 29 us against the 4-wave kernel's ~14 (profiles/r5_run5_tn_ws_min_tiles_ab_b10.txt)
+constexpr int TN_WS_MIN_TILES = 28;
+
+// waves per block = 16-row output tiles per block: the count in [4, 16] that wastes the fewest rows of Ka (ties -> more waves)
+static int pick_tn_waves(int Ka) {
+  int best = 4, best_waste = INT32_MAX;
+  for (int nw = 16; nw >= 4; --nw) {
+    const int bm = nw * 16, waste = cdiv(Ka, bm) * bm - Ka;
+    if (waste < best_waste) { best_waste = waste; best = nw; }
+  }
+  return best;
+}
+// What the bf16-split kernels take.  QAGNN_GEMM_SPLIT=0 pins the fp32-MFMA kernels of gemm.hip: the one numerically distinct fallback
+// (the module mirror reads the same variable for the NN products: qagnn_amd/_lib.py)
+static bool tn_split_ok(const TnProduct& p, int Ka, int lda) {
+  static const int mode = getenv("QAGNN_GEMM_SPLIT") ? atoi(getenv("QAGNN_GEMM_SPLIT")) : 1;
+  const bool gather = p.a_rowidx != nullptr;
+  const int64_t big = (int64_t)p.R * ((lda > p.ldb && !gather) ? lda : p.ldb) * 4;  // (a gathered A goes through flat loads)
+  if (gather && (Ka <= 112 || p.a_scale)) return false;
+  return mode != 0 && Ka >= 64 && p.No >= 104 && p.R >= 1024 && big < (int64_t)0x7FFFFFFF;  // 32-bit buffer offsets
+}
+
+TnRoute tn_route(const TnProduct& p) {
+  TnRoute r = {};
+  r.np = 3;
+  r.affine = p.a_scale != nullptr;
+  r.gather = p.a_rowidx != nullptr;
+  r.colsum = p.bsum != nullptr;
+  r.sum_by4 = p.ldc % 4 == 0 && aligned16(p.C);
+  // the two-operand product is ONE launch and ONE chunk sum where the split kernels take both halves, else two products
+  const bool split = !r.colsum && tn_split_ok(p, p.Ka1, p.lda1) && (!p.two || (r.sum_by4 && tn_split_ok(p, p.Ka2, p.lda2)));
+  const int lo = tn_min_chunk(p.R, split);
+  int row_blocks;
+  if (split) {
+    // the scaled fp16 forms (three MFMAs, or one) where every operand's maximum is known
+    if (r.sum_by4 && !r.gather && p.amax[0] && p.amax[2] && (!p.two || p.amax[1])) r.np = p.np;
+    r.kt = (p.two || p.Ka1 <= 112) ? 7 : 13;  // (KT, NT) = (7, 13): the wide B tile, else (13, 7); two operands: 112-row tiles over A1's
+    r.nt = 20 - r.kt;                         // columns, then over A2's
+    row_blocks = cdiv(p.Ka1, r.kt * 16) + (p.two ? cdiv(p.Ka2, r.kt * 16) : 0);
+    const int bpc = cdiv(p.No, r.nt * 16) * row_blocks;
+    r.chunk_rows = tn_chunk_rows(p.R, bpc, 2, 32, lo);
+    r.family = TnFamily::SPLIT;
+    // Long two-operand products run k_gemm_tn_ws, ONE 8-wave block per CU: chunks sized for one block per CU (28 chunks of 72 k-tiles at
+    // 64 000 rows instead of 56 of 36) halve the partial sums that are written and summed again
+    if (p.two) {
+      const int rows1 = tn_chunk_rows(p.R, bpc, 1, 32, lo);
+      if (rows1 >= 2 * TN_WS_MIN_TILES * 32) r.chunk_rows = rows1;
+      if (r.chunk_rows >= TN_WS_MIN_TILES * 32) r.family = TnFamily::WS;
+    }
+  } else if (p.two) {
+    r.family = TnFamily::PAIR;
+    return r;
+  } else {  // the strip kernel is compiled for NT = 13 and 7 / 13 / 16 waves; k_gemm_tn serves every other width
+    r.nt = pick_nt(p.No);
+    r.waves = pick_tn_waves(p.Ka1);
+    r.family = r.nt == 13 && (r.waves == 7 || r.waves == 13 || r.waves == 16) ? TnFamily::STRIP : TnFamily::RUNTIME;
+    row_blocks = cdiv(p.Ka1, r.waves * 16);
+    r.chunk_rows = tn_chunk_rows(p.R, cdiv(p.No, r.nt * 16) * row_blocks, r.waves <= 8 ? 2 : 1, 16, lo);
+  }
+  r.nchunks = cdiv(p.R, r.chunk_rows);
+  r.grid = dim3(cdiv(p.No, r.nt * 16), row_blocks, r.nchunks);
+  r.ws_elems = (int64_t)r.nchunks * ((int64_t)(p.Ka1 + p.Ka2) * p.No + (r.colsum ? (int64_t)p.groups * p.No : 0));
+  return r;
+}
+
+static int tn_validate(const TnProduct& p) {
+  QAGNN_REQUIRE(p.A1 && p.B && p.C && p.ws && (!p.two || p.A2), QAGNN_EINVAL, "gemm_tn: null pointer");
+  QAGNN_REQUIRE(p.R > 0 && p.Ka1 > 0 && p.No > 0 && p.Ka1 % 4 == 0 && p.No % 4 == 0 && (!p.two || (p.Ka2 > 0 && p.Ka2 % 4 == 0)), QAGNN_EINVAL,
+                "gemm_tn: bad sizes R=%d Ka1=%d Ka2=%d No=%d (Ka, No multiples of 4)", p.R, p.Ka1, p.Ka2, p.No);
+  QAGNN_REQUIRE(p.lda1 % 4 == 0 && p.ldb % 4 == 0 && aligned16(p.A1) && aligned16(p.B) && (!p.two || (p.lda2 % 4 == 0 && aligned16(p.A2))),
+                QAGNN_EINVAL, "gemm_tn: operands must be 16-byte aligned with pitches multiple of 4");
+  QAGNN_REQUIRE(!p.a_scale || (!p.two && p.a_shift && aligned16(p.a_scale) && aligned16(p.a_shift)), QAGNN_EINVAL,
+                "gemm_tn: a_scale/a_shift must both be given and 16-byte aligned (one-operand products only)");
+  QAGNN_REQUIRE(!p.bsum || (p.groups >= 1 && p.groups <= 4 && (p.groups == 1 || p.b_rowidx)), QAGNN_EINVAL, "gemm_tn: colsum groups=%d (1..4)",
+                p.groups);
+  return QAGNN_OK;
+}
+
+static int tn_run(const TnProduct& p, hipStream_t stream) {
+  if (int rc = tn_validate(p)) return rc;
+  const TnRoute r = tn_route(p);
+  if (r.family == TnFamily::PAIR) {  // in the six-MFMA form, whatever maxima are known
+    TnProduct q = p;
+    q.two = false; q.A2 = nullptr; q.lda2 = q.Ka2 = 0;
+    q.amax[0] = q.amax[1] = q.amax[2] = nullptr;
+    if (int rc = tn_run(q, stream)) return rc;
+    q.A1 = p.A2; q.lda1 = p.lda2; q.Ka1 = p.Ka2; q.C = p.C + (int64_t)p.Ka1 * p.ldc;
+    return tn_run(q, stream);
+  }
+  const int Ka = p.Ka1 + p.Ka2;
+  QAGNN_REQUIRE(r.ws_elems <= tn_ws_bound(p.R, Ka, p.No), QAGNN_EINVAL, "gemm_tn: the route outgrows qagnn_gemm_tn_workspace_elems()");
+  float* Pcs = r.colsum ? p.ws + (int64_t)r.nchunks * Ka * p.No : nullptr;
+  const int rc = r.family == TnFamily::WS      ? launch_tn_ws(r, p, stream)
+                 : r.family == TnFamily::SPLIT ? launch_tn_split(r, p, stream)
+                 : r.family == TnFamily::STRIP ? launch_tn_strip(r, p, Pcs, stream)
+                                               : launch_tn(r, p, Pcs, stream);
+  if (rc != QAGNN_OK) return rc;
+  if (int rc2 = launch_sum_chunks(p.ws, p.C, p.ldc, Ka, p.No, r.nchunks, p.accumulate, r.sum_by4, stream)) return rc2;
+  return r.colsum ? launch_sum_chunks(Pcs, p.bsum, p.No, p.groups, p.No, r.nchunks, 0, false, stream) : QAGNN_OK;
+}
+
+int gemm_tn(const TnProduct& p, hipStream_t stream) {
+  TimedScope timed(1, stream);
+  return tn_run(p, stream);
+}
+
+}  // namespace qagnn
+
+using namespace qagnn;
+
+// ---- the C ABI: each entry point fills a product description ------------------------------------------------------------------------
+extern "C" int64_t qagnn_packed_min_rows(int64_t rows) { return rows < 0 ? g_pack_min_m.load() : g_pack_min_m.exchange(rows > 1 ? rows : 1); }
+
+extern "C" int64_t qagnn_gemm_nn_pack_bytes(int32_t No, int32_t K1, int32_t K2) { return nn2_pack_bytes(No, K1, K2, 3) + 256; }  // (>= the two-piece image + its scale words)
+
+extern "C" int64_t qagnn_gemm_nn_ws_bytes(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2) {
+  alignas(16) static char any_ws;  // what the route packs when the scratch is there and large enough
+  return a && B1n ? nn_route(NnProduct{a, true, B1n, ldn1, B2n, ldn2, &any_ws, INT64_MAX}).ws_bytes : 0;
+}
+
+extern "C" int qagnn_gemm_nn_f32(const qagnn_gemm_nn_args* a, qagnn_stream_t stream) {
+  return gemm_nn(NnProduct{a, false, nullptr, 0, nullptr, 0, nullptr, 0}, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_nn_split_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
+                                       qagnn_stream_t stream) {
+  return gemm_nn(NnProduct{a, true, B1n, ldn1, B2n, ldn2, nullptr, 0}, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_nn_split_ws_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
+                                          void* ws, int64_t ws_bytes, qagnn_stream_t stream) {
+  return gemm_nn(NnProduct{a, true, B1n, ldn1, B2n, ldn2, ws, ws_bytes}, (hipStream_t)stream);
+}
+
+extern "C" int64_t qagnn_gemm_tn_workspace_elems(int32_t R, int32_t Ka, int32_t No) { return tn_ws_bound(R, Ka, No); }
+
+extern "C" int qagnn_gemm_tn_colsum_f32(const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, int32_t R,
+                                        int32_t Ka, int32_t No, const float* a_scale, const float* a_shift, const int64_t* a_rowidx,
+                                        int32_t accumulate, float* bsum, const int64_t* b_rowidx, int32_t groups, float* workspace,
+                                        qagnn_stream_t stream) {
+  TnProduct p = tn_product(A, lda, Ka, nullptr, 0, 0, B, ldb, C, ldc, R, No, a_scale, a_shift, workspace);
+  p.a_rowidx = a_rowidx; p.accumulate = accumulate; p.bsum = bsum; p.b_rowidx = b_rowidx; p.groups = groups;
+  return gemm_tn(p, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_tn_f32(const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc, int32_t R,
+                                 int32_t Ka, int32_t No, const float* a_scale, const float* a_shift, const int64_t* a_rowidx,
+                                 int32_t accumulate, float* workspace, qagnn_stream_t stream) {
+  TnProduct p = tn_product(A, lda, Ka, nullptr, 0, 0, B, ldb, C, ldc, R, No, a_scale, a_shift, workspace);
+  p.a_rowidx = a_rowidx; p.accumulate = accumulate;
+  return gemm_tn(p, (hipStream_t)stream);
+}
+
+// C [Ka1 + Ka2, No] = [A1 | A2]^T B: the two weight gradients that share their B operand (X^T dK|dM|dQ and S^T dK|dM|dQ of a hop)
+extern "C" int qagnn_gemm_tn2_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
+                                  int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, float* workspace, qagnn_stream_t stream) {
+  TnProduct p = tn_product(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, nullptr, nullptr, workspace);
+  p.two = true;
+  return gemm_tn(p, (hipStream_t)stream);
+}
+
+// The same products in the scaled fp16 forms (gemm_nn2.hip's header): _h2 three MFMAs per product, _h1 ONE (reduced precision: operands
+// rounded to fp16 under the same scales; on request only -- qagnn_hop_args.gemm_split == 3).  A2 == nullptr / Ka2 == 0: one operand.
+// Shapes the split kernels do not take, or a missing maximum, fall back to the six-MFMA route.
+extern "C" int qagnn_gemm_tn_h2_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
+                                    int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,
+                                    const uint32_t* amax_a1, const uint32_t* amax_a2, const uint32_t* amax_b, float* workspace,
+                                    qagnn_stream_t stream) {
+  return gemm_tn(tn_product(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, a_scale, a_shift, workspace, amax_a1, amax_a2, amax_b, 2),
+                 (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_tn_h1_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
+                                    int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,
+                                    const uint32_t* amax_a1, const uint32_t* amax_a2, const uint32_t* amax_b, float* workspace,
+                                    qagnn_stream_t stream) {
+  return gemm_tn(tn_product(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, a_scale, a_shift, workspace, amax_a1, amax_a2, amax_b, 1),
+                 (hipStream_t)stream);
+}

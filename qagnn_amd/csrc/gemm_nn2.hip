@@ -47,7 +47,6 @@
 // 16-byte stores; bias / row table / accumulate / BatchNorm column statistics).
 #include <stdlib.h>
 
-#include <atomic>
 
 #include "common.h"
 
@@ -703,45 +702,15 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #undef QAGNN_NN2_SIX
 #undef QAGNN_NN2_SIX_T
 
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
-
+// PACKED: B1n = the packed buffer, ldn1 = its column tiles per k-tile.  WV = 8: the staggered 256-row block, one per CU.
 template <int NT, bool AFFINE, bool STATS, int NP, bool PACKED, int WV>
-static int launch_i(const qagnn_gemm_nn_args& b, const float* B1n, int ldn1, const float* B2n, int ldn2, int grid, int ntiles, hipStream_t stream) {
+static int launch_i(const NnRoute& r, const qagnn_gemm_nn_args& b, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
   const size_t lds = nn2_lds_bytes<NT, STATS, WV, NP>(AFFINE ? 2 * ((b.K1 + 31) & ~31) * 4 : 0);
   constexpr int lds_max = nn2_lds_bytes<NT, STATS, WV, NP>(AFFINE ? 2 * 256 * 4 : 0);  // (nn2_ok: K1 <= 256 with a scale / shift)
-  static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (lds_max > 64 * 1024 && !raised[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm_nn2<NT, AFFINE, STATS, NP, PACKED, WV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e != hipSuccess) { set_error("gemm_nn2: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e)); return QAGNN_EHIP; }
-    raised[dev & 63] = true;
-  }
-  k_gemm_nn2<NT, AFFINE, STATS, NP, PACKED, WV><<<grid, WV * 64, lds, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
+  if (int rc = raise_lds_limit<k_gemm_nn2<NT, AFFINE, STATS, NP, PACKED, WV>>(lds_max, "k_gemm_nn2")) return rc;
+  k_gemm_nn2<NT, AFFINE, STATS, NP, PACKED, WV><<<r.grid, WV * 64, lds, stream>>>(b, B1n, ldn1, B2n, ldn2, r.ntiles);
   QAGNN_LAUNCH_CHECK("k_gemm_nn2");
   return QAGNN_OK;
-}
-
-// PACKED: B1n = the packed buffer, ldn1 = its column tiles per k-tile.  WV = 8: the staggered 256-row block, one per CU.
-template <int NT, int NP, bool PACKED = false, int WV = 4>
-static int launch_nt(const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
-  qagnn_gemm_nn_args b = a;
-  b.xcd_remap = 1;
-  const int ntiles = cdiv(a.No, NT * 16) * cdiv(a.M, WV * 32);
-  const int cap = (num_cus() * (WV == 8 ? 1 : 2)) & ~7;
-  const int grid = ntiles < cap ? ntiles : cap;
-  if constexpr (NT == 13 || NT == 7 || NT == 4 || NT == 2) {
-    if (a.colstat_part) return launch_i<NT, false, true, NP, PACKED, WV>(b, B1n, ldn1, B2n, ldn2, grid, ntiles, stream);
-  }
-  if (a.a_scale) return launch_i<NT, true, false, NP, PACKED, WV>(b, B1n, ldn1, B2n, ldn2, grid, ntiles, stream);
-  return launch_i<NT, false, false, NP, PACKED, WV>(b, B1n, ldn1, B2n, ldn2, grid, ntiles, stream);
 }
 
 // B [No][K1] | [No][K2] (k contiguous) -> the packed image of PACKED kernels: block ((it * NJ + j) * 3 + p) of 1 KB holds, for lane
@@ -831,7 +800,7 @@ __global__ __launch_bounds__(256) void k_pack_b_multi(PackArgs a, unsigned char*
   else pack_b_wave<3>(d.B1n, d.ldn1, d.K1, d.B2n, d.ldn2, d.K2, d.No, d.NJ, d.nkt, it, j, out + d.out_off);
 }
 
-static int walk_tiles(int K1, int K2) {
+int walk_tiles(int K1, int K2) {
   const int r1 = K2 > 0 ? (K1 & 31) : 0;
   const int mixi = r1 != 0 ? 1 : 0;
   const int n1 = mixi ? (K1 >> 5) : ((K1 + 31) >> 5);
@@ -842,93 +811,44 @@ static int walk_tiles(int K1, int K2) {
 
 }  // namespace nn2
 
-// Which form a product takes (the A/B runs of the forms against each other: profiles/r4_run16_nn2_stagger.txt, r4_run28_round4_switches_ab.txt):
-// B packed once per product (k_pack_b) wherever the caller hands over a workspace and the product has at least nn2_pack_min_m() rows, the
-// in-kernel split otherwise; the staggered 8-wave block wherever a packed product has at least one 256-row tile per CU.
-// The threshold is one process-wide value (qagnn_packed_min_rows: tests lower it to run small products in the packed forms).
-static std::atomic<int64_t> g_pack_min_m{8192};
-int64_t nn2_pack_min_m() { return g_pack_min_m.load(std::memory_order_relaxed); }
-bool nn2_packed_ok(const qagnn_gemm_nn_args& a, int64_t ws_bytes, int np) { return a.M >= nn2_pack_min_m() && ws_bytes >= nn2_pack_bytes(a.No, a.K1, a.K2, np); }
-// Measured at M = 64 000 (tools/nn2_ablate.hip, profiles/r4_run16_nn2_stagger.txt), 4-wave blocks -> staggered block:
-// [208|112] -> 624 141 -> 122 us, 624 -> 208 96..101 -> 79, but 208 -> 208 38 -> 39 and 624 -> 112 (NT = 7) 53 -> 54: with one block per
-// CU nothing runs under a tile's first loads, and the last tiles' stores are a tail at HBM speed, which 10 k-tiles of 13 column tiles
-// amortise and 7 k-tiles or 7 column tiles do not.
-static bool nn2_staggered(int nt, const qagnn_gemm_nn_args& a) {
-  return nt >= 8 && nn2::walk_tiles(a.K1, a.K2) >= 10 && (int64_t)cdiv(a.No, nt * 16) * cdiv(a.M, 256) * 10 >= nn2::num_cus() * 9;
-}
-// the PACKED kernel on an image `p` of B (NJ column tiles per k-tile)
-static int launch_nn2_image(int nt, const qagnn_gemm_nn_args& a, const float* p, int NJ, hipStream_t stream, int np = 3) {
-  if (np == 1) {  // the one-MFMA reduced-precision form (qagnn_gemm_nn_args.pieces = 1)
-    switch (nt) {
-      case 13: return nn2::launch_nt<13, 1, true>(a, p, NJ, nullptr, 0, stream);
-      case 8: return nn2::launch_nt<8, 1, true>(a, p, NJ, nullptr, 0, stream);
-      case 7: return nn2::launch_nt<7, 1, true>(a, p, NJ, nullptr, 0, stream);
-      case 4: return nn2::launch_nt<4, 1, true>(a, p, NJ, nullptr, 0, stream);
-      default: return nn2::launch_nt<2, 1, true>(a, p, NJ, nullptr, 0, stream);
-    }
-  }
-  if (np == 2) {  // the two-piece fp16 form: 4-wave blocks at every shape (tools/nn2_ablate.hip, profiles/r6_run1_three_product_ablation.txt)
-    switch (nt) {
-      case 13: return nn2::launch_nt<13, 2, true>(a, p, NJ, nullptr, 0, stream);
-      case 8: return nn2::launch_nt<8, 2, true>(a, p, NJ, nullptr, 0, stream);
-      case 7: return nn2::launch_nt<7, 2, true>(a, p, NJ, nullptr, 0, stream);
-      case 4: return nn2::launch_nt<4, 2, true>(a, p, NJ, nullptr, 0, stream);
-      default: return nn2::launch_nt<2, 2, true>(a, p, NJ, nullptr, 0, stream);
-    }
-  }
-  if (nn2_staggered(nt, a)) {
-    if (nt == 13) return nn2::launch_nt<13, 3, true, 8>(a, p, NJ, nullptr, 0, stream);
-    return nn2::launch_nt<8, 3, true, 8>(a, p, NJ, nullptr, 0, stream);
-  }
-  switch (nt) {
-    case 13: return nn2::launch_nt<13, 3, true>(a, p, NJ, nullptr, 0, stream);
-    case 8: return nn2::launch_nt<8, 3, true>(a, p, NJ, nullptr, 0, stream);
-    case 7: return nn2::launch_nt<7, 3, true>(a, p, NJ, nullptr, 0, stream);
-    case 4: return nn2::launch_nt<4, 3, true>(a, p, NJ, nullptr, 0, stream);
-    default: return nn2::launch_nt<2, 3, true>(a, p, NJ, nullptr, 0, stream);
-  }
-}
-
-// what the second-generation kernel takes: no fused row gather, 32-bit operand offsets, segments that are multiples of 8
-bool nn2_ok(const qagnn_gemm_nn_args& a, int ldn1, int ldn2) {
-  const int64_t lim = (int64_t)0x7FFFFFFF;
-  // (a gathered A1: the table's extent must be known and addressable with the kernels' 32-bit offsets; one segment)
-  if (a.a_rowidx && !(a.a_rows > 0 && a.a_rows * (int64_t)a.lda1 * 4 < lim && a.K2 == 0)) return false;
-  if (a.K1 % 8 != 0 || a.K2 % 8 != 0) return false;
-  if ((int64_t)a.M * a.lda1 * 4 >= lim || (int64_t)a.No * ldn1 * 4 >= lim || (int64_t)a.M * a.ldc * 4 >= lim) return false;
-  if (a.K2 > 0 && ((int64_t)a.M * a.lda2 * 4 >= lim || (int64_t)a.No * ldn2 * 4 >= lim)) return false;
-  if (a.K2 > 0 && (a.K1 & 31) != 0 && a.K2 < 32 - (a.K1 & 31)) return false;  // (the straddling tile must lie inside segment 2)
-  if (a.a_scale && a.K1 > 256) return false;  // (the scale / shift vectors live in LDS next to the two B images)
-  return true;
-}
-
-int launch_nn2(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
-  switch (nt) {
-    case 13: return nn2::launch_nt<13, 3>(a, B1n, ldn1, B2n, ldn2, stream);
-    case 8: return nn2::launch_nt<8, 3>(a, B1n, ldn1, B2n, ldn2, stream);
-    case 7: return nn2::launch_nt<7, 3>(a, B1n, ldn1, B2n, ldn2, stream);
-    case 4: return nn2::launch_nt<4, 3>(a, B1n, ldn1, B2n, ldn2, stream);
-    default: return nn2::launch_nt<2, 3>(a, B1n, ldn1, B2n, ldn2, stream);
-  }
+// The shapes the kernel is built in: the in-kernel split (six MFMAs, 4 waves); on an image of B every arithmetic form with 4 waves, and
+// for six MFMAs with NT = 13 / 8 the staggered 8-wave block.  Which of them a product takes: nn_route (gemm_dispatch.hip).
+int launch_nn2(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
+  qagnn_gemm_nn_args b = a;
+  b.xcd_remap = 1;
+  const int shape = r.b == NnB::IN_KERNEL ? 0 : r.wv == 8 ? 4 : r.np;  // 0 | 1, 2, 3 = pieces of an image | 4 = staggered
+  return dispatch_int<13, 8, 7, 4, 2>(r.nt, [&](auto nt) {
+    return dispatch_int<0, 1, 2, 3, 4>(shape, [&](auto sh) {
+      constexpr int NT = nt.value, NP = (sh.value == 0 || sh.value == 4) ? 3 : sh.value, WV = sh.value == 4 ? 8 : 4;
+      constexpr bool PACKED = sh.value != 0;
+      if constexpr (WV == 8 && NT != 13 && NT != 8) {
+        set_error("k_gemm_nn2: no staggered block with %d column tiles", NT);
+        return QAGNN_EUNSUPPORTED;
+      } else {
+        if constexpr (NT != 8) {
+          if (r.stats) return nn2::launch_i<NT, false, true, NP, PACKED, WV>(r, b, B1n, ldn1, B2n, ldn2, stream);
+        }
+        return dispatch_bool(r.affine, [&](auto aff) { return nn2::launch_i<NT, aff.value, false, NP, PACKED, WV>(r, b, B1n, ldn1, B2n, ldn2, stream); });
+      }
+    });
+  });
 }
 
 // bytes of the packed image of B for one product (13 column tiles of slack: the last column block of a k-tile reads its full width);
-// np == 2: + one exponent word per column tile (13 more of slack for the same reason), rounded up to 16 bytes
+// np <= 2: + one exponent word per column tile (13 more of slack for the same reason), rounded up to 16 bytes
 int64_t nn2_pack_bytes(int No, int K1, int K2, int np) {
   const int64_t img = ((int64_t)nn2::walk_tiles(K1, K2) * cdiv(No, 16) + 13) * (np * 1024);
   return np <= 2 ? img + (((int64_t)cdiv(No, 16) + 13) * 4 + 15) / 16 * 16 : img;
 }
-// (h2_ok: what the two-piece form additionally asks of a product -- a known maximum of A and a finite-size image)
-bool nn2_h2_ok(const qagnn_gemm_nn_args& a) { return a.a_amax1 != nullptr && (a.K2 == 0 || a.a_amax2 != nullptr) && a.M >= nn2_pack_min_m(); }
 
-// pack B into `ws` (>= nn2_pack_bytes), then the PACKED kernel: two launches
-int launch_nn2_packed(int nt, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream, int np) {
+// B -> its image in `ws` (>= nn2_pack_bytes)
+int launch_pack_b(int np, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream) {
   const int NJ = cdiv(a.No, 16), nkt = nn2::walk_tiles(a.K1, a.K2);
-  if (np == 2) nn2::k_pack_b<2><<<dim3(cdiv(NJ, 4), nkt), 256, 0, stream>>>(B1n, ldn1, a.K1, B2n, ldn2, a.K2, a.No, NJ, nkt, reinterpret_cast<unsigned char*>(ws));
-  else if (np == 1) nn2::k_pack_b<1><<<dim3(cdiv(NJ, 4), nkt), 256, 0, stream>>>(B1n, ldn1, a.K1, B2n, ldn2, a.K2, a.No, NJ, nkt, reinterpret_cast<unsigned char*>(ws));
-  else nn2::k_pack_b<3><<<dim3(cdiv(NJ, 4), nkt), 256, 0, stream>>>(B1n, ldn1, a.K1, B2n, ldn2, a.K2, a.No, NJ, nkt, reinterpret_cast<unsigned char*>(ws));
-  QAGNN_LAUNCH_CHECK("k_pack_b");
-  return launch_nn2_image(nt, a, reinterpret_cast<const float*>(ws), NJ, stream, np);
+  return dispatch_int<3, 2, 1>(np, [&](auto p) {
+    nn2::k_pack_b<p.value><<<dim3(cdiv(NJ, 4), nkt), 256, 0, stream>>>(B1n, ldn1, a.K1, B2n, ldn2, a.K2, a.No, NJ, nkt, reinterpret_cast<unsigned char*>(ws));
+    QAGNN_LAUNCH_CHECK("k_pack_b");
+    return QAGNN_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -961,16 +881,9 @@ static bool prepack_takes(const qagnn_pack_desc& d) {
   return true;
 }
 
-int launch_nn2_prepacked(int nt, const qagnn_gemm_nn_args& a, const void* pk, hipStream_t stream, int np) {
-  return launch_nn2_image(nt, a, reinterpret_cast<const float*>(pk), cdiv(a.No, 16), stream, np);
-}
 }  // namespace qagnn
 
 using namespace qagnn;
-
-extern "C" int64_t qagnn_packed_min_rows(int64_t rows) {
-  return rows < 0 ? g_pack_min_m.load() : g_pack_min_m.exchange(rows > 1 ? rows : 1);
-}
 
 extern "C" int64_t qagnn_gemm_nn_prepack_bytes(const qagnn_pack_desc* d, int32_t n) {
   int64_t tot = 0;

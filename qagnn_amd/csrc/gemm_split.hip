@@ -329,41 +329,26 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   }
 }
 
-static int split_num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
-
-template <int NT>
-static int launch_split(const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
+int launch_nn_split(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
   qagnn_gemm_nn_args b = a;
   b.xcd_remap = 1;
-  const int ntiles = cdiv(a.No, NT * 16) * cdiv(a.M, SBM);
-  const int cap = (split_num_cus() * 2) & ~7;
-  const int grid = ntiles < cap ? ntiles : cap;
-  const int64_t lim = (int64_t)0x7FFFFFFF;
-  const bool flat = a.a_rowidx || (int64_t)a.M * a.lda1 * 4 >= lim || (int64_t)a.M * a.lda2 * 4 >= lim ||
-                    (int64_t)a.No * ldn1 * 4 >= lim || (int64_t)a.No * ldn2 * 4 >= lim;
-  if constexpr (NT == 13 || NT == 7 || NT == 4 || NT == 2) {
-    if (a.colstat_part) {  // (validated by the entry point: bias-only epilogue, no gather, 32-bit offsets)
-      k_gemm_nn_split<NT, false, false, true><<<grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
-      QAGNN_LAUNCH_CHECK("k_gemm_nn_split<stats>");
-      return QAGNN_OK;
+  return dispatch_int<13, 8, 7, 4, 2>(r.nt, [&](auto nt) {
+    constexpr int NT = nt.value;
+    if constexpr (NT != 8) {  // (column statistics: 193..208 output columns, bias-only epilogue, no gather, 32-bit offsets -- nn_route)
+      if (r.stats) {
+        k_gemm_nn_split<NT, false, false, true><<<r.grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, r.ntiles);
+        QAGNN_LAUNCH_CHECK("k_gemm_nn_split<stats>");
+        return QAGNN_OK;
+      }
     }
-  }
-  if (flat) {
-    if (a.a_scale) k_gemm_nn_split<NT, true, true><<<grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
-    else k_gemm_nn_split<NT, false, true><<<grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
-  } else {
-    if (a.a_scale) k_gemm_nn_split<NT, true, false><<<grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
-    else k_gemm_nn_split<NT, false, false><<<grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, ntiles);
-  }
-  QAGNN_LAUNCH_CHECK("k_gemm_nn_split");
-  return QAGNN_OK;
+    return dispatch_bool(r.flat, [&](auto flat) {
+      return dispatch_bool(r.affine, [&](auto aff) {
+        k_gemm_nn_split<NT, aff.value, flat.value><<<r.grid, STHR, 0, stream>>>(b, B1n, ldn1, B2n, ldn2, r.ntiles);
+        QAGNN_LAUNCH_CHECK("k_gemm_nn_split");
+        return QAGNN_OK;
+      });
+    });
+  });
 }
 
 
@@ -653,7 +638,6 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 //   * one barrier per k-tile.  The roles are taken by arrival order on each SIMD (HW_ID), so that every SIMD holds one wave of each
 //     kind: the matrix pipe sees an MFMA stream, the vector ALU the split arithmetic, at the same time.
 // ------------------------------------------------------------------------------------------------------------
-static bool tn_xcd() { return true; }  // the blocks of one split-K chunk on one XCD (-2..5 % per kernel: profiles/r4_run17_tn_ws.txt)
 constexpr int WTHR = 512;
 // QAGNN_TNW_ABL (tools/tn_ablate.hip only; numerically wrong, timing only): bit 0 the producers do not split / store, bit 1 the producers
 // do not load, bit 2 the compute waves issue no MFMAs, bit 3 no fragment reads either, bit 4 the producers wait for their loads and drop them
@@ -997,223 +981,45 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   }
 }
 
+// ---- launchers (the route: gemm_dispatch.hip).  chunk_rows > 0: the blocks of one split-K chunk on one XCD (-2..5 % per kernel:
+// profiles/r4_run17_tn_ws.txt) -------------------------------------------------------------------------------------------------------
+#define QAGNN_TN_ARGS p.A1, p.lda1, p.B, p.ldb, p.ws, p.R, p.Ka1, p.No, p.a_scale, p.a_shift, r.chunk_rows
+static TnAmax tn_amax(const TnRoute& r, const TnProduct& p) {
+  return r.np == 3 ? TnAmax{nullptr, nullptr, nullptr} : TnAmax{p.amax[0], p.two ? p.amax[1] : nullptr, p.amax[2]};
+}
 template <int KT, int NT, bool AFFINE, int NP = 3>
-static int launch_tn_ws_i(dim3 grid, hipStream_t stream, const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No,
-                          const float* sc, const float* sh, int chunk_rows, const float* A2 = nullptr, int lda2 = 0, int Ka2 = 0,
-                          TnAmax amax = TnAmax{nullptr, nullptr, nullptr}) {
-  constexpr size_t lds = (size_t)2 * NP * (KT * 16 + NT * 16) * TCP * sizeof(uint16_t) + 64;
-  static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (!raised[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm_tn_ws<KT, NT, AFFINE, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("gemm_tn_ws: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e)); return QAGNN_EHIP; }
-    raised[dev & 63] = true;
-  }
-  k_gemm_tn_ws<KT, NT, AFFINE, NP><<<grid, WTHR, lds, stream>>>(A, lda, B, ldb, P, R, Ka, No, sc, sh, tn_xcd() ? chunk_rows : -chunk_rows, A2, lda2, Ka2, amax);
+static int launch_tn_ws_i(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
+  constexpr int lds = 2 * NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t) + 64;
+  if (int rc = raise_lds_limit<k_gemm_tn_ws<KT, NT, AFFINE, NP>>(lds, "k_gemm_tn_ws")) return rc;
+  k_gemm_tn_ws<KT, NT, AFFINE, NP><<<r.grid, WTHR, lds, stream>>>(QAGNN_TN_ARGS, p.A2, p.lda2, p.Ka2, tn_amax(r, p));
   QAGNN_LAUNCH_CHECK("k_gemm_tn_ws");
   return QAGNN_OK;
 }
-
 template <int KT, int NT, bool AFFINE, bool GATHER = false, int NP = 3>
-static int launch_tn_split_i(dim3 grid, hipStream_t stream, const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No,
-                             const float* sc, const float* sh, int chunk_rows, const int64_t* ridx = nullptr, const float* A2 = nullptr,
-                             int lda2 = 0, int Ka2 = 0, TnAmax amax = TnAmax{nullptr, nullptr, nullptr}) {
-  constexpr size_t lds = (size_t)NP * (KT * 16 + NT * 16) * TCP * sizeof(uint16_t);
-  static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (lds > 64 * 1024 && !raised[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("gemm_tn_split: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e)); return QAGNN_EHIP; }
-    raised[dev & 63] = true;
-  }
-  k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP><<<grid, TTHR, lds, stream>>>(A, lda, B, ldb, P, R, Ka, No, sc, sh, tn_xcd() ? chunk_rows : -chunk_rows, ridx,
-                                                                           A2, lda2, Ka2, amax);
+static int launch_tn_split_i(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
+  constexpr int lds = NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t);
+  if (int rc = raise_lds_limit<k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP>>(lds, "k_gemm_tn_split")) return rc;
+  k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP><<<r.grid, TTHR, lds, stream>>>(QAGNN_TN_ARGS, p.a_rowidx, p.A2, p.lda2, p.Ka2, tn_amax(r, p));
   QAGNN_LAUNCH_CHECK("k_gemm_tn_split");
   return QAGNN_OK;
 }
+#undef QAGNN_TN_ARGS
 
-// QAGNN_GEMM_SPLIT=0 pins the fp32-MFMA kernels of gemm.hip: the one numerically distinct fallback (the module mirror reads the same
-// variable for the NN products: qagnn_amd/_lib.py)
-static int tn_split_mode() {
-  static const int v = getenv("QAGNN_GEMM_SPLIT") ? atoi(getenv("QAGNN_GEMM_SPLIT")) : 1;
-  return v;
+// k_gemm_tn_ws is built for the two-operand product [X | S]^T dKMQ, (KT, NT) = (7, 13), in the three arithmetic forms
+int launch_tn_ws(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
+  return dispatch_int<3, 2, 1>(r.np, [&](auto np) { return launch_tn_ws_i<7, 13, false, np.value>(r, p, stream); });
 }
-bool tn_split_ok(int R, int Ka, int No, int lda, int ldb, bool gather, bool affine) {
-  const int v = tn_split_mode();
-  const int64_t big = (int64_t)R * ((lda > ldb && !gather) ? lda : ldb) * 4;  // (a gathered A goes through flat loads)
-  if (gather && (Ka <= 112 || affine)) return false;
-  return v != 0 && Ka >= 64 && No >= 104 && R >= 1024 && big < (int64_t)0x7FFFFFFF;  // 32-bit buffer offsets
-}
-static bool tn_split_wide_b(int Ka) { return Ka <= 112; }  // (KT, NT) = (7, 13), else (13, 7)
-constexpr int TN_WS_MIN_TILES_C = 28;  // (= TN_WS_MIN_TILES below: chunks of that many k-tiles and more run k_gemm_tn_ws)
-// rows per split-K chunk: two blocks per CU, a multiple of the 32-row k-tile, never below `lo` (the workspace's sizing)
-int tn_split_chunk_rows(int R, int Ka, int No, int lo) {
-  const int ac = tn_split_wide_b(Ka) ? 112 : 208, bc = tn_split_wide_b(Ka) ? 208 : 112;
-  const int blocks_per_chunk = cdiv(No, bc) * cdiv(Ka, ac);
-  const int target = 2 * split_num_cus() / blocks_per_chunk;
-  const int rows = (cdiv(R, target > 0 ? target : 1) + TKR - 1) / TKR * TKR;
-  const int lo32 = (lo + TKR - 1) / TKR * TKR;
-  return rows > lo32 ? rows : lo32;
-}
-// [A1 | A2]^T B in one launch: 112-row output tiles (the (7, 13) shape) over A1's columns, then over A2's
-int tn_split2_chunk_rows(int R, int Ka1, int Ka2, int No, int lo) {
-  const int blocks_per_chunk = cdiv(No, 208) * (cdiv(Ka1, 112) + cdiv(Ka2, 112));
-  const int lo32 = (lo + TKR - 1) / TKR * TKR;
-#ifndef QAGNN_TN_WS_TWO_ROUNDS
-  // Long products run k_gemm_tn_ws, ONE 8-wave block per CU: chunks sized for one block per CU (28 chunks of 72 k-tiles at 64 000 rows
-  // instead of 56 of 36) halve the partial sums that are written and summed again and the uncovered first loads / last stores per CU
-  {
-    const int target1 = split_num_cus() / blocks_per_chunk;
-    const int rows1 = (cdiv(R, target1 > 0 ? target1 : 1) + TKR - 1) / TKR * TKR;
-    if (rows1 >= 2 * TN_WS_MIN_TILES_C * TKR) return rows1 > lo32 ? rows1 : lo32;
-  }
-#endif
-  const int target = 2 * split_num_cus() / blocks_per_chunk;
-  const int rows = (cdiv(R, target > 0 ? target : 1) + TKR - 1) / TKR * TKR;
-  return rows > lo32 ? rows : lo32;
-}
-// k_gemm_tn_ws serves the two-operand product [X | S]^T dKMQ where its chunks are long (36 k-tiles per block at 64 000 rows: 201 -> 171 us).
-// Measured with 8 - 24 k-tiles per block (tools/tn_ablate.hip, profiles/r4_run17_tn_ws.txt): 208 x 624 115 -> 126 us, 208 x 208 43 -> 57,
-// 112 x 624 72 -> 74 -- one block per CU leaves a block's first loads and its partial-sum stores uncovered, which only a long chunk
-// amortises; at the 2-tile chunks of a 10-subgraph batch it took 29 us against the 4-wave kernel's ~14 (profiles/r5_run5_tn_ws_min_tiles_ab_b10.txt:
-// the step 2.29 -> 2.22 ms)
-constexpr int TN_WS_MIN_TILES = TN_WS_MIN_TILES_C;
-int launch_tn_split2(const float* A1, int lda1, int Ka1, const float* A2, int lda2, int Ka2, const float* B, int ldb, float* P, int R, int No,
-                     int chunk_rows, hipStream_t stream, const uint32_t* const* amax, int np) {
-  dim3 grid(cdiv(No, 208), cdiv(Ka1, 112) + cdiv(Ka2, 112), cdiv(R, chunk_rows));
-  if (amax) {  // the scaled fp16 forms (amax = {max|A1|, max|A2|, max|B|}; np = 2: three MFMAs, np = 1: one)
-    const TnAmax am{amax[0], amax[1], amax[2]};
-    if (np == 1) {
-      if (chunk_rows >= TN_WS_MIN_TILES * 32)
-        return launch_tn_ws_i<7, 13, false, 1>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, A2, lda2, Ka2, am);
-      return launch_tn_split_i<7, 13, false, false, 1>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, nullptr, A2, lda2, Ka2, am);
-    }
-    if (chunk_rows >= TN_WS_MIN_TILES * 32)
-      return launch_tn_ws_i<7, 13, false, 2>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, A2, lda2, Ka2, am);
-    return launch_tn_split_i<7, 13, false, false, 2>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, nullptr, A2, lda2, Ka2, am);
-  }
-  if (chunk_rows >= TN_WS_MIN_TILES * 32)
-    return launch_tn_ws_i<7, 13, false>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, A2, lda2, Ka2);
-  return launch_tn_split_i<7, 13, false>(grid, stream, A1, lda1, B, ldb, P, R, Ka1, No, nullptr, nullptr, chunk_rows, nullptr, A2, lda2, Ka2);
-}
-int launch_tn_split(const float* A, int lda, const float* B, int ldb, float* P, int R, int Ka, int No, const float* sc, const float* sh,
-                    const int64_t* ridx, int chunk_rows, hipStream_t stream, const uint32_t* const* amax, int np) {
-  if (amax && !ridx && np == 1) {  // the one-MFMA reduced-precision form
-    const TnAmax am{amax[0], nullptr, amax[2]};
-    if (tn_split_wide_b(Ka)) {
-      dim3 grid(cdiv(No, 208), cdiv(Ka, 112), cdiv(R, chunk_rows));
-      return sc ? launch_tn_split_i<7, 13, true, false, 1>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am)
-                : launch_tn_split_i<7, 13, false, false, 1>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am);
-    }
-    dim3 grid(cdiv(No, 112), cdiv(Ka, 208), cdiv(R, chunk_rows));
-    return sc ? launch_tn_split_i<13, 7, true, false, 1>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am)
-              : launch_tn_split_i<13, 7, false, false, 1>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am);
-  }
-  if (amax && !ridx) {  // the three-MFMA form (amax = {max|A|, -, max|B|})
-    const TnAmax am{amax[0], nullptr, amax[2]};
-    if (tn_split_wide_b(Ka)) {
-      dim3 grid(cdiv(No, 208), cdiv(Ka, 112), cdiv(R, chunk_rows));
-      return sc ? launch_tn_split_i<7, 13, true, false, 2>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am)
-                : launch_tn_split_i<7, 13, false, false, 2>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am);
-    }
-    dim3 grid(cdiv(No, 112), cdiv(Ka, 208), cdiv(R, chunk_rows));
-    return sc ? launch_tn_split_i<13, 7, true, false, 2>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am)
-              : launch_tn_split_i<13, 7, false, false, 2>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, nullptr, nullptr, 0, 0, am);
-  }
-  if (ridx) {
-    dim3 grid(cdiv(No, 112), cdiv(Ka, 208), cdiv(R, chunk_rows));
-    return launch_tn_split_i<13, 7, false, true>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows, ridx);
-  }
-  if (tn_split_wide_b(Ka)) {
-    dim3 grid(cdiv(No, 208), cdiv(Ka, 112), cdiv(R, chunk_rows));
-    return sc ? launch_tn_split_i<7, 13, true>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows)
-              : launch_tn_split_i<7, 13, false>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows);
-  }
-  dim3 grid(cdiv(No, 112), cdiv(Ka, 208), cdiv(R, chunk_rows));
-  return sc ? launch_tn_split_i<13, 7, true>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows)
-            : launch_tn_split_i<13, 7, false>(grid, stream, A, lda, B, ldb, P, R, Ka, No, sc, sh, chunk_rows);
+// (KT, NT) = (7, 13) or (13, 7); the row gather exists for (13, 7) without prologue in the six-MFMA form
+int launch_tn_split(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
+  if (r.gather) return launch_tn_split_i<13, 7, false, true>(r, p, stream);
+  return dispatch_bool(r.kt == 7, [&](auto wide_b) {
+    return dispatch_bool(r.affine, [&](auto aff) {
+      return dispatch_int<3, 2, 1>(r.np, [&](auto np) {
+        constexpr int KT = wide_b.value ? 7 : 13;
+        return launch_tn_split_i<KT, 20 - KT, aff.value, false, np.value>(r, p, stream);
+      });
+    });
+  });
 }
 
 }  // namespace qagnn
-
-using namespace qagnn;
-
-extern "C" int64_t qagnn_gemm_nn_pack_bytes(int32_t No, int32_t K1, int32_t K2) { return nn2_pack_bytes(No, K1, K2, 3) + 256; }  // (>= the two-piece image + its scale words)
-
-extern "C" int64_t qagnn_gemm_nn_ws_bytes(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2) {
-  if (!a || !B1n || !nn2_ok(*a, ldn1, ldn2)) return 0;                                      // not a product of the packed kernels
-  const int np = nn2_h2_ok(*a) ? (a->pieces == 1 ? 1 : 2) : 3;
-  if (nn2_prepack_lookup(B1n, ldn1, a->K1, B2n, ldn2, a->K2, a->No, np)) return 0;  // B is registered: nothing to pack per call
-  const int64_t need = nn2_pack_bytes(a->No, a->K1, a->K2, np);
-  return nn2_packed_ok(*a, need, np) ? need : 0;                                              // (too few rows: the in-kernel split)
-}
-
-extern "C" int qagnn_gemm_nn_split_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
-                                       qagnn_stream_t stream_) {
-  return qagnn_gemm_nn_split_ws_f32(a, B1n, ldn1, B2n, ldn2, nullptr, 0, stream_);
-}
-
-extern "C" int qagnn_gemm_nn_split_ws_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
-                                          void* ws, int64_t ws_bytes, qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  TimedScope timed(0, stream);
-  QAGNN_REQUIRE(a && a->A1 && B1n && a->C, QAGNN_EINVAL, "gemm_nn_split: null pointer");
-  QAGNN_REQUIRE(a->M > 0 && a->No > 0 && a->K1 >= 4, QAGNN_EINVAL, "gemm_nn_split: bad sizes M=%d No=%d K1=%d", a->M, a->No, a->K1);
-  QAGNN_REQUIRE(a->K1 % 4 == 0 && a->K2 % 4 == 0 && a->K2 >= 0 && (a->K2 == 0 || a->K2 >= 4), QAGNN_EINVAL,
-                "gemm_nn_split: K1=%d K2=%d must be multiples of 4", a->K1, a->K2);
-  QAGNN_REQUIRE(a->No % 4 == 0, QAGNN_EINVAL, "gemm_nn_split: No=%d must be a multiple of 4", a->No);
-  QAGNN_REQUIRE(a->lda1 % 4 == 0 && ldn1 % 4 == 0 && ldn1 >= a->K1 && aligned16(a->A1) && aligned16(B1n), QAGNN_EINVAL,
-                "gemm_nn_split: operand 1 must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(a->K2 == 0 || (a->A2 && B2n && a->lda2 % 4 == 0 && ldn2 % 4 == 0 && ldn2 >= a->K2 && aligned16(a->A2) && aligned16(B2n)),
-                QAGNN_EINVAL, "gemm_nn_split: operand 2 must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a->rowtab || a->rowidx, QAGNN_EINVAL, "gemm_nn_split: rowtab without rowidx");
-  QAGNN_REQUIRE(a->ldc % 4 == 0 && aligned16(a->C) && (!a->bias || aligned16(a->bias)) && (!a->rowtab || (aligned16(a->rowtab) && a->ldt % 4 == 0)),
-                QAGNN_EINVAL, "gemm_nn_split: C / bias / rowtab must be 16-byte aligned with pitches multiple of 4");
-  QAGNN_REQUIRE(!a->a_scale || (a->a_shift && aligned16(a->a_scale) && aligned16(a->a_shift)), QAGNN_EINVAL,
-                "gemm_nn_split: a_scale/a_shift must both be given and 16-byte aligned");
-  const int nt16 = cdiv(a->No, 16);
-  if (a->colstat_part) {
-    const int64_t lim = (int64_t)0x7FFFFFFF;
-    QAGNN_REQUIRE(nt16 == 13 && !a->a_scale && !a->a_rowidx && !a->rowtab && !a->accumulate && a->K2 == 0, QAGNN_EUNSUPPORTED,
-                  "gemm_nn_split: column statistics need 193..208 output columns and a bias-only epilogue (No=%d)", a->No);
-    QAGNN_REQUIRE((int64_t)a->M * a->lda1 * 4 < lim && (int64_t)a->No * ldn1 * 4 < lim, QAGNN_EUNSUPPORTED,
-                  "gemm_nn_split: column statistics with operands of 2 GB and more");
-  }
-  int nt = nt16 >= 13 ? 13 : nt16 >= 8 ? 8 : nt16 >= 7 ? 7 : nt16 >= 4 ? 4 : 2;
-  // Few row tiles (the host-bound configurations: 10 subgraphs are 16 row tiles, a 64-subgraph MedQA shard 100, on 256 CUs): a
-  // block's time is its own serial k-loop, which scales with the column tiles it carries, and the other CUs idle -- so the column
-  // tile narrows until there are about 1.5 blocks per CU (or it is 32 columns wide).  Measured, rocprofv3 kernel durations
-  // (profiles/r3_run5_nn_small_m.txt): 2 000 x 208 x 208 25.3 -> 9.4 us at 32 columns; 12 800 rows 27.3 -> 16.3 us at 64 columns
-  // (18.6 at 32); 624 -> 208 at 12 800 rows 63 -> 37 us.  The arithmetic per output element does not depend on the tile shape:
-  // results are bit-identical.
-  {
-    const int row_tiles = cdiv(a->M, SBM), want = split_num_cus() * 3 / 2;
-    const int cands[3] = {7, 4, 2};
-    for (int ci = 0; ci < 3 && row_tiles * cdiv(a->No, nt * 16) < want; ++ci)
-      if (cands[ci] < nt) nt = cands[ci];
-  }
-  if (nn2_ok(*a, ldn1, ldn2)) {
-    // The three-MFMA form where the operand maxima are known (a_amax1 / a_amax2) and B's two-piece image exists or can be made
-    if (nn2_h2_ok(*a)) {
-      const int np = a->pieces == 1 ? 1 : 2;  // (1: the one-MFMA reduced-precision form, on request only)
-      if (const void* pk = nn2_prepack_lookup(B1n, ldn1, a->K1, B2n, ldn2, a->K2, a->No, np)) return launch_nn2_prepacked(nt, *a, pk, stream, np);
-      if (ws && aligned16(ws) && nn2_packed_ok(*a, ws_bytes, np)) return launch_nn2_packed(nt, *a, B1n, ldn1, B2n, ldn2, ws, stream, np);
-    }
-    // B pre-packed by the caller (qagnn_gemm_nn_prepack_f32: one launch for all weights of a step)?
-    if (const void* pk = nn2_prepack_lookup(B1n, ldn1, a->K1, B2n, ldn2, a->K2, a->No)) return launch_nn2_prepacked(nt, *a, pk, stream);
-    if (ws && nn2_packed_ok(*a, ws_bytes)) {
-      QAGNN_REQUIRE(aligned16(ws), QAGNN_EINVAL, "gemm_nn_split: the pack workspace must be 16-byte aligned");
-      return launch_nn2_packed(nt, *a, B1n, ldn1, B2n, ldn2, ws, stream);
-    }
-    return launch_nn2(nt, *a, B1n, ldn1, B2n, ldn2, stream);
-  }
-  switch (nt) {
-    case 13: return launch_split<13>(*a, B1n, ldn1, B2n, ldn2, stream);
-    case 8: return launch_split<8>(*a, B1n, ldn1, B2n, ldn2, stream);
-    case 7: return launch_split<7>(*a, B1n, ldn1, B2n, ldn2, stream);
-    case 4: return launch_split<4>(*a, B1n, ldn1, B2n, ldn2, stream);
-    default: return launch_split<2>(*a, B1n, ldn1, B2n, ldn2, stream);
-  }
-}

@@ -57,13 +57,10 @@ struct HopAmax {
   uint32_t* y;      // where this hop's GELU / dropout leaves max |y|
   uint32_t* own;    // the hop's own block
 };
-// The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays from nn2_pack_min_m() rows on (packed B images)
-static bool hop_h2(const qagnn_hop_args* h) { return h->gemm_split >= 2 && h->amax != nullptr && h->batch_stats && h->N >= nn2_pack_min_m(); }
+// The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays where products take packed B images
+static bool hop_h2(const qagnn_hop_args* h) { return h->gemm_split >= 2 && h->amax != nullptr && h->batch_stats && nn_rows_packed(h->N); }
 // gemm_split == 3: the reduced-precision form (one fp16 MFMA per product) wherever 2 would take three
 static int hop_pieces(const qagnn_hop_args* h) { return h->gemm_split == 3 ? 1 : 0; }
-typedef int (*tn_scaled_fn)(const float*, int32_t, int32_t, const float*, int32_t, int32_t, const float*, int32_t, float*, int32_t, int32_t, int32_t,
-                            const float*, const float*, const uint32_t*, const uint32_t*, const uint32_t*, float*, qagnn_stream_t);
-static tn_scaled_fn hop_tn(const qagnn_hop_args* h) { return h->gemm_split == 3 ? qagnn_gemm_tn_h1_f32 : qagnn_gemm_tn_h2_f32; }
 static HopAmax hop_amax_single(const qagnn_hop_args* h) {
   HopAmax m{hop_h2(h), nullptr, nullptr, nullptr, h->amax};
   if (m.on) {  // (x_amax / s_amax: words the caller's producers filled; read-only here)
@@ -106,8 +103,14 @@ extern "C" int64_t qagnn_hop_fwd_workspace_elems(int32_t N, int32_t Ep, int32_t 
 // [No][K] layout, which the hop holds for every weight (W and W^T both arrive packed)
 static int hop_nn(const qagnn_hop_args* h, const qagnn_gemm_nn_args* a, const float* B1n, int ldn1, const float* B2n, int ldn2,
                   float* pkws, int64_t pk_elems, qagnn_stream_t stream) {
-  if (h->gemm_split && a->K1 % 4 == 0 && a->K2 % 4 == 0) return qagnn_gemm_nn_split_ws_f32(a, B1n, ldn1, B2n, ldn2, pkws, pk_elems * 4, stream);
-  return qagnn_gemm_nn_f32(a, stream);
+  return gemm_nn(NnProduct{a, h->gemm_split != 0, B1n, ldn1, B2n, ldn2, pkws, pk_elems * 4}, (hipStream_t)stream);
+}
+// weight gradient C = [A1 | A2]^T B over the hop's N rows (A2 == nullptr: one operand); am_*: the operands' maxima -- the scaled form
+// the hop asks for where all of them are known (am_b is, in a backward that runs the form), the six-MFMA form otherwise
+static int hop_tn(const qagnn_hop_args* h, const float* A1, int Ka1, const float* A2, int Ka2, const float* B, int No, float* C, const float* sc,
+                  const float* sh, const uint32_t* am_a1, const uint32_t* am_a2, const uint32_t* am_b, float* tnws, qagnn_stream_t stream) {
+  return gemm_tn(tn_product(A1, Ka1, Ka1, A2, Ka2, Ka2, B, No, C, No, h->N, No, sc, sh, tnws, am_a1, am_a2, am_b, h->gemm_split == 3 ? 1 : 2),
+                 (hipStream_t)stream);
 }
 
 // x_ready / s_ready: the words of X / S already hold this call's maxima (an earlier hop of the stack produced them)
@@ -285,6 +288,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   // (the three-MFMA form in the backward needs every maximum the forward left: the same condition, and h1's bound)
   const bool h2 = am.on && DP > 192 && DP <= 208;
   uint32_t* const w_dout = h2 ? am.own + AM_DOUT : nullptr, *const w_dh1 = h2 ? am.own + AM_DH1 : nullptr, *const w_dkmq = h2 ? am.own + AM_DKMQ : nullptr;
+  const uint32_t* const w_h1 = h2 ? am.own + AM_H1 : nullptr, *const w_aggr = h2 ? am.own + AM_AGGR : nullptr;
   if (h->apply_act) {
     HOP_TRY(launch_gelu_dropout(h->out, h->dy, bufA, (int64_t)N * DP, h->p_drop, h->seed, w_dout, ampart, (hipStream_t)stream));
     dout = bufA;
@@ -295,8 +299,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
     HOP_TRY(qagnn_colreduce_f32(0, dout, DP, nullptr, DP, N, DP, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, h->db2, crws, stream));
   // second Linear: dW2^T = relu(bn(h1))^T dout, d r = dout W2
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
-  if (h2) HOP_TRY(hop_tn(h)(h->h1, DP, DP, nullptr, 0, 0, dout, DP, h->dW2t, DP, N, DP, scale, shift, am.own + AM_H1, nullptr, w_dout, tnws, wstream));
-  else HOP_TRY(qagnn_gemm_tn_f32(h->h1, DP, dout, DP, h->dW2t, DP, N, DP, DP, scale, shift, nullptr, 0, tnws, wstream));
+  HOP_TRY(hop_tn(h, h->h1, DP, nullptr, 0, dout, DP, h->dW2t, scale, shift, w_h1, nullptr, w_dout, tnws, wstream));
   // relu(bn(h1)) carries a column of ones there: that row of the weight gradient is the bias gradient (no copy when the caller's db2 IS
   // that row)
   if (h->ones_col >= 0 && h->db2 != h->dW2t + (int64_t)h->ones_col * DP) {
@@ -313,8 +316,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
                                     h->batch_stats ? (float)(1.0 / (double)N) : 0.f, nullptr, h->db1, crws, w_dh1, (hipStream_t)stream));
   // first Linear (db1 = colsum(d h1) came out of the pass above)
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
-  if (h2) HOP_TRY(hop_tn(h)(h->aggr, DP, DP, nullptr, 0, 0, bufC, DP, h->dW1t, DP, N, DP, nullptr, nullptr, am.own + AM_AGGR, nullptr, w_dh1, tnws, wstream));
-  else HOP_TRY(qagnn_gemm_tn_f32(h->aggr, DP, bufC, DP, h->dW1t, DP, N, DP, DP, nullptr, nullptr, nullptr, 0, tnws, wstream));
+  HOP_TRY(hop_tn(h, h->aggr, DP, nullptr, 0, bufC, DP, h->dW1t, nullptr, nullptr, w_aggr, nullptr, w_dh1, tnws, wstream));
   qagnn_gemm_nn_args gg = {};
   gg.A1 = bufC; gg.lda1 = DP; gg.K1 = DP; gg.B1 = h->W1; gg.ldb1 = DP; gg.C = bufB; gg.ldc = DP; gg.M = N; gg.No = DP;
   gg.a_amax1 = w_dh1; gg.pieces = hop_pieces(h);
@@ -324,17 +326,11 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
                                h2 ? ampart : nullptr, w_dkmq, (hipStream_t)stream));
   // projection: weight gradients, node-type-table gradient, data gradients
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
-  if (SP > 0 && h->dWs_t == h->dWx_t + (int64_t)DP * 3 * DP) {  // the two gradients are one [DP + SP, 3 DP] matrix: one launch
-    if (h2) HOP_TRY(hop_tn(h)(h->X, DP, DP, h->S, SP, SP, dKMQ, 3 * DP, h->dWx_t, 3 * DP, N, 3 * DP, nullptr, nullptr, am.x, am.s, w_dkmq, tnws, wstream));
-    else HOP_TRY(qagnn_gemm_tn2_f32(h->X, DP, DP, h->S, SP, SP, dKMQ, 3 * DP, h->dWx_t, 3 * DP, N, 3 * DP, tnws, wstream));
-  } else if (h2) {
-    HOP_TRY(hop_tn(h)(h->X, DP, DP, nullptr, 0, 0, dKMQ, 3 * DP, h->dWx_t, 3 * DP, N, 3 * DP, nullptr, nullptr, am.x, nullptr, w_dkmq, tnws, wstream));
-    if (SP > 0)
-      HOP_TRY(hop_tn(h)(h->S, SP, SP, nullptr, 0, 0, dKMQ, 3 * DP, h->dWs_t, 3 * DP, N, 3 * DP, nullptr, nullptr, am.s, nullptr, w_dkmq, tnws, wstream));
+  if (SP > 0 && h->dWs_t == h->dWx_t + (int64_t)DP * 3 * DP) {  // the two gradients are one [DP + SP, 3 DP] matrix: one product
+    HOP_TRY(hop_tn(h, h->X, DP, h->S, SP, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, am.s, w_dkmq, tnws, wstream));
   } else {
-    HOP_TRY(qagnn_gemm_tn_f32(h->X, DP, dKMQ, 3 * DP, h->dWx_t, 3 * DP, N, DP, 3 * DP, nullptr, nullptr, nullptr, 0, tnws, wstream));
-    if (SP > 0)
-      HOP_TRY(qagnn_gemm_tn_f32(h->S, SP, dKMQ, 3 * DP, h->dWs_t, 3 * DP, N, SP, 3 * DP, nullptr, nullptr, nullptr, 0, tnws, wstream));
+    HOP_TRY(hop_tn(h, h->X, DP, nullptr, 0, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, nullptr, w_dkmq, tnws, wstream));
+    if (SP > 0) HOP_TRY(hop_tn(h, h->S, SP, nullptr, 0, dKMQ, 3 * DP, h->dWs_t, nullptr, nullptr, am.s, nullptr, w_dkmq, tnws, wstream));
   }
   if (SP > 0 && h->tab_col >= 0) {
     // the type indicators ride in S's padding columns: their rows of dWs_t ARE the type-table gradient

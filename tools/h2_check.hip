@@ -52,7 +52,11 @@ int main(int argc, char** argv) {
   void* ws;
   CK(hipMalloc(&ws, qagnn::nn2_pack_bytes(No, K1, K2, np)));
   const int nt = No >= 208 ? 13 : 7;
-  int rc = qagnn::launch_nn2_packed(nt, a, dB1, K1, K2 ? dB2 : nullptr, K2, ws, 0, np);
+  qagnn::NnRoute r = {};
+  r.family = qagnn::NnFamily::NN2; r.b = qagnn::NnB::PACK; r.nt = nt; r.np = np; r.wv = 4;
+  qagnn::nn_grid(r, M, No, 128, 2);
+  int rc = qagnn::launch_pack_b(np, a, dB1, K1, K2 ? dB2 : nullptr, K2, ws, 0);
+  if (rc == 0) rc = qagnn::launch_nn2(r, a, (const float*)ws, (No + 15) / 16, nullptr, 0, 0);
   CK(hipDeviceSynchronize());
   printf("rc %d  M %d K1 %d K2 %d No %d np %d  amax %g %g\n", rc, M, K1, K2, No, np, am1, am2);
   std::vector<float> C((size_t)M * No);

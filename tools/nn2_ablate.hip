@@ -41,8 +41,9 @@ static float* dev_rand(size_t n, unsigned seed) {
 
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 64000;
-  struct Shape { const char* name; int K1, K2, No; } shapes[] = {{"mlp 208->208", 208, 0, 208}, {"proj [208|112]->624", 208, 112, 624},
-                                                                 {"dX 624->208", 624, 0, 208}, {"dS 624->112", 624, 0, 112}};
+  // wv6: the block the library takes in the six-MFMA form at 64 000 rows (nn_route, gemm_dispatch.hip: 8 = the staggered block)
+  struct Shape { const char* name; int K1, K2, No, wv6; } shapes[] = {{"mlp 208->208", 208, 0, 208, 4}, {"proj [208|112]->624", 208, 112, 624, 8},
+                                                                      {"dX 624->208", 624, 0, 208, 8}, {"dS 624->112", 624, 0, 112, 4}};
   hipStream_t st;
   CK(hipStreamCreate(&st));
   hipEvent_t e0, e1;
@@ -76,13 +77,11 @@ int main(int argc, char** argv) {
       CK(hipMalloc(&ws, qagnn::nn2_pack_bytes(sh.No, sh.K1, sh.K2, f.np)));
       qagnn_gemm_nn_args b = a;
       if (f.np <= 2) { b.a_amax1 = am; b.a_amax2 = sh.K2 ? am + 1 : nullptr; }
-      qagnn::launch_nn2_packed(nt, b, B1n, sh.K1, B2n, sh.K2, ws, st, f.np);  // (packs the image)
-      auto run = [&] {
-        if (f.wv == 0) return qagnn::launch_nn2_prepacked(nt, b, ws, st, 3);
-        if (f.np == 1)
-          return nt == 13 ? qagnn::nn2::launch_nt<13, 1, true>(b, (const float*)ws, NJ, nullptr, 0, st) : qagnn::nn2::launch_nt<7, 1, true>(b, (const float*)ws, NJ, nullptr, 0, st);
-        return nt == 13 ? qagnn::nn2::launch_nt<13, 2, true>(b, (const float*)ws, NJ, nullptr, 0, st) : qagnn::nn2::launch_nt<7, 2, true>(b, (const float*)ws, NJ, nullptr, 0, st);
-      };
+      qagnn::launch_pack_b(f.np, b, B1n, sh.K1, B2n, sh.K2, ws, st);
+      qagnn::NnRoute r = {};
+      r.family = qagnn::NnFamily::NN2; r.b = qagnn::NnB::PACK; r.nt = nt; r.np = f.np; r.wv = f.wv ? f.wv : sh.wv6;
+      qagnn::nn_grid(r, M, sh.No, r.wv * 32, r.wv == 8 ? 1 : 2);
+      auto run = [&] { return qagnn::launch_nn2(r, b, (const float*)ws, NJ, nullptr, 0, st); };
       for (int i = 0; i < 3; ++i) run();
       CK(hipStreamSynchronize(st));
       const int reps = 30;

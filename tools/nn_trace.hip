@@ -11,7 +11,10 @@ int main() {
   for (auto& s : shapes) {
     qagnn_gemm_nn_args a = {};
     a.A1 = A1; a.lda1 = s.K1; a.K1 = s.K1; a.C = Cc; a.ldc = s.No; a.M = M; a.No = s.No;
-    for (int i = 0; i < 5; ++i) qagnn_gemm_nn_split_f32(&a, B1, s.K1, nullptr, 0, 0);
+    qagnn::NnRoute r = {};
+    r.family = qagnn::NnFamily::SPLIT; r.nt = 13; r.np = 3; r.wv = 4;
+    qagnn::nn_grid(r, M, s.No, 128, 2);
+    for (int i = 0; i < 5; ++i) qagnn::launch_nn_split(r, a, B1, s.K1, nullptr, 0, 0);
     hipDeviceSynchronize();
     static unsigned long long tr[4][40][7];
     hipMemcpyFromSymbol(tr, HIP_SYMBOL(qagnn::g_nn_trace), sizeof(tr));

@@ -16,14 +16,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
-// (the NN half of the translation unit refers to gemm_nn2.hip)
-bool nn2_ok(const qagnn_gemm_nn_args&, int, int) { return false; }
-bool nn2_packed_ok(const qagnn_gemm_nn_args&, int64_t) { return false; }
-int64_t nn2_pack_bytes(int, int, int) { return 0; }
-int launch_nn2(int, const qagnn_gemm_nn_args&, const float*, int, const float*, int, hipStream_t) { return 0; }
-int launch_nn2_packed(int, const qagnn_gemm_nn_args&, const float*, int, const float*, int, void*, hipStream_t) { return 0; }
-const void* nn2_prepack_lookup(const float*, int, int, const float*, int, int, int) { return nullptr; }
-int launch_nn2_prepacked(int, const qagnn_gemm_nn_args&, const void*, hipStream_t) { return 0; }
 }  // namespace qagnn
 
 #define CK(x)                                                                      \
@@ -47,8 +39,9 @@ static float* dev_rand(size_t n, unsigned seed) {
 
 int main() {
   const int R = 64000;
-  struct Shape { const char* name; int Ka1, Ka2, No; } shapes[] = {{"[X|S]^T dKMQ  208+112 x 624", 208, 112, 624}, {"208 x 624", 208, 0, 624},
-                                                                  {"208 x 208", 208, 0, 208}, {"112 x 624", 112, 0, 624}};
+  // chunk: the rows per split-K chunk the library takes for the shape at 64 000 rows on 256 CUs (tn_route, gemm_dispatch.hip)
+  struct Shape { const char* name; int Ka1, Ka2, No, chunk; } shapes[] = {{"[X|S]^T dKMQ  208+112 x 624", 208, 112, 624, 2304}, {"208 x 624", 208, 0, 624, 768},
+                                                                         {"208 x 208", 208, 0, 208, 256}, {"112 x 624", 112, 0, 624, 384}};
   hipStream_t st;
   CK(hipStreamCreate(&st));
   hipEvent_t e0, e1;
@@ -59,26 +52,18 @@ int main() {
     float* A1 = dev_rand((size_t)R * sh.Ka1, 1);
     float* A2 = sh.Ka2 ? dev_rand((size_t)R * sh.Ka2, 2) : nullptr;
     float* B = dev_rand((size_t)R * sh.No, 3);
-    const int chunk = sh.Ka2 ? qagnn::tn_split2_chunk_rows(R, sh.Ka1, sh.Ka2, sh.No, 0) : qagnn::tn_split_chunk_rows(R, sh.Ka1, sh.No, 0);
-    const int nchunk = (R + chunk - 1) / chunk;
+    const int chunk = sh.chunk, nchunk = (R + chunk - 1) / chunk;
     float* P;
     CK(hipMalloc(&P, (size_t)nchunk * (sh.Ka1 + sh.Ka2) * sh.No * 4));
+    const qagnn::TnProduct p = qagnn::tn_product(A1, sh.Ka1, sh.Ka1, A2, sh.Ka2, sh.Ka2, B, sh.No, nullptr, sh.No, R, sh.No, nullptr, nullptr, P);
+    const bool wide_b = sh.Ka2 || sh.Ka1 <= 112;  // (KT, NT) = (7, 13), else (13, 7)
+    qagnn::TnRoute r = {};
+    r.np = 3; r.kt = wide_b ? 7 : 13; r.nt = 20 - r.kt; r.chunk_rows = chunk; r.nchunks = nchunk;
+    r.grid = dim3((sh.No + r.nt * 16 - 1) / (r.nt * 16), (sh.Ka1 + r.kt * 16 - 1) / (r.kt * 16) + (sh.Ka2 ? (sh.Ka2 + 111) / 112 : 0), nchunk);
     for (int ws = 0; ws < 2; ++ws) {
       auto run = [&] {
-        if (sh.Ka2) {
-          if (ws) { dim3 grid((sh.No + 207) / 208, (sh.Ka1 + 111) / 112 + (sh.Ka2 + 111) / 112, nchunk);
-            qagnn::launch_tn_ws_i<7, 13, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk, A2, sh.Ka2, sh.Ka2);
-          } else { dim3 grid((sh.No + 207) / 208, (sh.Ka1 + 111) / 112 + (sh.Ka2 + 111) / 112, nchunk);
-            qagnn::launch_tn_split_i<7, 13, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk, nullptr, A2, sh.Ka2, sh.Ka2); }
-        } else if (sh.Ka1 <= 112) {
-          dim3 grid((sh.No + 207) / 208, (sh.Ka1 + 111) / 112, nchunk);
-          if (ws) qagnn::launch_tn_ws_i<7, 13, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk);
-          else qagnn::launch_tn_split_i<7, 13, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk);
-        } else {
-          dim3 grid((sh.No + 111) / 112, (sh.Ka1 + 207) / 208, nchunk);
-          if (ws) qagnn::launch_tn_ws_i<13, 7, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk);
-          else qagnn::launch_tn_split_i<13, 7, false>(grid, st, A1, sh.Ka1, B, sh.No, P, R, sh.Ka1, sh.No, nullptr, nullptr, chunk);
-        }
+        if (wide_b) ws ? qagnn::launch_tn_ws_i<7, 13, false>(r, p, st) : qagnn::launch_tn_split_i<7, 13, false>(r, p, st);
+        else ws ? qagnn::launch_tn_ws_i<13, 7, false>(r, p, st) : qagnn::launch_tn_split_i<13, 7, false>(r, p, st);
       };
       for (int i = 0; i < 3; ++i) run();
       CK(hipStreamSynchronize(st));
