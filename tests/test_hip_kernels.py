@@ -4,7 +4,9 @@ against a float64 evaluation with a backward-error bound (|d| <= c * eps32 * sum
 """
 import contextlib
 import ctypes
+import functools
 import os
+import types
 
 import numpy as np
 import pytest
@@ -62,9 +64,52 @@ def padded_graph(seed, B, n, real, E, R=38, T=4):
     return torch.stack([src, tgt]), torch.randint(0, R, (E,), generator=g), torch.randint(0, T, (B * n,), generator=g), R, T
 
 
+# Segment lengths (self loop included) at which the edge kernels of csrc/edge_attn.hip change path: the 16-edge register groups of the
+# deg <= 64 softmax (15|16|17, 31|32|33, 47|48|49, 63|64), the switch to the hub path at 65, the 64-edge chunks that every kernel walks
+# (64|65, 128|129, 192|193), the short tail chunks whose EDGE_UNROLL batch holds clamped duplicates (66 .. 69, 130, 131), and the
+# ~200-edge context node of a real CommonsenseQA subgraph.
+LADDER_W = [2, 3, 4, 5, 6, 15, 16, 17, 18, 31, 32, 33, 34, 47, 48, 49, 50, 63, 64, 65, 66, 67, 68, 69, 127, 128, 129, 130, 131, 191, 192, 193, 200]
+LADDER_CLASS_COUNTS = [1, 63, 64, 65, 127, 128, 129]  # edges of the types 0 .. 6: around one and two QAGNN_CLS_CHUNK = 64 chunks
+
+
+def degree_ladder(seed=11, R=38, T=4, pool=256):
+    """One source star and one target star per w in LADDER_W: star i has w - 1 edges to (from) distinct leaves of a pool of 256, so with the
+    self loop of the graph preparation its source (target) segment is exactly w edges long.  Nodes: [0, |W|) source stars, [|W|, 2 |W|)
+    target stars, the leaf pool, 7 isolated nodes; one node type, so an edge's class is its type.  Types 0 .. 6 hold exactly
+    LADDER_CLASS_COUNTS edges (type 7 none, the rest random in 8 .. R - 1)."""
+    g = torch.Generator().manual_seed(seed)
+    nW = len(LADDER_W)
+    src, tgt = [], []
+    for i, w in enumerate(LADDER_W):
+        leaves = 2 * nW + torch.randperm(pool, generator=g)[:w - 1]
+        src += [i] * (w - 1)
+        tgt += leaves.tolist()
+        leaves = 2 * nW + torch.randperm(pool, generator=g)[:w - 1]
+        src += leaves.tolist()
+        tgt += [nW + i] * (w - 1)
+    N, E = 2 * nW + pool + 7, len(src)
+    et = torch.randint(8, R, (E,), generator=g)
+    perm, o = torch.randperm(E, generator=g), 0
+    for r, c in enumerate(LADDER_CLASS_COUNTS):
+        et[perm[o:o + c]] = r
+        o += c
+    return torch.tensor([src, tgt]), et, torch.zeros(N, dtype=torch.long), R, T
+
+
+def class_ladder(seed=12, N=40, R=38, T=4):
+    """577 random edges among 40 nodes of one type whose types 0 .. 6 hold exactly LADDER_CLASS_COUNTS edges: E' = 617 <= CLS_BLK, one
+    position group, so those counts are the lengths the class pass (k_edge_bwd_cls, k_cls_reduce) cuts into chunks."""
+    g = torch.Generator().manual_seed(seed)
+    E = sum(LADDER_CLASS_COUNTS)
+    ei = torch.randint(0, N, (2, E), generator=g)
+    et = torch.cat([torch.full((c,), r) for r, c in enumerate(LADDER_CLASS_COUNTS)])[torch.randperm(E, generator=g)]
+    return ei, et, torch.zeros(N, dtype=torch.long), R, T
+
+
 GRAPH_CASES = [('big_pad', lambda: padded_graph(7, 320, 200, 128, 400000)), ('rand_small', lambda: rand_graph(1, 50, 300)), ('rand_hub', lambda: rand_graph(2, 700, 9000, hub=True)),
                ('no_edges', lambda: rand_graph(3, 40, 0)), ('one_node', lambda: rand_graph(4, 1, 5)),
-               ('medqa_classes', lambda: rand_graph(5, 3000, 40000, R=34)), ('big', lambda: rand_graph(6, 64000, 400000))]
+               ('medqa_classes', lambda: rand_graph(5, 3000, 40000, R=34)), ('big', lambda: rand_graph(6, 64000, 400000)),
+               ('degree_ladder', degree_ladder), ('class_ladder', class_ladder)]
 
 
 def golden_graph(case):
@@ -426,14 +471,18 @@ def test_sin_basis_matches_host_libm():
     assert (got - ref).abs().max().item() < 5e-7
 
 
+HEAD_DIM = {52: 50, 8: 8, 28: 25, 16: 16}  # head pitch HP -> live floats per head (the rest of a head's slots are zero pads)
+
+
+def _graph_of(case_or_name):
+    return dict(GRAPH_CASES)[case_or_name]() if case_or_name in dict(GRAPH_CASES) else golden_graph(case_or_name)
+
+
 def edge_inputs(case_or_name, HP, seed):
-    if case_or_name in dict(GRAPH_CASES):
-        ei, et, nt, R, T = dict(GRAPH_CASES)[case_or_name]()
-    else:
-        ei, et, nt, R, T = golden_graph(case_or_name)
+    ei, et, nt, R, T = _graph_of(case_or_name)
     g = torch.Generator().manual_seed(seed)
     N, C, DP = nt.numel(), R * T * T + T, 4 * HP
-    dh = {52: 50, 8: 8, 28: 25, 16: 16}[HP]
+    dh = HEAD_DIM[HP]
     mask = (torch.arange(DP) % HP < dh).float()
     KMQ = torch.randn(N, 3 * DP, generator=g) * mask.repeat(3)
     EkEm = torch.randn(C, 2 * DP, generator=g) * mask.repeat(2)
@@ -441,54 +490,149 @@ def edge_inputs(case_or_name, HP, seed):
     return (ei, et, nt, R, T), KMQ, EkEm, G, 1.0 / dh ** 0.5
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize('name,HP', [('csqa_b10', 52), ('medqa_b8', 52), ('small_train', 8), ('rand_hub', 52), ('rand_small', 28),
-                                     ('no_edges', 16), ('one_node', 52), ('big', 52), ('big_pad', 52)])
-def test_edge_attention_forward_backward(name, HP):
-    (ei, et, nt, R, T), KMQ, EkEm, G, qs = edge_inputs(name, HP, 21)
-    K = hip()
-    g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
-    aggr, a, alpha = K.edge_attn_fwd(g, KMQ.cuda(), EkEm.cuda(), HP, qs)
-    dKMQ, dEkEm = K.edge_attn_bwd(g, KMQ.cuda(), EkEm.cuda(), HP, qs, a, alpha, G.cuda())
-    torch.cuda.synchronize()
+def edge_inputs_offset(case_or_name, HP, seed):
+    """Exact scores with a large common offset: every entry is -1, 0 or 1, except the first column of every head, where Q = 32, K = 0 and
+    Ek = 16; qscale = 1/4.  Every raw score is then 128 + (an integer of at most dh - 1) / 4, exactly in fp32: exp(score) overflows fp32
+    (e^128 > 3.4e38) unless the segment's maximum is subtracted first, score - max is exact, and the softmax stays spread over its segment
+    (neighbouring scores differ by quarters), so a maximum taken over the wrong slots shows as well."""
+    ei, et, nt, R, T = _graph_of(case_or_name)
+    g = torch.Generator().manual_seed(seed)
+    N, C, DP = nt.numel(), R * T * T + T, 4 * HP
+    mask = (torch.arange(DP) % HP < HEAD_DIM[HP]).float()
+    tern = lambda *shape: torch.randint(-1, 2, shape, generator=g).float()  # noqa: E731
+    KMQ, EkEm, G = tern(N, 3 * DP) * mask.repeat(3), tern(C, 2 * DP) * mask.repeat(2), tern(N, DP) * mask
+    for h in range(4):
+        KMQ[:, h * HP], KMQ[:, 2 * DP + h * HP], EkEm[:, h * HP] = 0.0, 32.0, 16.0
+    return (ei, et, nt, R, T), KMQ, EkEm, G, 0.25
+
+
+EDGE_OUTPUTS = ('aggr', 'a', 'alpha', 'dKMQ', 'dEkEm')
+EDGE_BARS = {'a': 2e-6, 'alpha': 2e-6, 'aggr': 5e-6, 'dKMQ': 2e-5, 'dEkEm': 2e-5}  # of the reference's maximum
+
+
+def _build_edge_case(name, HP, kind):
+    (ei, et, nt, R, T), KMQ, EkEm, G, qs = (edge_inputs_offset if kind == 'offset' else edge_inputs)(name, HP, 21)
     e = EmuGraph(ei, et, nt, R, T)
-    aggr_r, a_r, alpha_r = EMU.edge_attn_fwd(e, KMQ.double(), EkEm.double(), HP, qs)
-    dKMQ_r, dEkEm_r = EMU.edge_attn_bwd(e, KMQ.double(), EkEm.double(), HP, qs, a_r, alpha_r, G.double())
-    for nm, got, ref, tol in (('a', a, a_r, 2e-6), ('alpha', alpha, alpha_r, 2e-6), ('aggr', aggr, aggr_r, 5e-6),
-                              ('dKMQ', dKMQ, dKMQ_r, 2e-5), ('dEkEm', dEkEm, dEkEm_r, 2e-5)):
-        got = got.cpu().double()
+    fwd = EMU.edge_attn_fwd(e, KMQ.double(), EkEm.double(), HP, qs)
+    ref = dict(zip(EDGE_OUTPUTS, fwd + EMU.edge_attn_bwd(e, KMQ.double(), EkEm.double(), HP, qs, fwd[1], fwd[2], G.double())))
+    case = types.SimpleNamespace(name=name, HP=HP, kind=kind, graph=(ei, et, nt, R, T), e=e, KMQ=KMQ, EkEm=EkEm, G=G, qs=qs, ref=ref,
+                                 emu32=None, bars=dict(EDGE_BARS))
+    if kind == 'offset' or name in ('degree_ladder', 'class_ladder'):
+        # The yardstick of the cases added with the ladders: the emulation's own formulas evaluated in float32 (so: the same arithmetic as the
+        # kernels up to the order of the sums), each output's worst error against the float64 evaluation, relative to that output's maximum.
+        # A new case's bar is the fixed bar or 4 x this, whichever is larger -- 4 for the kernels' other summation order (16-lane DPP trees,
+        # 64-edge chunks, class chunk partials) against index_add_.  It comes from the reference alone, never from a kernel's result.
+        f32 = EMU.edge_attn_fwd(e, KMQ, EkEm, HP, qs)
+        f32 = f32 + EMU.edge_attn_bwd(e, KMQ, EkEm, HP, qs, f32[1], f32[2], G)
+        case.emu32 = {nm: ((x.double() - ref[nm]).abs().max() / (ref[nm].abs().max() + 1e-30)).item() for nm, x in zip(EDGE_OUTPUTS, f32)}
+        case.bars = {nm: max(EDGE_BARS[nm], 4 * case.emu32[nm]) for nm in EDGE_OUTPUTS}
+    return case
+
+
+_cached_edge_case = functools.lru_cache(maxsize=None)(_build_edge_case)
+
+
+def edge_case(name, HP, kind='randn'):
+    """Graph, operands (seed 21), the float64 emulation of all five outputs and the bar of each.  The small cases that several tests share
+    are built once per process; nobody writes to what this returns."""
+    small = kind == 'offset' or name in ('degree_ladder', 'class_ladder', 'rand_small')
+    return (_cached_edge_case if small else _build_edge_case)(name, HP, kind)
+
+
+def _worst_row(case, nm, d):
+    """Where `nm`'s largest error sits, in the terms that select a kernel path: the length of the row's segment (self loop included)."""
+    e, DP = case.e, 4 * case.HP
+    deg_s, deg_t = (e.rowptr_s[1:] - e.rowptr_s[:-1]).tolist(), (e.rowptr_t[1:] - e.rowptr_t[:-1]).tolist()
+    row, col = divmod(int(d.argmax()), d.size(1))
+    if nm in ('a', 'alpha'):
+        s = int(e.src_s[row])
+        return f'edge {row} (head {col}) of source node {s}, source degree {deg_s[s]}'
+    if nm == 'aggr':
+        return f'node {row} col {col}, target degree {deg_t[row]}'
+    if nm == 'dKMQ':
+        part = 'dK', 'dM', 'dQ'
+        return f'node {row} col {col} ({part[col // DP]}), ' + (f'target degree {deg_t[row]}' if col < DP else f'source degree {deg_s[row]}')
+    return f'class {row} col {col} ({"dEk" if col < DP else "dEm"}), {int(e.cls_count[row])} edges of that class'
+
+
+def check_edge_outputs(case, got, log=None):
+    """Every assertion the edge-attention tests make on (aggr, a, alpha, dKMQ, dEkEm) against edge_case()'s reference.  `log`: a list that
+    receives one (output, worst error / scale, bar, float32 yardstick) per output before anything is asserted."""
+    e, HP, DP = case.e, case.HP, 4 * case.HP
+    got = {nm: t.detach().cpu() for nm, t in zip(EDGE_OUTPUTS, got)}
+    failures = []
+    for nm in ('a', 'alpha', 'aggr', 'dKMQ', 'dEkEm'):
+        ref = case.ref[nm]
+        d = (got[nm].double() - ref).abs().reshape(ref.size(0), -1)
+        d = torch.where(torch.isnan(d), torch.full_like(d, float('inf')), d)  # (a NaN is the worst error, not one that max() may skip)
         scale = ref.abs().max().item() + 1e-30
-        err = (got - ref).abs().max().item()
-        assert err <= tol * scale, f'{nm}: max err {err:.3e} vs scale {scale:.3e}'
-        assert torch.isfinite(got).all()
+        err = d.max().item() if d.numel() else 0.0
+        if log is not None:
+            log.append((nm, err / scale, case.bars[nm], case.emu32[nm] if case.emu32 else None))
+        if not err <= case.bars[nm] * scale:
+            failures.append(f'{nm}: max err {err:.3e} vs scale {scale:.3e} (bar {case.bars[nm]:.1e}) at {_worst_row(case, nm, d)}')
+        elif not torch.isfinite(got[nm]).all():
+            failures.append(f'{nm} is not finite')
+    assert not failures, '; '.join(failures)
     # pads stay exactly zero
-    DP = 4 * HP
-    dh = {52: 50, 8: 8, 28: 25, 16: 16}[HP]
-    padmask = (torch.arange(DP) % HP >= dh)
-    assert (aggr.cpu()[:, padmask] == 0).all() and (dKMQ.cpu()[:, padmask.repeat(3)] == 0).all()
+    padmask = (torch.arange(DP) % HP >= HEAD_DIM[HP])
+    assert (got['aggr'][:, padmask] == 0).all() and (got['dKMQ'][:, padmask.repeat(3)] == 0).all()
     # softmax rows: sum over each source segment of a == 1 (size-independent property)
-    seg = torch.zeros(e.N, 4, dtype=torch.float64).index_add_(0, e.src_s.long(), a.cpu().double())
-    assert (seg - 1).abs().max().item() < 1e-5
+    seg = torch.zeros(e.N, 4, dtype=torch.float64).index_add_(0, e.src_s.long(), got['a'].double())
+    worst = (seg - 1).abs().max(1).values
+    deg_s = e.rowptr_s[1:] - e.rowptr_s[:-1]
+    assert worst.max().item() < 1e-5, f'sum of a over the segment of source degree {int(deg_s[worst.argmax()])} is off by {worst.max().item():.3e}'
     # a node row whose only edge is its self loop (every PAD row) gets dK = dQ = 0 EXACTLY -- softmax of one score has the gradient
     # a (ga - a ga) = 0 whatever K, Q, G hold: 27 % of a CommonsenseQA batch's projection gradient is structurally zero (DESIGN.md section 6)
     lone = (torch.bincount(e.es, minlength=e.N) == 1) & (torch.bincount(e.et, minlength=e.N) == 1)
-    dk = dKMQ.cpu()
+    dk = got['dKMQ']
     assert (dk[lone][:, :DP] == 0).all() and (dk[lone][:, 2 * DP:] == 0).all()
+
+
+def run_edge_kernels(case):
+    (ei, et, nt, R, T), HP, qs = case.graph, case.HP, case.qs
+    K = hip()
+    g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
+    aggr, a, alpha = K.edge_attn_fwd(g, case.KMQ.cuda(), case.EkEm.cuda(), HP, qs)
+    dKMQ, dEkEm = K.edge_attn_bwd(g, case.KMQ.cuda(), case.EkEm.cuda(), HP, qs, a, alpha, case.G.cuda())
+    torch.cuda.synchronize()
+    return aggr, a, alpha, dKMQ, dEkEm
+
+
+def print_figures(label, log):
+    """One line per case for the record of a GPU run (profiles/attention_ladder_gpu_tests.txt; shown by pytest -s, or on failure): per output
+    the worst error / the bar, both as fractions of the reference's maximum, and the float32 emulation's error where the bar rests on it."""
+    print(f'FIGURE {label}: ' + ' | '.join(f'{nm} {err:.2e} / {bar:.2e}' + ('' if yard is None else f' (f32 {yard:.2e})') for nm, err, bar, yard in log))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name,HP', [('csqa_b10', 52), ('medqa_b8', 52), ('small_train', 8), ('rand_hub', 52), ('rand_small', 28),
+                                     ('no_edges', 16), ('one_node', 52), ('big', 52), ('big_pad', 52),
+                                     ('degree_ladder', 52), ('degree_ladder', 8), ('degree_ladder', 28), ('class_ladder', 52),
+                                     ('class_ladder', 16)])
+def test_edge_attention_forward_backward(name, HP):
+    case = edge_case(name, HP)
+    log = []
+    try:
+        check_edge_outputs(case, run_edge_kernels(case), log)
+    finally:
+        print_figures(f'edge[{name}-{HP}-randn]', log)
 
 
 @pytest.mark.gpu
 def test_edge_attention_is_deterministic():
-    (ei, et, nt, R, T), KMQ, EkEm, G, qs = edge_inputs('rand_hub', 52, 3)
-    K = hip()
-    outs = []
-    for _ in range(3):
-        g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
-        aggr, a, alpha = K.edge_attn_fwd(g, KMQ.cuda(), EkEm.cuda(), 52, qs)
-        dKMQ, dEkEm = K.edge_attn_bwd(g, KMQ.cuda(), EkEm.cuda(), 52, qs, a, alpha, G.cuda())
-        outs.append([t.cpu() for t in (aggr, a, dKMQ, dEkEm)])
-    for o in outs[1:]:
-        for x, y in zip(outs[0], o):
-            assert torch.equal(x, y), 'run-to-run bit difference: a reduction order is not fixed'
+    for name in ('rand_hub', 'degree_ladder'):
+        (ei, et, nt, R, T), KMQ, EkEm, G, qs = edge_inputs(name, 52, 3)
+        K = hip()
+        outs = []
+        for _ in range(3):
+            g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
+            aggr, a, alpha = K.edge_attn_fwd(g, KMQ.cuda(), EkEm.cuda(), 52, qs)
+            dKMQ, dEkEm = K.edge_attn_bwd(g, KMQ.cuda(), EkEm.cuda(), 52, qs, a, alpha, G.cuda())
+            outs.append([t.cpu() for t in (aggr, a, dKMQ, dEkEm)])
+        for o in outs[1:]:
+            for x, y in zip(outs[0], o):
+                assert torch.equal(x, y), f'{name}: run-to-run bit difference: a reduction order is not fixed'
 
 
 @pytest.mark.gpu
@@ -578,7 +722,7 @@ def test_head_post_forward_backward(B, n, NH, DP, dv, Ds, d, p1, p2):
 @pytest.mark.gpu
 @pytest.mark.parametrize('name,HP,mode', [('csqa_b10', 52, 'train'), ('csqa_b10', 52, 'eval'), ('small_train', 8, 'train'),
                                           ('rand_hub', 52, 'train_noact'), ('medqa_b8', 52, 'train_noS'), ('big', 52, 'train'),
-                                          ('big_pad', 52, 'train')])
+                                          ('big_pad', 52, 'train'), ('degree_ladder', 52, 'train')])
 def test_fused_hop_equals_composed_path(name, HP, mode, monkeypatch):
     """qagnn_hop_{fwd,bwd}_f32 (csrc/hop.hip) sequences the library's own launchers: every forward buffer, every gradient and
     the BatchNorm running buffers must be BIT-identical to composing the per-kernel entry points from Python
@@ -1129,12 +1273,13 @@ def test_gemm_tn_reduced_precision_form(R, Ka1, Ka2, No, kind, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['big', 'big_pad', 'csqa_b10-everywhere', 'small_train-everywhere'])
+@pytest.mark.parametrize('name', ['big', 'big_pad', 'csqa_b10-everywhere', 'small_train-everywhere', 'degree_ladder-everywhere'])
 def test_native_hop_in_the_three_mfma_form(name, monkeypatch):
     """The natively sequenced hop with gemm_split = 2 (every large product in the three-MFMA form, the operand maxima travelling from the
     producing kernels) against the same hop with the exact 3 x bf16 products: every forward buffer and every gradient within fp32
     round-off of each other, none bit-identical (the form did run), everything finite; the amax words hold the true maxima.
-    *-everywhere: a golden case's graph (2 000 / 120 node rows; d = 200 and d = 32) with the row threshold at 1 (helpers.form_everywhere)."""
+    *-everywhere: a golden case's graph (2 000 / 120 node rows; d = 200 and d = 32) with the row threshold at 1 (helpers.form_everywhere);
+    degree_ladder (329 rows, d = 200): the per-node maxima of the edge kernels on their one-edge, register, chunked and hub rows."""
     name, _, form = name.partition('-')
     hip()
     with (helpers.form_everywhere() if form else contextlib.nullcontext()):
