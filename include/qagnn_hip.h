@@ -497,7 +497,7 @@ int qagnn_node_prep_f32(const float* raw_scores, const int64_t* adj_len, const i
  * Fused multi-tensor RAdam step.  Replaces the per-parameter Python loop of
  *   utils/optimization_utils.py:31-97  (RAdam.step: ~10 elementwise kernels per tensor, ~70 decoder tensors)
  * p, g, m, v: HOST arrays of n_tensors DEVICE pointers (parameter, gradient, exp_avg, exp_avg_sq; fp32, contiguous, any
- * alignment), numel: host array of element counts.  All tensors share one step count, i.e. one (step_size, mode):
+ * alignment; NULL allowed where numel is 0), numel: host array of element counts.  All tensors share one step count, i.e. one (step_size, mode):
  *   mode 2: N_sma >= 5 (:83-87)   mode 1: SGD-like branch (:89-92)   mode 0: moments only (step_size < 0)
  * Per element:  v = beta2 v + (1-beta2) g g;  m = beta1 m + (1-beta1) g;  p -= weight_decay lr p;  p -= step_size lr m / (sqrt(v)+eps)
  * (or  p -= step_size lr m  in mode 1).  The hyper-parameters are doubles: 1 - beta, weight_decay lr and step_size lr are formed in
@@ -506,6 +506,34 @@ int qagnn_node_prep_f32(const float* raw_scores, const int64_t* adj_len, const i
 int qagnn_radam_step_f32(int32_t n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v,
                          const int64_t* numel, double beta1, double beta2, double eps, double lr, double weight_decay, double step_size,
                          int32_t mode, qagnn_stream_t stream);
+/* The same step with every gradient multiplied by the DEVICE word *grad_scale as it is read:  gi = fl32(g[i] * *grad_scale), then the
+ * update above on gi -- the gradients themselves are not written.  With grad_scale = out2 + 1 of qagnn_grad_norm_f32 (below) this is
+ * clip_grad_norm_ followed by the step without the clipped gradients ever reaching memory, bit-identical to qagnn_scale_multi_f32
+ * followed by qagnn_radam_step_f32.  grad_scale = NULL IS qagnn_radam_step_f32: the same kernel, the same bits. */
+int qagnn_radam_step_scaled_f32(int32_t n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                const int64_t* numel, double beta1, double beta2, double eps, double lr, double weight_decay,
+                                double step_size, int32_t mode, const float* grad_scale, qagnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Global-norm gradient clipping on the device.  Replaces, between the backward pass and the optimiser step,
+ *   qagnn.py:267-278  torch.nn.utils.clip_grad_norm_(model.parameters(), args.max_grad_norm)   (--max_grad_norm defaults to 1.0:
+ *                     every training run clips; ~10 launches and one more read and write of every gradient)
+ * g: HOST array of n_tensors DEVICE pointers (fp32, contiguous, any alignment; NULL allowed where numel is 0), numel: host array of
+ * element counts, each in [0, 2^31).
+ * qagnn_grad_norm_f32:  out2[0] = total_norm = sqrt(sum over all tensors of g^2),  out2[1] = min(1, max_norm / (total_norm + 1e-6)) --
+ *   torch's formula, no special casing: a NaN or inf among the gradients gives the norm and the coefficient torch gives; all-zero
+ *   gradients give 0 and exactly 1.  Two stages, no atomics, the same bits on every call: one fp32 partial per 4096-element chunk
+ *   (16 sequential adds per thread, an 8-level tree over the 256 threads) into `workspace` (qagnn_grad_norm_workspace_elems floats,
+ *   contents undefined before and after), then one block sums the partials in a fixed order in double; the coefficient is formed in
+ *   double and rounded once.  Worst-case relative error of the norm: ((16 + 8 + 1) / 2 + 1) 2^-24.
+ * qagnn_scale_multi_f32:  g[i] = fl32(g[i] * *scale) for every element, *scale a DEVICE word (out2 + 1: the in-place clip, for any
+ *   optimiser).  The coefficient never visits the host.
+ * Pointer tables travel in the kernel arguments, like the RAdam step's: nothing to allocate, capture safe.
+ * ------------------------------------------------------------------------------------------------------------ */
+int64_t qagnn_grad_norm_workspace_elems(int32_t n_tensors, const int64_t* numel);
+int qagnn_grad_norm_f32(int32_t n_tensors, const float* const* g, const int64_t* numel, double max_norm, float* workspace,
+                        float* out2, qagnn_stream_t stream);
+int qagnn_scale_multi_f32(int32_t n_tensors, float* const* g, const int64_t* numel, const float* scale, qagnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -24,10 +24,11 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_edge_attn_fwd_f32', 'qagnn_edge_attn_bwd_f32',
            'qagnn_hop_fwd_workspace_elems', 'qagnn_hop_bwd_workspace_elems', 'qagnn_hop_fwd_f32', 'qagnn_hop_bwd_f32',
            'qagnn_stack_fwd_f32', 'qagnn_stack_bwd_f32', 'qagnn_absmax_f32', 'qagnn_zero_words', 'qagnn_gemm_tn_h2_f32', 'qagnn_gelu_dropout_fwd_amax_f32', 'qagnn_gelu_dropout_amax_scratch_elems',
-           'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows']
+           'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows',
+           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
-ABI_VERSION = 22  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows)
+ABI_VERSION = 23  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32)
 
 _i32, _i64, _f32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p
 
@@ -93,6 +94,11 @@ def load_library(path=LIB_PATH):
     lib.qagnn_seed_epoch_advance.argtypes = [_u64, _vp]
     lib.qagnn_seed_epoch_set.argtypes = [_u64, _vp]
     lib.qagnn_radam_step_f32.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp] + [C.c_double] * 6 + [_i32, _vp]
+    lib.qagnn_radam_step_scaled_f32.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp] + [C.c_double] * 6 + [_i32, _vp, _vp]
+    lib.qagnn_grad_norm_workspace_elems.restype = _i64
+    lib.qagnn_grad_norm_workspace_elems.argtypes = [_i32, _vp]
+    lib.qagnn_grad_norm_f32.argtypes = [_i32, _vp, _vp, C.c_double, _vp, _vp, _vp]
+    lib.qagnn_scale_multi_f32.argtypes = [_i32, _vp, _vp, _vp, _vp]
     lib.qagnn_gemm_nn_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp]
     lib.qagnn_gemm_nn_split_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i32, _vp]
     lib.qagnn_gemm_nn_pack_bytes.restype = _i64
@@ -420,17 +426,64 @@ class HipKernels(metaclass=_GuardedMeta):
             ERR_WATCH.watch(flags, 'concept_ids (an id outside the entity table)')
         return score, mask, ridx
 
-    def radam_step(self, params, grads, exp_avgs, exp_avg_sqs, beta1, beta2, eps, lr, weight_decay, step_size, mode):
-        """One fused RAdam update of a list of fp32 device tensors that share a step count (qagnn_radam_step_f32)."""
+    def radam_step(self, params, grads, exp_avgs, exp_avg_sqs, beta1, beta2, eps, lr, weight_decay, step_size, mode, grad_scale=None):
+        """One fused RAdam update of a list of fp32 device tensors that share a step count (qagnn_radam_step_f32).
+        grad_scale: a one-element fp32 device tensor (grad_norm()'s coefficient word) every gradient is multiplied by as it is read
+        (qagnn_radam_step_scaled_f32); the gradients are not written."""
         n = len(params)
         for group in (params, grads, exp_avgs, exp_avg_sqs):
             assert len(group) == n and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in group)
         assert all(p.numel() == g.numel() == m.numel() == v.numel() for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs))
         tab = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
         numel = (C.c_int64 * n)(*[t.numel() for t in params])
-        rc = self.lib.qagnn_radam_step_f32(n, tab(params), tab(grads), tab(exp_avgs), tab(exp_avg_sqs), numel, float(beta1), float(beta2),
-                                           float(eps), float(lr), float(weight_decay), float(step_size), int(mode), self._stream())
-        self._check(rc, 'qagnn_radam_step_f32')
+        args = (n, tab(params), tab(grads), tab(exp_avgs), tab(exp_avg_sqs), numel, float(beta1), float(beta2),
+                float(eps), float(lr), float(weight_decay), float(step_size), int(mode))
+        if grad_scale is None:
+            self._check(self.lib.qagnn_radam_step_f32(*args, self._stream()), 'qagnn_radam_step_f32')
+            return
+        self._check_scale_word(grad_scale, params[0].device if n else grad_scale.device)
+        self._check(self.lib.qagnn_radam_step_scaled_f32(*args, grad_scale.data_ptr(), self._stream()), 'qagnn_radam_step_scaled_f32')
+
+    GRAD_NORM_CHUNK, GRAD_NORM_THREADS = 4096, 256  # csrc/optim.hip: MT_CHUNK, MT_THREADS (the reduction shape of grad_norm's stage 1)
+
+    @staticmethod
+    def _check_scale_word(scale, device):
+        assert scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == device, \
+            f'need a one-element fp32 tensor on {device}, got {tuple(scale.shape)} {scale.dtype} {scale.device}'
+
+    @staticmethod
+    def _grad_table(grads):
+        n = len(grads)
+        assert all(g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == grads[0].device for g in grads)
+        return n, (C.c_void_p * n)(*[g.data_ptr() for g in grads]), (C.c_int64 * n)(*[g.numel() for g in grads])
+
+    def grad_norm(self, grads, max_norm, workspace=None):
+        """-> fp32 [2] on the gradients' device: [0] the global L2 norm of a list of fp32 device tensors, [1] the clip coefficient
+        min(1, max_norm / (norm + 1e-6)) (qagnn_grad_norm_f32; torch.nn.utils.clip_grad_norm_'s formula).  Nothing comes back to the host.
+        workspace: an fp32 device tensor of at least grad_norm_workspace_elems(grads) elements (else one is allocated)."""
+        n, tab, numel = self._grad_table(grads)
+        dev = grads[0].device if n else torch.device('cuda', torch.cuda.current_device())
+        need = int(self.lib.qagnn_grad_norm_workspace_elems(n, numel))
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=dev)
+        assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.device == dev \
+            and workspace.numel() >= need, f'grad_norm: need {need} fp32 workspace elements on {dev}'
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        self._check(self.lib.qagnn_grad_norm_f32(n, tab, numel, float(max_norm), workspace.data_ptr(), out.data_ptr(), self._stream()),
+                    'qagnn_grad_norm_f32')
+        return out
+
+    def grad_norm_workspace_elems(self, grads):
+        n, _, numel = self._grad_table(grads)
+        return int(self.lib.qagnn_grad_norm_workspace_elems(n, numel))
+
+    def scale_multi(self, grads, scale):
+        """g *= scale[0] for every tensor of a list of fp32 device tensors, scale a one-element device tensor (qagnn_scale_multi_f32)."""
+        n, tab, numel = self._grad_table(grads)
+        if n == 0:
+            return
+        self._check_scale_word(scale, grads[0].device)
+        self._check(self.lib.qagnn_scale_multi_f32(n, tab, numel, scale.data_ptr(), self._stream()), 'qagnn_scale_multi_f32')
 
     # -- GEMMs ---------------------------------------------------------------------------------------------------
     STAT_TILE = 128  # rows per tile of the column statistics a GEMM can leave behind (gemm_split.hip: SBM)

@@ -6,6 +6,10 @@ but the update itself is ONE fused multi-tensor HIP launch sequence per (group, 
 kernels per parameter in a Python loop: the decoder has ~70 tensors / 2.85 M parameters, so a reference step is ~700 tiny
 launches.  fp32 parameters on the GPU go through libqagnn_hip's qagnn_radam_step_f32; parameters that live on the CPU (unit
 tests of the training driver) are updated with the same formulas in torch.
+
+`clip_grad_norm_` is the line in front of the optimiser step in the reference's training loop (qagnn.py:267-278): the global L2 norm
+and the clip coefficient are computed on the device (qagnn_grad_norm_f32) and applied either in place (qagnn_scale_multi_f32, any
+optimiser) or, with `defer_to=` a `RAdam` of this module, inside that optimiser's next step as it reads the gradients.
 """
 import math
 
@@ -105,7 +109,15 @@ class RAdam(Optimizer):
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
         self.degenerated_to_sgd = degenerated_to_sgd
+        self._grad_scale = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def defer_grad_scale(self, scale):
+        """The NEXT step() reads every gradient as grad * scale (a one-element fp32 tensor, e.g. the clip coefficient left on the device
+        by clip_grad_norm_(..., defer_to=self)) and leaves the gradients themselves untouched; consumed by that one step.  None: no scale."""
+        if scale is not None and not (isinstance(scale, torch.Tensor) and scale.numel() == 1 and scale.dtype == torch.float32):
+            raise TypeError('defer_grad_scale: need a one-element fp32 tensor or None')
+        self._grad_scale = scale
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -113,6 +125,7 @@ class RAdam(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        scale, self._grad_scale = self._grad_scale, None
         for group in self.param_groups:
             beta1, beta2 = group['betas']
             buckets = {}  # (step, on_gpu) -> lists: parameters that share a step count share step_size and the branch taken
@@ -129,7 +142,7 @@ class RAdam(Optimizer):
                 state['step'] += 1
                 fused = p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
                 buckets.setdefault((state['step'], fused, p.device if fused else None), []).append(p)
-            for (step, fused, _dev), ps in buckets.items():
+            for (step, fused, dev), ps in buckets.items():
                 n_sma, step_size = radam_step_size(step, beta1, beta2, self.degenerated_to_sgd)
                 mode = 2 if n_sma >= 5 else (1 if step_size > 0 else 0)
                 if fused:
@@ -137,11 +150,14 @@ class RAdam(Optimizer):
                     grads = [p.grad if (p.grad.dtype == torch.float32 and p.grad.is_contiguous()) else p.grad.float().contiguous() for p in ps]
                     ops.kernels().radam_step(list(ps), grads, [self.state[p]['exp_avg'] for p in ps],
                                              [self.state[p]['exp_avg_sq'] for p in ps], beta1, beta2, group['eps'], group['lr'],
-                                             group['weight_decay'], step_size, mode)
+                                             group['weight_decay'], step_size, mode,
+                                             grad_scale=None if scale is None else scale.to(dev).reshape(1))
                     continue
                 for p in ps:  # CPU tensors / other dtypes: the same update, tensor by tensor (utils/optimization_utils.py:52-93)
                     state = self.state[p]
                     grad = p.grad.float()
+                    if scale is not None:
+                        grad = grad * scale.to(grad.device).reshape(())
                     p32 = p.float()
                     m, v = state['exp_avg'], state['exp_avg_sq']
                     v.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
@@ -156,6 +172,43 @@ class RAdam(Optimizer):
                         p32.add_(m, alpha=-step_size * group['lr'])
                     p.copy_(p32)
         return loss
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None, *, defer_to=None):
+    """torch.nn.utils.clip_grad_norm_ as the reference's training loop calls it (qagnn.py:267-278), without leaving the device: returns
+    the total norm (0-dim tensor) and scales the gradients by min(1, max_norm / (norm + 1e-6)).
+
+    Fused path -- every gradient fp32, contiguous, dense and on ONE GPU, norm_type == 2, error_if_nonfinite false: two-stage deterministic
+    norm + coefficient on the device (qagnn_grad_norm_f32), then
+      defer_to=None       one multi-tensor launch sequence g *= coef (qagnn_scale_multi_f32): works with any optimiser;
+      defer_to=optimizer  (this module's RAdam only) the gradients are left as they are and the optimiser keeps the coefficient word: its
+                          next step() multiplies each gradient by it as it reads (qagnn_radam_step_scaled_f32) and then drops it.
+    Every other input (CPU tensors, other dtypes, gradients on two devices as in the reference's encoder-on-cuda:0 / decoder-on-cuda:1
+    layout, other norms, error_if_nonfinite) goes as a whole to torch.nn.utils.clip_grad_norm_, which clips in place; defer_to is
+    ignored there and the optimiser is given nothing to apply."""
+    if defer_to is not None and not isinstance(defer_to, RAdam):
+        raise TypeError(f'clip_grad_norm_(defer_to=...) takes a {RAdam.__module__}.RAdam, whose step applies the coefficient; '
+                        f'got {type(defer_to).__name__} (clip in place for every other optimiser: defer_to=None)')
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    fused = (len(grads) > 0 and float(norm_type) == 2.0 and not error_if_nonfinite
+             and all(g.is_cuda and g.dtype == torch.float32 and not g.is_sparse and g.is_contiguous() and g.device == grads[0].device
+                     for g in grads))
+    if not fused:
+        if defer_to is not None:
+            defer_to.defer_grad_scale(None)
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite,
+                                              foreach=foreach)
+    from . import ops
+    k = ops.kernels()
+    out = k.grad_norm(grads, max_norm)
+    if defer_to is not None:
+        defer_to.defer_grad_scale(out[1:2])
+    else:
+        k.scale_multi(grads, out[1:2])
+    return out[0]
 
 
 OPTIMIZER_CLASSES = {
