@@ -16,6 +16,22 @@
  *   - "head-padded" node rows: a feature row of d = H*dh floats is stored as H groups of HP = roundup4(dh) floats
  *     (pads are zero), DP = H*HP floats per row (d=200,H=4: HP=52, DP=208 -> 832-byte rows, 16-byte aligned heads).
  *     H must be 4 (the reference hard-codes head_count=4, modeling_qagnn.py:387) and dh <= 64.
+ *
+ * Non-finite values (NaN, +inf, -inf in fp32 data; index arrays are never non-finite) -- held by tests/test_nonfinite.py
+ *   - For every entry point that takes fp32 data, the SET of non-finite output elements equals that of the float64
+ *     evaluation of the same operation in torch's semantics (tests/emu_kernels.py) on the same inputs.  WHICH non-finite
+ *     value an element holds may differ (the fp16 split of an inf has a NaN low piece).
+ *   - Every element that evaluation leaves finite stays finite and inside the entry point's error bound.
+ *   - In particular the ReLU of the BatchNorm operand prologue (a_scale / a_shift) is torch's: relu(NaN) = NaN, and its
+ *     backward passes the gradient where the forward value is NaN; a NaN batch variance stays NaN in the statistics and
+ *     the running buffers (torch.nn.BatchNorm1d does the same).  A poisoned hop hands on NaN, never plausible numbers.
+ *   - The ONE exemption: a softmax segment of one edge (a node whose only edge is its self loop -- 40 % of a CommonsenseQA
+ *     batch's rows).  qagnn_edge_attn_fwd_f32 writes a = alpha = 1 there without reading the score, so a non-finite K, Q
+ *     or Ek row of such a segment leaves its a / alpha finite where the reference's softmax gives NaN, and
+ *     qagnn_edge_attn_bwd_f32 writes that segment's exactly-zero softmax gradient (dQ = 0) without reading a row.  (M, Em
+ *     and G of such a row still reach aggr and dM.)
+ *   - Every dropout site multiplies by its keep factor (0 or 1 / (1 - p)): a dropped NaN stays NaN, as in torch.
+ *   - The operand-maximum words (qagnn_absmax_f32 and the *_amax by-products) skip NaN; an inf gives 0x7F800000.
  */
 #ifndef QAGNN_HIP_H
 #define QAGNN_HIP_H

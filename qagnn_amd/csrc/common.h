@@ -320,6 +320,9 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// max(v, lo) that keeps a NaN of v (fmaxf returns the other operand): the ReLU of the BatchNorm operand prologues is torch's, relu(NaN) = NaN.
+// For finite v it equals fmaxf(v, lo) up to the sign of zero.
+__device__ __forceinline__ float floor_nan(float v, float lo) { return v < lo ? lo : v; }
 __device__ __forceinline__ float4 fma4(float s, float4 a, float4 acc) {
   return make_float4(fmaf(s, a.x, acc.x), fmaf(s, a.y, acc.y), fmaf(s, a.z, acc.z), fmaf(s, a.w, acc.w));
 }

@@ -67,10 +67,10 @@ __global__ __launch_bounds__(256) void k_colreduce(const float* __restrict__ X, 
         } else {
           const float4 h = hs[u];
           float4 dy;
-          dy.x = fmaf(h.x, sc.x, sh.x) > 0.f ? x.x : 0.f;
-          dy.y = fmaf(h.y, sc.y, sh.y) > 0.f ? x.y : 0.f;
-          dy.z = fmaf(h.z, sc.z, sh.z) > 0.f ? x.z : 0.f;
-          dy.w = fmaf(h.w, sc.w, sh.w) > 0.f ? x.w : 0.f;
+          dy.x = fmaf(h.x, sc.x, sh.x) <= 0.f ? 0.f : x.x;
+          dy.y = fmaf(h.y, sc.y, sh.y) <= 0.f ? 0.f : x.y;
+          dy.z = fmaf(h.z, sc.z, sh.z) <= 0.f ? 0.f : x.z;
+          dy.w = fmaf(h.w, sc.w, sh.w) <= 0.f ? 0.f : x.w;
           acc[0] = add4(acc[0], dy);
           acc[1].x = fmaf(dy.x, (h.x - mu.x) * is.x, acc[1].x);
           acc[1].y = fmaf(dy.y, (h.y - mu.y) * is.y, acc[1].y);
@@ -140,7 +140,7 @@ __global__ void k_bn_relu_bwd(const float* __restrict__ dR, const float* __restr
   float4 o;
 #define ONE(f)                                              \
   {                                                         \
-    const float dy = fmaf(h.f, sc.f, sh.f) > 0.f ? g.f : 0.f; \
+    const float dy = fmaf(h.f, sc.f, sh.f) <= 0.f ? 0.f : g.f; \
     const float hh = (h.f - mu.f) * is.f;                   \
     o.f = ga.f * is.f * (dy - k1.f * inv_rows - hh * (k2.f * inv_rows)); \
   }
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(BF_COLS * BF_PARTS) void k_bn_stats_finalize(const 
     __syncthreads();
   }
   if (q == 0 && c < Cc) {
-    const float mean = a.mean, var = fmaxf(a.m2 / (float)R, 0.f);  // biased, as BatchNorm normalises with
+    const float mean = a.mean, var = floor_nan(a.m2 / (float)R, 0.f);  // biased, as BatchNorm normalises with
     const float is = rsqrtf(var + eps), sc = gamma[c] * is;
     stats[c] = mean;
     stats[Cc + c] = var;
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_colsum(const float* __restr
         float4 o;
 #define ONE(f)                                                          \
   {                                                                     \
-    const float dy = fmaf(h.f, sc.f, sh.f) > 0.f ? x.f : 0.f;           \
+    const float dy = fmaf(h.f, sc.f, sh.f) <= 0.f ? 0.f : x.f;          \
     const float hh = (h.f - mu.f) * is.f;                               \
     o.f = ga.f * is.f * (dy - k1.f * ir - hh * (k2.f * ir));            \
   }

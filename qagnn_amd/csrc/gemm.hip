@@ -139,10 +139,10 @@ __global__ __launch_bounds__(WAVES * 64) QAGNN_NN_ATTR void k_gemm_nn(qagnn_gemm
         if (AFFINE && kt < nk1) {
           const int k0 = kt * BK;
           const float4 sc = ld4(a.a_scale + k0 + ac4 * 4), sh = ld4(a.a_shift + k0 + ac4 * 4);
-          v.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-          v.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-          v.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-          v.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+          v.x = floor_nan(fmaf(v.x, sc.x, sh.x), 0.f);
+          v.y = floor_nan(fmaf(v.y, sc.y, sh.y), 0.f);
+          v.z = floor_nan(fmaf(v.z, sc.z, sh.z), 0.f);
+          v.w = floor_nan(fmaf(v.w, sc.w, sh.w), 0.f);
         }
         if (a.a_rowidx && kt < nk1 && arow[p] < 0) v = make_float4(0.f, 0.f, 0.f, 0.f);  // gathered "-1" rows are zero rows
         st4(As + (ar + p * (NTHR / 4)) * PA_NN + ac4 * 4, v);
@@ -278,10 +278,10 @@ __global__ __launch_bounds__(1024) void k_gemm_tn(const float* __restrict__ A, i
       if (srow >= 0) {
         v = ld4(A + srow * lda + acol);
         if (AFFINE) {
-          v.x = fmaxf(fmaf(v.x, a_sc.x, a_sh.x), 0.f);
-          v.y = fmaxf(fmaf(v.y, a_sc.y, a_sh.y), 0.f);
-          v.z = fmaxf(fmaf(v.z, a_sc.z, a_sh.z), 0.f);
-          v.w = fmaxf(fmaf(v.w, a_sc.w, a_sh.w), 0.f);
+          v.x = floor_nan(fmaf(v.x, a_sc.x, a_sh.x), 0.f);
+          v.y = floor_nan(fmaf(v.y, a_sc.y, a_sh.y), 0.f);
+          v.z = floor_nan(fmaf(v.z, a_sc.z, a_sh.z), 0.f);
+          v.w = floor_nan(fmaf(v.w, a_sc.w, a_sh.w), 0.f);
         }
       }
       ra = v;
@@ -419,10 +419,10 @@ __global__ __launch_bounds__(NWT * 64) void k_gemm_tn_strip(const float* __restr
         v = ld4(A + srow * lda + acol);
         if (AFFINE) {  // BN affine of these 4 columns: re-read per tile (L1 hit) rather than held in 8 registers
           const float4 a_sc = ld4(a_scale + acol), a_sh = ld4(a_shift + acol);
-          v.x = fmaxf(fmaf(v.x, a_sc.x, a_sh.x), 0.f);
-          v.y = fmaxf(fmaf(v.y, a_sc.y, a_sh.y), 0.f);
-          v.z = fmaxf(fmaf(v.z, a_sc.z, a_sh.z), 0.f);
-          v.w = fmaxf(fmaf(v.w, a_sc.w, a_sh.w), 0.f);
+          v.x = floor_nan(fmaf(v.x, a_sc.x, a_sh.x), 0.f);
+          v.y = floor_nan(fmaf(v.y, a_sc.y, a_sh.y), 0.f);
+          v.z = floor_nan(fmaf(v.z, a_sc.z, a_sh.z), 0.f);
+          v.w = floor_nan(fmaf(v.w, a_sc.w, a_sh.w), 0.f);
         }
       }
       ra = v;

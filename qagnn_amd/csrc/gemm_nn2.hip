@@ -88,8 +88,8 @@ __device__ __forceinline__ void split_frag2(const u32x4s (&r)[2], u32x4s (&f)[NP
     const uint32_t ux = r[e >> 2][e & 3], uy = r[(e + 1) >> 2][(e + 1) & 3];
     float x = __builtin_bit_cast(float, ux), y = __builtin_bit_cast(float, uy);
     if constexpr (AFFINE) {
-      x = fmaxf(fmaf(x, sc[e], sh[e]), lo);
-      y = fmaxf(fmaf(y, sc[e + 1], sh[e + 1]), lo);
+      x = floor_nan(fmaf(x, sc[e], sh[e]), lo);
+      y = floor_nan(fmaf(y, sc[e + 1], sh[e + 1]), lo);
     }
     if constexpr (NP == 2) split2(x, y, s, ph[e >> 1], pl[e >> 1]);
     else split1(x, y, s, ph[e >> 1]);
@@ -105,7 +105,7 @@ __device__ __forceinline__ void split_frag(const u32x4s (&r)[2], u32x4s (&f)[3],
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     uint32_t u = r[e >> 2][e & 3];
-    if constexpr (AFFINE) u = __builtin_bit_cast(uint32_t, fmaxf(fmaf(__builtin_bit_cast(float, u), sc[e], sh[e]), lo));
+    if constexpr (AFFINE) u = __builtin_bit_cast(uint32_t, floor_nan(fmaf(__builtin_bit_cast(float, u), sc[e], sh[e]), lo));
     split3(u, h1[e], h2[e], h3[e]);
   }
   const u32x4s p1 = {pack_hi(h1[0], h1[1]), pack_hi(h1[2], h1[3]), pack_hi(h1[4], h1[5]), pack_hi(h1[6], h1[7])};

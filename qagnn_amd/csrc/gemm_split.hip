@@ -181,10 +181,10 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         if (AFFINE && first) {
           const int kc = min(k0, K - 4);
           const float4 sc = ld4(a.a_scale + kc), sh = ld4(a.a_shift + kc);
-          v.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-          v.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-          v.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-          v.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+          v.x = floor_nan(fmaf(v.x, sc.x, sh.x), 0.f);
+          v.y = floor_nan(fmaf(v.y, sc.y, sh.y), 0.f);
+          v.z = floor_nan(fmaf(v.z, sc.z, sh.z), 0.f);
+          v.w = floor_nan(fmaf(v.w, sc.w, sh.w), 0.f);
         }
         if constexpr (FLAT) {
           const bool ok = kin && (!first || arow[p] >= 0) && (first || m0 + lr + p * 32 < a.M);
@@ -410,7 +410,7 @@ __device__ __forceinline__ void store_task(uint16_t* __restrict__ img, int img_e
       float v = j == 0 ? r[i].x : j == 1 ? r[i].y : j == 2 ? r[i].z : r[i].w;
       if (AFF) {
         const float s = j == 0 ? sc.x : j == 1 ? sc.y : j == 2 ? sc.z : sc.w, h = j == 0 ? sh.x : j == 1 ? sh.y : j == 2 ? sh.z : sh.w;
-        v = fmaxf(fmaf(v, s, h), 0.f);
+        v = floor_nan(fmaf(v, s, h), 0.f);
       }
       x[i] = v;
     }
@@ -657,7 +657,7 @@ __device__ __forceinline__ void store_task_lo(uint16_t* __restrict__ img, int im
       float v = j == 0 ? r[i].x : j == 1 ? r[i].y : j == 2 ? r[i].z : r[i].w;
       if (AFF) {
         const float s_ = j == 0 ? sc.x : j == 1 ? sc.y : j == 2 ? sc.z : sc.w, h = j == 0 ? sh.x : j == 1 ? sh.y : j == 2 ? sh.z : sh.w;
-        v = fmaxf(fmaf(v, s_, h), lo);
+        v = floor_nan(fmaf(v, s_, h), lo);
       }
       x[i] = v;
     }

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64 * POOL_W) void k_pool_fwd(const float* __restric
     const int64_t base = ((int64_t)b * NH + h) * n;
     for (int l = lane; l < n; l += 64) {
       const float a = sc[h * n + l] * inv;
-      const float ad = (p > 0.f && uniform01(seed, (uint64_t)(base + l)) < p) ? 0.f : a * keep_scale;
+      const float ad = a * ((p > 0.f && uniform01(seed, (uint64_t)(base + l)) < p) ? 0.f : keep_scale);  // (x 0, as torch's dropout: keeps a NaN)
       attn[base + l] = a;
       attn_d[base + l] = ad;
       sc[h * n + l] = ad;

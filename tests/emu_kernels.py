@@ -67,6 +67,17 @@ def _chk(*tensors):
         assert t is None or (t.dim() == 2 and t.is_contiguous()), f'operand must be a contiguous 2-D tensor, got {tuple(t.shape)} / {t.stride()}'
 
 
+def _same(a, b):
+    """torch.equal that takes a NaN for equal to a NaN in the same place (operand self-checks under non-finite data)."""
+    return a.shape == b.shape and bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+
+
+def _relu_bwd(g, pre):
+    """torch's relu backward (threshold_backward), a SELECT: 0 where the forward input is <= 0, else the gradient -- so the gradient
+    passes where that input is NaN, and a non-finite gradient at a masked element is dropped."""
+    return torch.where(pre <= 0, torch.zeros((), dtype=g.dtype, device=g.device), g)
+
+
 def _uniform01(seed, idx):
     """numpy twin of uniform01() in csrc/elementwise.hip (splitmix64 finaliser)."""
     with np.errstate(over='ignore'):
@@ -141,7 +152,8 @@ class EmuKernels:
     def _gather_rows(A, idx):
         if idx is None:
             return A
-        return A[idx.clamp(min=0)] * (idx >= 0).to(A.dtype).unsqueeze(1)
+        # a negative index reads a zero row (selected, not multiplied by 0: 0 * NaN would leak table row 0 into it)
+        return torch.where((idx >= 0).unsqueeze(1), A[idx.clamp(min=0)], torch.zeros((), dtype=A.dtype, device=A.device))
 
     STAT_TILE = 128
 
@@ -172,8 +184,8 @@ class EmuKernels:
     def gemm_nn(self, A1, B1, A2=None, B2=None, bias=None, rowtab=None, rowidx=None, a_scale=None, a_shift=None,
                 out=None, accumulate=False, a_rowidx=None, B1n=None, B2n=None, colstats=False):
         _chk(A1, B1, A2, B2, out, rowtab, B1n, B2n)
-        assert B1n is None or (B1n.shape == (B1.size(1), B1.size(0)) and torch.equal(B1n, B1.t())), 'B1n must be B1 transposed'
-        assert B2n is None or (B2n.shape == (B2.size(1), B2.size(0)) and torch.equal(B2n, B2.t())), 'B2n must be B2 transposed'
+        assert B1n is None or (B1n.shape == (B1.size(1), B1.size(0)) and _same(B1n, B1.t())), 'B1n must be B1 transposed'
+        assert B2n is None or (B2n.shape == (B2.size(1), B2.size(0)) and _same(B2n, B2.t())), 'B2n must be B2 transposed'
         A1 = self._gather_rows(A1, a_rowidx)
         if a_scale is not None:
             A1 = torch.relu(A1 * a_scale + a_shift)
@@ -248,11 +260,11 @@ class EmuKernels:
         return invstd, scale, shift
 
     def bn_bwd_reduce(self, dR, H, mean, invstd, scale, shift):
-        dy = dR * ((H * scale + shift) > 0)
+        dy = _relu_bwd(dR, H * scale + shift)
         return torch.stack([dy.sum(0), (dy * (H - mean) * invstd).sum(0)])
 
     def bn_relu_bwd(self, dR, H, mean, invstd, scale, shift, gamma, red, inv_rows, roww=None):
-        dy = dR * ((H * scale + shift) > 0)
+        dy = _relu_bwd(dR, H * scale + shift)
         w = inv_rows if roww is None else roww.unsqueeze(1)
         return gamma * invstd * (dy - red[0] * w - (H - mean) * invstd * (red[1] * w))
 
@@ -292,6 +304,17 @@ class EmuKernels:
     HEAD_LIMITS = (4, 256, 256)
 
     @staticmethod
+    def _head_blocks(BDv, NH, DP, dv):
+        """The NH diagonal [DP, dv] blocks of BDv, which must be block diagonal (head h's rows reach head h's outputs only).  The products
+        are taken head by head, as the reference's per-head bmm does: a dense product would meet the structural zeros with a non-finite
+        value of ANOTHER head (0 x NaN)."""
+        off = torch.ones_like(BDv, dtype=torch.bool)
+        for h in range(NH):
+            off[h * DP:(h + 1) * DP, h * dv:(h + 1) * dv] = False
+        assert bool((BDv[off] == 0).all()), 'BDv must be block diagonal'
+        return [BDv[h * DP:(h + 1) * DP, h * dv:(h + 1) * dv] for h in range(NH)]
+
+    @staticmethod
     def _head_pos(d, DP, dev):
         k = torch.arange(d, device=dev)
         return (k // (d // 4)) * (DP // 4) + k % (d // 4)
@@ -300,7 +323,8 @@ class EmuKernels:
         B, NH, DP = z.shape
         NO = BDv.size(1)
         asum = attn.sum(2)
-        out = z.reshape(B, NH * DP) @ BDv + bv * asum.repeat_interleave(NO // NH, 1)
+        dv = NO // NH
+        out = torch.cat([z[:, h] @ blk for h, blk in enumerate(self._head_blocks(BDv, NH, DP, dv))], 1) + bv * asum.repeat_interleave(dv, 1)
         outd = out * self._pool_keep(out.shape, p_pool, seed_pool, out)
         Z = K3[:, 0][:, self._head_pos(d, DP, z.device)]
         cat = torch.cat([outd, sent, Z], 1)
@@ -320,7 +344,8 @@ class EmuKernels:
         dout = dcat[:, :NO] * k1
         dZ = torch.zeros(B, DP, dtype=out.dtype, device=out.device)
         dZ[:, pos] = dcat[:, NO + Ds:]
-        dz = (dout @ BDv.t()).reshape(B, NH, DP)
+        dv = NO // NH
+        dz = torch.stack([dout[:, h * dv:(h + 1) * dv] @ blk.t() for h, blk in enumerate(self._head_blocks(BDv, NH, DP, dv))], 1)
         dasum = (dout * bv).reshape(B, NH, NO // NH).sum(2)
         part = torch.zeros(B, (L + NO + 1 + 3) // 4 * 4, dtype=out.dtype, device=out.device)
         part[:, :L] = dl * cat * k2

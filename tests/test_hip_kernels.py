@@ -1544,3 +1544,8 @@ def test_native_stack_in_the_three_mfma_form(name, monkeypatch):
                 assert w[l, AM_H1].item() == 0
             for j in (AM_DOUT, AM_DH1, AM_DKMQ):
                 assert np.isfinite(_word_f(w[l, j])) and (w[l, j].item() != 0 or DP != 208), (l, j)
+
+
+if os.environ.get('QAGNN_VARIANT_CHILD'):
+    # the pinned-family child run of test_gemm_kernel_families (-k test_gemm_tn, this file only) takes the non-finite TN tests too
+    from test_nonfinite import test_gemm_tn_nonfinite, test_gemm_tn_nonfinite_two_operands  # noqa: E402,F401

@@ -455,6 +455,17 @@ def test_dropout_parity_harness_on_cpu():
             helpers.hip_keep_masks = orig
 
 
+@pytest.mark.parametrize('train', [True, False])
+@pytest.mark.parametrize('poison', ['weight', 'embedding', 'score'])
+def test_nonfinite_module_harness_on_cpu(poison, train):
+    """The non-finite module harness of tests/test_nonfinite.py (equal non-finite logit sets against the oracle, finite logits at FWD, no
+    oracle gradient with a non-finite value that is finite here) with the torch emulation: checks the harness and the host logic --
+    the package must not launder a NaN between its kernels either."""
+    import test_nonfinite as T
+    bad, _ = T.module_vs_oracle(poison, train, device='cpu')
+    assert bad == (set(range(12)) if train else T.MODULE_POISONS[poison])
+
+
 @pytest.mark.parametrize('variant', ['default', 'dropout'])
 def test_bench_size_harness_on_cpu(variant, monkeypatch):
     """The bench-size harness of tests/test_hip_parity.py (the candidate's ReLU masks replayed on the oracle inside the kink band and
