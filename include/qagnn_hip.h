@@ -16,6 +16,10 @@
  *   - "head-padded" node rows: a feature row of d = H*dh floats is stored as H groups of HP = roundup4(dh) floats
  *     (pads are zero), DP = H*HP floats per row (d=200,H=4: HP=52, DP=208 -> 832-byte rows, 16-byte aligned heads).
  *     H must be 4 (the reference hard-codes head_count=4, modeling_qagnn.py:387) and dh <= 64.
+ *   - row pitches (lda*, ldb*, ldn*, ldc, ldt, ldx*, ld, ldk, lde, ldg, lddk, ldh, ldp, ld_sub): in floats, a multiple of 4, every row
+ *     16-byte aligned, and EVERY PITCH >= THE WIDTH IT STRIDES; a pitch below its width is QAGNN_EINVAL before anything is launched.  A
+ *     pitch above the width is a view into a larger buffer: no entry point reads or writes a float outside the rows x width it was
+ *     given -- neither the margins between the rows nor anything behind the last row (held by tests/test_pitched_operands.py).
  *
  * Non-finite values (NaN, +inf, -inf in fp32 data; index arrays are never non-finite) -- held by tests/test_nonfinite.py
  *   - For every entry point that takes fp32 data, the SET of non-finite output elements equals that of the float64
@@ -145,7 +149,10 @@ int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const int32_t* blob
  * NN:  C[M][ldc] (+)= [A1 | A2][M][K1+K2] * [B1 ; B2][K1+K2][No]  + bias[No] + rowtab[rowidx[m]][No]
  *      optional A prologue  a <- max(0, a*a_scale[k] + a_shift[k])   (BatchNorm+ReLU folded into the operand load)
  * TN:  C[Ka][ldc] (+)= A[R][Ka]^T * B[R][No]      (weight gradients; split over rows, deterministic two-stage sum)
- * Constraints: K1, K2, Ka multiples of 16... see each function; all row pitches multiples of 4 floats, 16-byte aligned.
+ * Constraints: K1, K2, Ka multiples of 16... see each function; all row pitches multiples of 4 floats, 16-byte aligned, and
+ * lda1 >= K1, lda2 >= K2, ldb1 / ldb2 >= No ([K][ldb] layout; ldn1 >= K1, ldn2 >= K2 for the [No][ldn] layout), ldc >= No, ldt >= No;
+ * TN: lda >= Ka, ldb >= No, ldc >= No.  Every kernel family takes every such pitch: no route declines one (where a route has a 2 GB
+ * operand limit, it counts rows x pitch).
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct qagnn_gemm_nn_args {
   const float* A1; int32_t lda1; int32_t K1; const float* B1; int32_t ldb1;
@@ -263,7 +270,7 @@ int qagnn_gemm_tn_colsum_f32(const float* A, int32_t lda, const float* B, int32_
  *   mode 1: out[c]    = sum_r (X[r][c] - mean[c])^2               (two-pass variance)
  *   mode 2: out[0][c] = sum_r dY[r][c],  out[1][c] = sum_r dY[r][c] * (H[r][c]-mean[c])*invstd[c]
  *           with dY = dR * [H*scale+shift > 0]   (BatchNorm+ReLU backward reductions; X = dR, X2 = H)
- * workspace: qagnn_colreduce_workspace_elems floats.
+ * workspace: qagnn_colreduce_workspace_elems floats.  ldx >= Cc, ldx2 >= Cc (mode 2); `out` is [groups or 1 or 2][Cc], contiguous.
  * ------------------------------------------------------------------------------------------------------------ */
 int64_t qagnn_colreduce_workspace_elems(int32_t R, int32_t Cc, int32_t groups);
 int qagnn_colreduce_f32(int32_t mode, const float* X, int32_t ldx, const float* X2, int32_t ldx2, int32_t R, int32_t Cc,
@@ -276,6 +283,7 @@ int qagnn_colreduce_f32(int32_t mode, const float* X, int32_t ldx, const float* 
  * Elementwise kernels.
  *   bn_relu_bwd:  dH = gscale[c] * (dY - c1[c] - hhat*c2[c]),  dY = dR*[H*scale+shift>0], hhat=(H-mean)*invstd
  *                 (train: c1 = mean(dY), c2 = mean(dY*hhat); eval: c1 = c2 = 0)       -- BatchNorm1d backward, :408
+ *                 dR, Hh and dH share the ONE row pitch ld >= Cc
  *   gelu_dropout: Y = gelu_tanh(X) * keep/(1-p)     (utils/layers.py:10-14 + F.dropout, modeling_qagnn.py:48-49,92-93)
  *                 keep is a counter-based hash of (seed, element index); backward regenerates it.
  *   sin_basis:    out[r][j] = sin(js[j] * score[r])  for j < J, 0 for J <= j < ldo   (modeling_qagnn.py:70-72)
@@ -315,6 +323,8 @@ int qagnn_pool_attn_bwd_f32(const float* u, const float* K, int32_t ldk, int32_t
  * Backward: dz [B][NH][DP], dattn [B][NH][n] (the gradient through sum_l attn), dout [B][NH*dv] (dBDv = z^T dout), dsent [B][Ds] or
  * NULL, dZ [B][DP] (padded, to be added to row 0 of the pooling's dK: qagnn_add_row0_f32), and part [B][ldp >= L + NH*dv + 1], L = NH*dv + Ds + d:
  * per subgraph the addends of d w_fc | d bv | d b_fc, whose column sums are those gradients.
+ * ldh (the distance between the rows 0 of consecutive subgraphs, n * the row pitch of the GNN output) >= DP; ldp at most 255 floats above
+ * its minimum: one pass of the 256-thread workgroup zeroes the extra columns.
  * QAGNN_EUNSUPPORTED outside NH <= 4, NH*dv <= 256, DP <= 256. */
 int qagnn_head_post_fwd_f32(const float* z, const float* attn, const float* BDv, const float* bv, const float* sent, const float* H, int64_t ldh,
                             const float* w_fc, const float* b_fc, int32_t B, int32_t NH, int32_t DP, int32_t dv, int32_t n, int32_t Ds, int32_t d,
@@ -323,9 +333,10 @@ int qagnn_head_post_fwd_f32(const float* z, const float* attn, const float* BDv,
 int qagnn_head_post_bwd_f32(const float* dlogits, const float* out, const float* asum, const float* BDv, const float* bv, const float* sent,
                             const float* H, int64_t ldh, const float* w_fc, int32_t B, int32_t NH, int32_t DP, int32_t dv, int32_t n, int32_t Ds,
                             int32_t d, float p_pool, float p_fc, uint64_t seed_pool, uint64_t seed_fc, float* dz, float* dattn, float* dout,
-                            float* dsent, float* dZ, float* part, int32_t ldp /* row pitch of part, >= L + NH*dv + 1; extra columns are zeroed */,
+                            float* dsent, float* dZ, float* part, int32_t ldp /* row pitch of part, in [L + NH*dv + 1, L + NH*dv + 256]; extra columns are zeroed */,
                             qagnn_stream_t stream);
-/* dK[b*ld_sub + j] += dZ[b*Cc + j]: the gradient of each subgraph's row 0 that the head reads directly, into the pooling's dK */
+/* dK[b*ld_sub + j] += dZ[b*Cc + j]: the gradient of each subgraph's row 0 that the head reads directly, into the pooling's dK
+ * (ld_sub = n * lddk, the distance between the rows 0 of consecutive subgraphs, >= Cc) */
 int qagnn_add_row0_f32(float* dK, int64_t ld_sub, const float* dZ, int32_t B, int32_t Cc, qagnn_stream_t stream);
 /* Weight packing of the module mirror (qagnn_amd.ops.GatherPlan; no reference counterpart: the reference multiplies by nn.Linear weights
  * in place, the kernels of this library want them transposed / head-padded / concatenated).  qagnn_gather_multi_f32: out[i] =
@@ -395,8 +406,9 @@ int qagnn_seed_epoch_set(uint64_t value, qagnn_stream_t stream);
  *   a_eh = softmax over the out-edges of src (eps 1e-16),  alpha_eh = deg(src) * a_eh
  *   aggr[tgt] += alpha_eh * msg_e
  * forward writes a[Ep][4], alpha[Ep][4] (source order) and aggr[N][DP]; `score` is scratch [Ep][4].
- * backward takes G = d aggr [N][DP] and writes dKMQ [N][3*DP], dEkEm [C][2*DP]; scratch: ga[Ep][4] (becomes gs),
- * rs[N][4], cls_part[max_chunks + QAGNN_CLS_SLICES*C][2*DP].
+ * backward takes G = d aggr [N][DP] (row pitch ldg) and writes dKMQ [N][3*DP] WITH THE ROW PITCH OF KMQ (ldk) and dEkEm [C][2*DP] WITH
+ * THE ROW PITCH OF EkEm (lde): the gradients are laid out like the operands they belong to.  scratch: ga[Ep][4] (becomes gs),
+ * rs[N][4], cls_part[max_chunks + QAGNN_CLS_SLICES*C][2*DP] (contiguous).  ldk >= 3*DP, lde >= 2*DP, lda >= DP, ldg >= DP.
  * ------------------------------------------------------------------------------------------------------------ */
 int qagnn_edge_attn_fwd_f32(const qagnn_graph* g, const float* KMQ, int32_t ldk, const float* EkEm, int32_t lde, int32_t HP,
                             float qscale, float* score, float* a, float* alpha, float* aggr, int32_t lda,

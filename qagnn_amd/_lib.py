@@ -185,6 +185,36 @@ def _chk2d(t, name, dtype=torch.float32):
     return t
 
 
+def _chkp(t, name):
+    """A 2-D fp32 operand of an entry point that takes a row pitch (include/qagnn_hip.h): contiguous, or a view whose rows are contiguous,
+    at least their width apart, a multiple of 4 floats apart and 16-byte aligned.  (The natively sequenced hops take no pitches: their
+    operands stay with _chk2d.)"""
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2, f'{name}: need a 2-D float32 device tensor, got {tuple(t.shape)} {t.dtype} {t.device}'
+    assert t.is_contiguous() or (t.stride(1) == 1 and (t.size(0) == 1 or (t.stride(0) >= t.size(1) and t.stride(0) % 4 == 0)) and t.data_ptr() % 16 == 0), \
+        f'{name}: rows must be contiguous, a multiple of 4 floats (and at least their width) apart and 16-byte aligned; got strides {t.stride()} for {tuple(t.shape)}'
+    return t
+
+
+def _ld(t):
+    """the row pitch handed to the library for a 2-D operand (a one-row tensor's stride(0) is arbitrary: its width)"""
+    return t.size(1) if t.size(0) == 1 else t.stride(0)
+
+
+def _chkp3(t, name):
+    """[B, n, Cc] node rows of the pooling head, i.e. [B * n, ld] with one row pitch ld = _ld3(t) >= Cc"""
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3, f'{name}: need a 3-D float32 device tensor'
+    B, n, Cc = t.shape
+    ld = _ld3(t)
+    assert t.is_contiguous() or (t.stride(2) == 1 and ld >= Cc and ld % 4 == 0 and (B == 1 or t.stride(0) == n * ld) and t.data_ptr() % 16 == 0), \
+        f'{name}: need [B, n, Cc] rows with one pitch (a multiple of 4 floats, >= Cc), 16-byte aligned; got strides {t.stride()} for {tuple(t.shape)}'
+    return t
+
+
+def _ld3(t):
+    B, n, Cc = t.shape
+    return t.stride(1) if n > 1 else (t.stride(0) if B > 1 else Cc)
+
+
 VALIDATE = os.environ.get('QAGNN_VALIDATE', '0') == '1'  # synchronous input validation (debugging corrupt batches)
 
 
@@ -500,12 +530,12 @@ class HipKernels(metaclass=_GuardedMeta):
         for d, pr in zip(descs, pairs):
             b1, b2 = pr[0], pr[1]
             d.pieces = pr[2] if len(pr) > 2 else 3  # (b1, b2, 2): the two scaled fp16 images of the three-MFMA form
-            _chk2d(b1, 'B1n')
-            d.B1n, d.ldn1, d.K1, d.No = b1.data_ptr(), b1.size(1), b1.size(1), b1.size(0)
+            _chkp(b1, 'B1n')
+            d.B1n, d.ldn1, d.K1, d.No = b1.data_ptr(), _ld(b1), b1.size(1), b1.size(0)
             if b2 is not None:
-                _chk2d(b2, 'B2n')
+                _chkp(b2, 'B2n')
                 assert b2.size(0) == b1.size(0)
-                d.B2n, d.ldn2, d.K2 = b2.data_ptr(), b2.size(1), b2.size(1)
+                d.B2n, d.ldn2, d.K2 = b2.data_ptr(), _ld(b2), b2.size(1)
         nbytes = self.lib.qagnn_gemm_nn_prepack_bytes(descs, len(pairs))
         out = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=pairs[0][0].device)
         self._check(self.lib.qagnn_gemm_nn_prepack_f32(descs, len(pairs), out.data_ptr(), out.numel(), int(tag), self._stream()),
@@ -523,31 +553,31 @@ class HipKernels(metaclass=_GuardedMeta):
         cores by exact operand splitting (see gemm_split.hip), else on the fp32-input MFMAs.
         colstats=True (only where colstats_supported()): returns (C, part) with part [ceil(M/128), 3, No] = per 128-row tile x0 | S1 | S2
         of C's columns, for bn_stats_finalize."""
-        _chk2d(A1, 'A1'), _chk2d(B1, 'B1')
+        _chkp(A1, 'A1'), _chkp(B1, 'B1')
         K1 = A1.size(1)
         M = A1.size(0) if a_rowidx is None else a_rowidx.numel()
         No = B1.size(1)
         assert B1.size(0) == K1
         a = qagnn_gemm_nn_args()
-        a.A1, a.lda1, a.K1, a.B1, a.ldb1 = A1.data_ptr(), K1, K1, B1.data_ptr(), No
+        a.A1, a.lda1, a.K1, a.B1, a.ldb1 = A1.data_ptr(), _ld(A1), K1, B1.data_ptr(), _ld(B1)
         if A2 is not None:
-            _chk2d(A2, 'A2'), _chk2d(B2, 'B2')
+            _chkp(A2, 'A2'), _chkp(B2, 'B2')
             assert A2.size(0) == M and B2.shape == (A2.size(1), No)
-            a.A2, a.lda2, a.K2, a.B2, a.ldb2 = A2.data_ptr(), A2.size(1), A2.size(1), B2.data_ptr(), No
+            a.A2, a.lda2, a.K2, a.B2, a.ldb2 = A2.data_ptr(), _ld(A2), A2.size(1), B2.data_ptr(), _ld(B2)
         if out is None:
             assert not accumulate
             out = torch.empty((M, No), dtype=torch.float32, device=A1.device)
         else:
-            _chk2d(out, 'out')
+            _chkp(out, 'out')
             assert out.shape == (M, No)
-        a.C, a.ldc, a.M, a.No = out.data_ptr(), No, M, No
+        a.C, a.ldc, a.M, a.No = out.data_ptr(), _ld(out), M, No
         if bias is not None:
             assert bias.is_contiguous() and bias.numel() == No and bias.dtype == torch.float32
             a.bias = bias.data_ptr()
         if rowtab is not None:
-            _chk2d(rowtab, 'rowtab')
+            _chkp(rowtab, 'rowtab')
             assert rowtab.size(1) == No and rowidx.dtype == torch.long and rowidx.numel() == M and rowidx.is_contiguous()
-            a.rowtab, a.ldt, a.rowidx = rowtab.data_ptr(), No, rowidx.data_ptr()
+            a.rowtab, a.ldt, a.rowidx = rowtab.data_ptr(), _ld(rowtab), rowidx.data_ptr()
         if a_scale is not None:
             assert a_scale.numel() == K1 and a_shift.numel() == K1 and a_scale.is_contiguous() and a_shift.is_contiguous()
             a.a_scale, a.a_shift = a_scale.data_ptr(), a_shift.data_ptr()
@@ -567,23 +597,23 @@ class HipKernels(metaclass=_GuardedMeta):
             part = torch.empty((-(-M // self.STAT_TILE), 3, No), dtype=torch.float32, device=A1.device)
             a.colstat_part = part.data_ptr()
         if self.gemm_split and B1n is not None and (A2 is None or B2n is not None) and K1 % 4 == 0 and (A2 is None or A2.size(1) % 4 == 0):
-            _chk2d(B1n, 'B1n')
+            _chkp(B1n, 'B1n')
             assert B1n.shape == (No, K1)
-            n2, ld2 = None, 0
+            n2, ld1, ld2 = None, _ld(B1n), 0
             if A2 is not None:
-                _chk2d(B2n, 'B2n')
+                _chkp(B2n, 'B2n')
                 assert B2n.shape == (No, A2.size(1))
-                n2, ld2 = B2n.data_ptr(), B2n.size(1)
+                n2, ld2 = B2n.data_ptr(), _ld(B2n)
             # large products whose B is not registered (qagnn_gemm_nn_prepack_f32): B is split ONCE into the kernel's LDS image order
             # (scratch from the caching allocator, stream-ordered: the next product may reuse it), every row tile then streams it by DMA
             # instead of repeating the split.  The library says whether this very call would use the scratch (0: pre-packed / not taken)
-            ws_bytes = self.lib.qagnn_gemm_nn_ws_bytes(C.byref(a), B1n.data_ptr(), K1, n2, ld2) if M >= self.PACK_MIN_M else 0
+            ws_bytes = self.lib.qagnn_gemm_nn_ws_bytes(C.byref(a), B1n.data_ptr(), ld1, n2, ld2) if M >= self.PACK_MIN_M else 0
             if ws_bytes > 0:
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A1.device)
-                self._check(self.lib.qagnn_gemm_nn_split_ws_f32(C.byref(a), B1n.data_ptr(), K1, n2, ld2, ws.data_ptr(), ws_bytes, self._stream()),
+                self._check(self.lib.qagnn_gemm_nn_split_ws_f32(C.byref(a), B1n.data_ptr(), ld1, n2, ld2, ws.data_ptr(), ws_bytes, self._stream()),
                             'qagnn_gemm_nn_split_ws_f32')
             else:
-                self._check(self.lib.qagnn_gemm_nn_split_f32(C.byref(a), B1n.data_ptr(), K1, n2, ld2, self._stream()), 'qagnn_gemm_nn_split_f32')
+                self._check(self.lib.qagnn_gemm_nn_split_f32(C.byref(a), B1n.data_ptr(), ld1, n2, ld2, self._stream()), 'qagnn_gemm_nn_split_f32')
             return (out, part) if colstats else out
         assert K1 % 16 == 0 and (A2 is None or A2.size(1) % 16 == 0), 'the fp32-MFMA kernel needs K to be a multiple of 16'
         self._check(self.lib.qagnn_gemm_nn_f32(C.byref(a), self._stream()), 'qagnn_gemm_nn_f32')
@@ -594,14 +624,14 @@ class HipKernels(metaclass=_GuardedMeta):
         if out is None:
             out = torch.empty((Ka, No), dtype=torch.float32, device=dev)
         else:
-            _chk2d(out, 'out')
+            _chkp(out, 'out')
             assert out.shape == (Ka, No)
         return out, torch.empty(self.lib.qagnn_gemm_tn_workspace_elems(R, Ka, No), dtype=torch.float32, device=dev)
 
     def gemm_tn(self, A, B, a_scale=None, a_shift=None, out=None, accumulate=False, a_rowidx=None, colsum_groups=0,
                 b_rowidx=None):
         """C = A^T B.  colsum_groups = G > 0 additionally returns bsum [G, No] = per-group column sums of B."""
-        _chk2d(A, 'A'), _chk2d(B, 'B')
+        _chkp(A, 'A'), _chkp(B, 'B')
         Ka = A.size(1)
         R, No = B.shape
         assert (A.size(0) == R) if a_rowidx is None else (a_rowidx.numel() == R and a_rowidx.dtype == torch.long)
@@ -611,7 +641,7 @@ class HipKernels(metaclass=_GuardedMeta):
         if colsum_groups:
             assert b_rowidx is None or (b_rowidx.dtype == torch.long and b_rowidx.numel() == R and b_rowidx.is_contiguous())
             bsum = torch.empty((colsum_groups, No), dtype=torch.float32, device=A.device)
-        rc = self.lib.qagnn_gemm_tn_colsum_f32(A.data_ptr(), Ka, B.data_ptr(), No, out.data_ptr(), No, R, Ka, No, _ptr(a_scale),
+        rc = self.lib.qagnn_gemm_tn_colsum_f32(A.data_ptr(), _ld(A), B.data_ptr(), _ld(B), out.data_ptr(), _ld(out), R, Ka, No, _ptr(a_scale),
                                                _ptr(a_shift), _ptr(a_rowidx), 1 if accumulate else 0, _ptr(bsum), _ptr(b_rowidx),
                                                colsum_groups, ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_gemm_tn_colsum_f32')
@@ -628,38 +658,40 @@ class HipKernels(metaclass=_GuardedMeta):
 
     def gemm_tn_h2(self, A1, B, amax_a1, amax_b, A2=None, amax_a2=None, a_scale=None, a_shift=None, out=None):
         """[A1 | A2]^T B in the three-MFMA form (qagnn_gemm_tn_h2_f32); amax_*: absmax() words (amax_a1 AFTER the scale / shift prologue)"""
-        _chk2d(A1, 'A1'), _chk2d(B, 'B')
+        _chkp(A1, 'A1'), _chkp(B, 'B')
+        if A2 is not None:
+            _chkp(A2, 'A2')
         Ka1, Ka2 = A1.size(1), (A2.size(1) if A2 is not None else 0)
         R, No = B.shape
         out, ws = self._tn_out_ws(R, Ka1 + Ka2, No, out, B.device)
         fn = self.lib.qagnn_gemm_tn_h1_f32 if self.gemm_split == 3 else self.lib.qagnn_gemm_tn_h2_f32
-        rc = fn(A1.data_ptr(), Ka1, Ka1, _ptr(A2), Ka2, Ka2, B.data_ptr(), No, out.data_ptr(), No, R, No, _ptr(a_scale),
+        rc = fn(A1.data_ptr(), _ld(A1), Ka1, _ptr(A2), _ld(A2) if A2 is not None else 0, Ka2, B.data_ptr(), _ld(B), out.data_ptr(), _ld(out), R, No, _ptr(a_scale),
                                            _ptr(a_shift), amax_a1.data_ptr(), _ptr(amax_a2), amax_b.data_ptr(), ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_gemm_tn_h2_f32')
         return out
 
     def gemm_tn2(self, A1, A2, B, out=None):
         """[A1 | A2]^T B -> [Ka1 + Ka2, No]: two weight gradients that share their B operand, one launch (qagnn_gemm_tn2_f32)."""
-        _chk2d(A1, 'A1'), _chk2d(A2, 'A2'), _chk2d(B, 'B')
+        _chkp(A1, 'A1'), _chkp(A2, 'A2'), _chkp(B, 'B')
         Ka1, Ka2 = A1.size(1), A2.size(1)
         R, No = B.shape
         assert A1.size(0) == R and A2.size(0) == R
         out, ws = self._tn_out_ws(R, Ka1 + Ka2, No, out, B.device)
-        rc = self.lib.qagnn_gemm_tn2_f32(A1.data_ptr(), Ka1, Ka1, A2.data_ptr(), Ka2, Ka2, B.data_ptr(), No, out.data_ptr(), No, R, No,
+        rc = self.lib.qagnn_gemm_tn2_f32(A1.data_ptr(), _ld(A1), Ka1, A2.data_ptr(), _ld(A2), Ka2, B.data_ptr(), _ld(B), out.data_ptr(), _ld(out), R, No,
                                          ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_gemm_tn2_f32')
         return out
 
     # -- reductions / elementwise ----------------------------------------------------------------------------------
     def _colreduce(self, mode, X, X2, rowidx, groups, mean, invstd, scale, shift, nout, out_scale=1.0, roww=None, out=None):
-        _chk2d(X, 'X')
+        _chkp(X, 'X')
         R, Cc = X.shape
         if out is None:
             out = torch.empty((nout, Cc), dtype=torch.float32, device=X.device)
         else:
             assert out.shape == (nout, Cc) and out.is_contiguous() and out.dtype == torch.float32
         ws = torch.empty(self.lib.qagnn_colreduce_workspace_elems(R, Cc, groups), dtype=torch.float32, device=X.device)
-        rc = self.lib.qagnn_colreduce_f32(mode, X.data_ptr(), Cc, _ptr(X2), Cc, R, Cc, _ptr(rowidx), groups, _ptr(mean),
+        rc = self.lib.qagnn_colreduce_f32(mode, X.data_ptr(), _ld(X), _ptr(X2), _ld(X2) if X2 is not None else Cc, R, Cc, _ptr(rowidx), groups, _ptr(mean),
                                           _ptr(invstd), _ptr(scale), _ptr(shift), _ptr(roww), float(out_scale), out.data_ptr(), ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_colreduce_f32')
         return out
@@ -694,17 +726,29 @@ class HipKernels(metaclass=_GuardedMeta):
         return stats
 
     def bn_bwd_reduce(self, dR, H, mean, invstd, scale, shift):
-        _chk2d(H, 'H')
+        _chkp(H, 'H')
+        assert H.shape == dR.shape
         return self._colreduce(2, dR, H, None, 1, mean, invstd, scale, shift, 2)
 
-    def bn_relu_bwd(self, dR, H, mean, invstd, scale, shift, gamma, red, inv_rows, roww=None):
+    @staticmethod
+    def _bn_bwd_operands(dR, H, dH):
+        """dR, H and dH [R, Cc] share ONE row pitch (the entry points take a single ld) -> (dH, ld); dH=None: a fresh contiguous one,
+        which asks dR and H to be contiguous too"""
+        _chkp(dR, 'dR'), _chkp(H, 'H')
+        if dH is None:
+            dH = torch.empty(H.shape, dtype=torch.float32, device=H.device)
+        _chkp(dH, 'dH')
+        assert dR.shape == H.shape == dH.shape and _ld(dR) == _ld(H) == _ld(dH), \
+            f'bn_relu_bwd: dR, H and dH share one row pitch, got {_ld(dR)}, {_ld(H)}, {_ld(dH)}'
+        return dH, _ld(H)
+
+    def bn_relu_bwd(self, dR, H, mean, invstd, scale, shift, gamma, red, inv_rows, roww=None, dH=None):
         """red = bn_bwd_reduce(...) [2, Cc]; inv_rows = 1/R (batch statistics) or 0 (running statistics); roww [R]: the
-        per-row statistics weights when they were not uniform."""
+        per-row statistics weights when they were not uniform.  dH: the output, a view with the pitch of dR and H (else allocated)."""
         assert red.is_contiguous() and red.shape == (2, H.size(1))
-        _chk2d(dR, 'dR'), _chk2d(H, 'H')
+        dH, ld = self._bn_bwd_operands(dR, H, dH)
         R, Cc = H.shape
-        dH = torch.empty_like(H)
-        rc = self.lib.qagnn_bn_relu_bwd_f32(dR.data_ptr(), H.data_ptr(), dH.data_ptr(), Cc, R, Cc, mean.data_ptr(),
+        rc = self.lib.qagnn_bn_relu_bwd_f32(dR.data_ptr(), H.data_ptr(), dH.data_ptr(), ld, R, Cc, mean.data_ptr(),
                                             invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), gamma.data_ptr(),
                                             red[0].data_ptr(), red[1].data_ptr(), float(inv_rows), _ptr(roww), self._stream())
         self._check(rc, 'qagnn_bn_relu_bwd_f32')
@@ -713,27 +757,32 @@ class HipKernels(metaclass=_GuardedMeta):
     POOL_LIMITS = (4, 256, 1024)  # heads, row width, nodes per subgraph
 
     def pool_attn_fwd(self, u, cvec, K, mask, inv_temp, p, seed):
-        """u [B, NH, Cc], cvec [B, NH], K [B, n, Cc] (contiguous rows), mask [B, n] bool -> attn, attn_d [B, NH, n], z [B, NH, Cc]."""
+        """u [B, NH, Cc], cvec [B, NH], K [B, n, Cc] (rows with one pitch >= Cc), mask [B, n] bool -> attn, attn_d [B, NH, n], z [B, NH, Cc]."""
         B, NH, Cc = u.shape
         n = K.size(1)
-        assert u.is_contiguous() and cvec.is_contiguous() and K.is_contiguous() and mask.is_contiguous() and mask.dtype == torch.bool
+        assert u.is_contiguous() and cvec.is_contiguous() and mask.is_contiguous() and mask.dtype == torch.bool
+        _chkp3(K, 'K')
         attn = torch.empty((2, B, NH, n), dtype=torch.float32, device=u.device)
         z = torch.empty((B, NH, Cc), dtype=torch.float32, device=u.device)
-        rc = self.lib.qagnn_pool_attn_fwd_f32(u.data_ptr(), cvec.data_ptr(), K.data_ptr(), K.size(2), mask.data_ptr(), B, n, NH, Cc,
+        rc = self.lib.qagnn_pool_attn_fwd_f32(u.data_ptr(), cvec.data_ptr(), K.data_ptr(), _ld3(K), mask.data_ptr(), B, n, NH, Cc,
                                               float(inv_temp), float(p), int(seed), attn[0].data_ptr(), attn[1].data_ptr(),
                                               z.data_ptr(), self._stream())
         self._check(rc, 'qagnn_pool_attn_fwd_f32')
         return attn[0], attn[1], z
 
-    def pool_attn_bwd(self, u, K, inv_temp, p, seed, attn, attn_d, dz, dattn_d):
+    def pool_attn_bwd(self, u, K, inv_temp, p, seed, attn, attn_d, dz, dattn_d, dK=None):
+        """dK: the [B, n, Cc] output, rows with a pitch of its own (else a contiguous one is allocated)"""
         B, NH, Cc = u.shape
         n = K.size(1)
         assert dz.is_contiguous() and attn.is_contiguous() and attn_d.is_contiguous() and (dattn_d is None or dattn_d.is_contiguous())
-        dK = torch.empty_like(K)
+        _chkp3(K, 'K')
+        if dK is None:
+            dK = torch.empty(K.shape, dtype=torch.float32, device=K.device)
+        assert _chkp3(dK, 'dK').shape == K.shape
         du = torch.empty_like(u)
         dc = torch.empty((B, NH), dtype=torch.float32, device=u.device)
-        rc = self.lib.qagnn_pool_attn_bwd_f32(u.data_ptr(), K.data_ptr(), K.size(2), B, n, NH, Cc, float(inv_temp), float(p), int(seed),
-                                              attn.data_ptr(), attn_d.data_ptr(), dz.data_ptr(), _ptr(dattn_d), dK.data_ptr(), K.size(2), du.data_ptr(),
+        rc = self.lib.qagnn_pool_attn_bwd_f32(u.data_ptr(), K.data_ptr(), _ld3(K), B, n, NH, Cc, float(inv_temp), float(p), int(seed),
+                                              attn.data_ptr(), attn_d.data_ptr(), dz.data_ptr(), _ptr(dattn_d), dK.data_ptr(), _ld3(dK), du.data_ptr(),
                                               dc.data_ptr(), self._stream())
         self._check(rc, 'qagnn_pool_attn_bwd_f32')
         return dK, du, dc
@@ -745,32 +794,40 @@ class HipKernels(metaclass=_GuardedMeta):
         subgraph is read), w_fc [NH*dv + Ds + d], b_fc [1] -> logits [B], out [B, NH*dv] (before dropout), asum [B, NH]."""
         B, NH, DP = z.shape
         n, NO, Ds = attn.size(2), BDv.size(1), sent.size(1)
-        for t in (z, attn, BDv, bv, sent, K3, w_fc, b_fc):
+        for t in (z, attn, BDv, bv, sent, w_fc, b_fc):
             assert t.is_contiguous() and t.dtype == torch.float32
-        assert K3.shape == (B, n, DP) and BDv.size(0) == NH * DP and NO % NH == 0 and w_fc.numel() == NO + Ds + d and sent.size(0) == B
+        assert _chkp3(K3, 'K3').shape == (B, n, DP) and BDv.size(0) == NH * DP and NO % NH == 0 and w_fc.numel() == NO + Ds + d and sent.size(0) == B
         out = torch.empty((B, NO), dtype=torch.float32, device=z.device)
         asum = torch.empty((B, NH), dtype=torch.float32, device=z.device)
         logits = torch.empty((B,), dtype=torch.float32, device=z.device)
-        rc = self.lib.qagnn_head_post_fwd_f32(z.data_ptr(), attn.data_ptr(), BDv.data_ptr(), bv.data_ptr(), sent.data_ptr(), K3.data_ptr(), n * DP,
+        rc = self.lib.qagnn_head_post_fwd_f32(z.data_ptr(), attn.data_ptr(), BDv.data_ptr(), bv.data_ptr(), sent.data_ptr(), K3.data_ptr(), n * _ld3(K3),
                                               w_fc.data_ptr(), b_fc.data_ptr(), B, NH, DP, NO // NH, n, Ds, d, float(p_pool), float(p_fc),
                                               int(seed_pool), int(seed_fc), out.data_ptr(), asum.data_ptr(), logits.data_ptr(), self._stream())
         self._check(rc, 'qagnn_head_post_fwd_f32')
         return logits, out, asum
 
-    def head_post_bwd(self, dlogits, out, asum, BDv, bv, sent, K3, d, w_fc, p_pool, p_fc, seed_pool, seed_fc, n, need_dsent):
-        """-> dz [B, NH, DP], dattn [B, NH, n], dout [B, NH*dv], dsent [B, Ds] or None, dZ [B, DP], part [B, L + NH*dv + 1]"""
+    def head_post_bwd(self, dlogits, out, asum, BDv, bv, sent, K3, d, w_fc, p_pool, p_fc, seed_pool, seed_fc, n, need_dsent, ldp=None, part=None):
+        """-> dz [B, NH, DP], dattn [B, NH, n], dout [B, NH*dv], dsent [B, Ds] or None, dZ [B, DP], part [B, ldp] (L + NH*dv + 1 <= ldp <=
+        L + NH*dv + 1 + 255, a multiple of 4; default the smallest: the columns past L + NH*dv + 1 are zero, and one pass of the kernel's
+        256 threads zeroes them, hence the upper limit).  part: the caller's [B, ldp] buffer (every column of its rows is written)"""
         B, NO = out.shape
         NH, DP, Ds = asum.size(1), K3.size(2), sent.size(1)
         assert dlogits.is_contiguous() and dlogits.numel() == B
+        _chkp3(K3, 'K3')
+        ldp_min = (NO + Ds + d + NO + 1 + 3) // 4 * 4  # (pitch: a multiple of 4 for the column sums)
+        ldp = (ldp_min if part is None else part.size(1)) if ldp is None else int(ldp)
+        assert ldp_min <= ldp <= NO + Ds + d + NO + 1 + 255 and ldp % 4 == 0, f'ldp={ldp}: a multiple of 4 in [{ldp_min}, {NO + Ds + d + NO + 1 + 255}]'
         dev = out.device
         dz = torch.empty((B, NH, DP), dtype=torch.float32, device=dev)
         dattn = torch.empty((B, NH, n), dtype=torch.float32, device=dev)
         dout = torch.empty((B, NO), dtype=torch.float32, device=dev)
         dsent = torch.empty((B, Ds), dtype=torch.float32, device=dev) if need_dsent else None
         dZ = torch.empty((B, DP), dtype=torch.float32, device=dev)
-        part = torch.empty((B, (NO + Ds + d + NO + 1 + 3) // 4 * 4), dtype=torch.float32, device=dev)  # (pitch: a multiple of 4 for the column sums)
+        if part is None:
+            part = torch.empty((B, ldp), dtype=torch.float32, device=dev)
+        assert part.is_cuda and part.dtype == torch.float32 and part.shape == (B, ldp) and part.is_contiguous()
         rc = self.lib.qagnn_head_post_bwd_f32(dlogits.data_ptr(), out.data_ptr(), asum.data_ptr(), BDv.data_ptr(), bv.data_ptr(), sent.data_ptr(),
-                                              K3.data_ptr(), n * DP, w_fc.data_ptr(), B, NH, DP, NO // NH, n, Ds, d, float(p_pool), float(p_fc),
+                                              K3.data_ptr(), n * _ld3(K3), w_fc.data_ptr(), B, NH, DP, NO // NH, n, Ds, d, float(p_pool), float(p_fc),
                                               int(seed_pool), int(seed_fc), dz.data_ptr(), dattn.data_ptr(), dout.data_ptr(), _ptr(dsent),
                                               dZ.data_ptr(), part.data_ptr(), part.size(1), self._stream())
         self._check(rc, 'qagnn_head_post_bwd_f32')
@@ -808,10 +865,11 @@ class HipKernels(metaclass=_GuardedMeta):
         return out
 
     def add_row0(self, dK, dZ):
-        """dK [B, n, Cc] (contiguous): dK[:, 0, :] += dZ [B, Cc], in place."""
+        """dK [B, n, Cc] (rows with one pitch >= Cc): dK[:, 0, :] += dZ [B, Cc], in place."""
         B, n, Cc = dK.shape
-        assert dK.is_contiguous() and dZ.is_contiguous() and dZ.shape == (B, Cc)
-        self._check(self.lib.qagnn_add_row0_f32(dK.data_ptr(), n * Cc, dZ.data_ptr(), B, Cc, self._stream()), 'qagnn_add_row0_f32')
+        assert dZ.is_contiguous() and dZ.shape == (B, Cc)
+        _chkp3(dK, 'dK')
+        self._check(self.lib.qagnn_add_row0_f32(dK.data_ptr(), n * _ld3(dK), dZ.data_ptr(), B, Cc, self._stream()), 'qagnn_add_row0_f32')
         return dK
 
     def packed_min_rows(self, rows):
@@ -863,15 +921,14 @@ class HipKernels(metaclass=_GuardedMeta):
                                                         int(seed), self._stream()), 'qagnn_gelu_dropout_bwd_f32')
         return dX
 
-    def bn_relu_bwd_colsum(self, dR, H, mean, invstd, scale, shift, gamma, red, inv_rows, roww=None):
+    def bn_relu_bwd_colsum(self, dR, H, mean, invstd, scale, shift, gamma, red, inv_rows, roww=None, dH=None):
         """bn_relu_bwd that also returns colsum(dH) [Cc]."""
         assert red.is_contiguous() and red.shape == (2, H.size(1))
-        _chk2d(dR, 'dR'), _chk2d(H, 'H')
+        dH, ld = self._bn_bwd_operands(dR, H, dH)
         R, Cc = H.shape
-        dH = torch.empty_like(H)
         cs = torch.empty(Cc, dtype=torch.float32, device=H.device)
         ws = torch.empty(self.lib.qagnn_colreduce_workspace_elems(R, Cc, 1), dtype=torch.float32, device=H.device)
-        rc = self.lib.qagnn_bn_relu_bwd_colsum_f32(dR.data_ptr(), H.data_ptr(), dH.data_ptr(), Cc, R, Cc, mean.data_ptr(), invstd.data_ptr(),
+        rc = self.lib.qagnn_bn_relu_bwd_colsum_f32(dR.data_ptr(), H.data_ptr(), dH.data_ptr(), ld, R, Cc, mean.data_ptr(), invstd.data_ptr(),
                                                    scale.data_ptr(), shift.data_ptr(), gamma.data_ptr(), red[0].data_ptr(), red[1].data_ptr(),
                                                    float(inv_rows), _ptr(roww), cs.data_ptr(), ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_bn_relu_bwd_colsum_f32')
@@ -886,31 +943,41 @@ class HipKernels(metaclass=_GuardedMeta):
         return out
 
     # -- edge kernels -------------------------------------------------------------------------------------------------
-    def edge_attn_fwd(self, graph, KMQ, EkEm, HP, qscale):
-        _chk2d(KMQ, 'KMQ'), _chk2d(EkEm, 'EkEm')
+    def edge_attn_fwd(self, graph, KMQ, EkEm, HP, qscale, aggr=None):
+        """aggr: the [N, DP] output, a view with a pitch of its own (else a contiguous one is allocated)"""
+        _chkp(KMQ, 'KMQ'), _chkp(EkEm, 'EkEm')
         DP = 4 * HP
         assert KMQ.shape == (graph.N, 3 * DP) and EkEm.shape == (graph.C, 2 * DP)
         dev = KMQ.device
         a = torch.empty((graph.Ep, 4), dtype=torch.float32, device=dev)
         alpha = torch.empty_like(a)
-        aggr = torch.empty((graph.N, DP), dtype=torch.float32, device=dev)
+        if aggr is None:
+            aggr = torch.empty((graph.N, DP), dtype=torch.float32, device=dev)
+        assert _chkp(aggr, 'aggr').shape == (graph.N, DP)
         score = torch.empty_like(a)  # scratch of the generic kernels (raw scores of hub segments)
-        rc = self.lib.qagnn_edge_attn_fwd_f32(C.byref(graph.c), KMQ.data_ptr(), 3 * DP, EkEm.data_ptr(), 2 * DP, HP, float(qscale), score.data_ptr(),
-                                              a.data_ptr(), alpha.data_ptr(), aggr.data_ptr(), DP, self._stream())
+        rc = self.lib.qagnn_edge_attn_fwd_f32(C.byref(graph.c), KMQ.data_ptr(), _ld(KMQ), EkEm.data_ptr(), _ld(EkEm), HP, float(qscale), score.data_ptr(),
+                                              a.data_ptr(), alpha.data_ptr(), aggr.data_ptr(), _ld(aggr), self._stream())
         self._check(rc, 'qagnn_edge_attn_fwd_f32')
         return aggr, a, alpha
 
-    def edge_attn_bwd(self, graph, KMQ, EkEm, HP, qscale, a, alpha, G):
-        _chk2d(KMQ, 'KMQ'), _chk2d(EkEm, 'EkEm'), _chk2d(G, 'G')
+    def edge_attn_bwd(self, graph, KMQ, EkEm, HP, qscale, a, alpha, G, dKMQ=None, dEkEm=None):
+        """dKMQ / dEkEm: the outputs; the library writes them with the pitches of KMQ (ldk) and EkEm (lde), so a caller's views must have
+        those pitches (else contiguous ones are allocated, which asks KMQ / EkEm to be contiguous)"""
+        _chkp(KMQ, 'KMQ'), _chkp(EkEm, 'EkEm'), _chkp(G, 'G')
         DP = 4 * HP
         dev = KMQ.device
-        dKMQ = torch.empty_like(KMQ)
-        dEkEm = torch.empty_like(EkEm)
+        if dKMQ is None:
+            dKMQ = torch.empty(KMQ.shape, dtype=torch.float32, device=dev)
+        if dEkEm is None:
+            dEkEm = torch.empty(EkEm.shape, dtype=torch.float32, device=dev)
+        _chkp(dKMQ, 'dKMQ'), _chkp(dEkEm, 'dEkEm')
+        assert dKMQ.shape == KMQ.shape and dEkEm.shape == EkEm.shape and G.shape == (graph.N, DP)
+        assert _ld(dKMQ) == _ld(KMQ) and _ld(dEkEm) == _ld(EkEm), 'edge_attn_bwd: dKMQ / dEkEm are written with the pitches of KMQ / EkEm'
         ga = torch.empty((graph.Ep, 4), dtype=torch.float32, device=dev)
         rs = torch.empty((graph.N, 4), dtype=torch.float32, device=dev)
         cls_part = torch.empty((graph.max_chunks + CLS_SLICES * graph.C, 2 * DP), dtype=torch.float32, device=dev)
-        rc = self.lib.qagnn_edge_attn_bwd_f32(C.byref(graph.c), KMQ.data_ptr(), 3 * DP, EkEm.data_ptr(), 2 * DP, HP,
-                                              float(qscale), a.data_ptr(), alpha.data_ptr(), G.data_ptr(), DP,
+        rc = self.lib.qagnn_edge_attn_bwd_f32(C.byref(graph.c), KMQ.data_ptr(), _ld(KMQ), EkEm.data_ptr(), _ld(EkEm), HP,
+                                              float(qscale), a.data_ptr(), alpha.data_ptr(), G.data_ptr(), _ld(G),
                                               dKMQ.data_ptr(), dEkEm.data_ptr(), ga.data_ptr(), rs.data_ptr(),
                                               cls_part.data_ptr(), self._stream())
         self._check(rc, 'qagnn_edge_attn_bwd_f32')

@@ -435,6 +435,7 @@ extern "C" int qagnn_colreduce_f32(int32_t mode, const float* X, int32_t ldx, co
   QAGNN_REQUIRE(X && out && workspace, QAGNN_EINVAL, "colreduce: null pointer");
   QAGNN_REQUIRE(R > 0 && Cc > 0 && Cc % 4 == 0 && ldx % 4 == 0 && aligned16(X), QAGNN_EINVAL, "colreduce: bad sizes/alignment");
   QAGNN_REQUIRE(mode >= 0 && mode <= 2, QAGNN_EINVAL, "colreduce: bad mode %d", mode);
+  QAGNN_REQUIRE(ldx >= Cc && (mode != 2 || ldx2 >= Cc), QAGNN_EINVAL, "colreduce: ldx=%d / ldx2=%d below Cc=%d", ldx, ldx2, Cc);
   const bool small = cr_wr(R) == CR_WR_SMALL;
   dim3 grid(cdiv(Cc, 256), cdiv(R, 4 * cr_wr(R)));
   int nout;
@@ -470,6 +471,7 @@ extern "C" int qagnn_bn_relu_bwd_f32(const float* dR, const float* Hh, float* dH
   QAGNN_REQUIRE(dR && Hh && dH && mean && invstd && scale && shift && gamma && sum_dy && sum_dy_hhat, QAGNN_EINVAL,
                 "bn_relu_bwd: null pointer");
   QAGNN_REQUIRE(R > 0 && Cc > 0 && Cc % 4 == 0 && ld % 4 == 0, QAGNN_EINVAL, "bn_relu_bwd: bad sizes");
+  QAGNN_REQUIRE(ld >= Cc, QAGNN_EINVAL, "bn_relu_bwd: ld=%d below Cc=%d", ld, Cc);
   const int64_t tot = (int64_t)R * (Cc / 4);
   k_bn_relu_bwd<<<cdiv(tot, 256), 256, 0, stream>>>(dR, Hh, dH, ld, R, Cc, mean, invstd, scale, shift, gamma, sum_dy, sum_dy_hhat,
                                                     inv_rows, roww);
@@ -697,6 +699,7 @@ extern "C" int qagnn_bn_relu_bwd_colsum_f32(const float* dR, const float* Hh, fl
   QAGNN_REQUIRE(dR && Hh && dH && mean && invstd && scale && shift && gamma && sum_dy && sum_dy_hhat && colsum && workspace, QAGNN_EINVAL,
                 "bn_relu_bwd_colsum: null pointer");
   QAGNN_REQUIRE(R > 0 && Cc > 0 && Cc % 4 == 0 && ld % 4 == 0, QAGNN_EINVAL, "bn_relu_bwd_colsum: bad sizes");
+  QAGNN_REQUIRE(ld >= Cc, QAGNN_EINVAL, "bn_relu_bwd_colsum: ld=%d below Cc=%d", ld, Cc);
   return launch_bn_relu_bwd_colsum(dR, Hh, dH, ld, R, Cc, mean, invstd, scale, shift, gamma, sum_dy, sum_dy_hhat, inv_rows, roww, colsum, workspace,
                                    nullptr, stream);
 }

@@ -125,6 +125,11 @@ static int nn_validate(const NnProduct& p) {
                 QAGNN_EINVAL, "gemm_nn: C / bias / rowtab must be 16-byte aligned with pitches multiple of 4");
   QAGNN_REQUIRE(!a.a_scale || (a.a_shift && aligned16(a.a_scale) && aligned16(a.a_shift)), QAGNN_EINVAL,
                 "gemm_nn: a_scale/a_shift must both be given and 16-byte aligned");
+  // every pitch spans the width it strides (the fp32 route reads B as [K][ldb]; the split routes' [No][ldn] is checked above)
+  QAGNN_REQUIRE(a.lda1 >= a.K1 && (a.K2 == 0 || a.lda2 >= a.K2), QAGNN_EINVAL, "gemm_nn: lda1=%d / lda2=%d below K1=%d / K2=%d", a.lda1, a.lda2,
+                a.K1, a.K2);
+  QAGNN_REQUIRE(p.split || (ldb1 >= a.No && (a.K2 == 0 || ldb2 >= a.No)), QAGNN_EINVAL, "gemm_nn: ldb1=%d / ldb2=%d below No=%d", ldb1, ldb2, a.No);
+  QAGNN_REQUIRE(a.ldc >= a.No && (!a.rowtab || a.ldt >= a.No), QAGNN_EINVAL, "gemm_nn: ldc=%d / ldt=%d below No=%d", a.ldc, a.ldt, a.No);
   if (p.split && a.colstat_part) {
     const int64_t lim = (int64_t)0x7FFFFFFF;
     QAGNN_REQUIRE(cdiv(a.No, 16) == 13 && !a.a_scale && !a.a_rowidx && !a.rowtab && !a.accumulate && a.K2 == 0, QAGNN_EUNSUPPORTED,
@@ -240,6 +245,9 @@ static int tn_validate(const TnProduct& p) {
                 QAGNN_EINVAL, "gemm_tn: operands must be 16-byte aligned with pitches multiple of 4");
   QAGNN_REQUIRE(!p.a_scale || (!p.two && p.a_shift && aligned16(p.a_scale) && aligned16(p.a_shift)), QAGNN_EINVAL,
                 "gemm_tn: a_scale/a_shift must both be given and 16-byte aligned (one-operand products only)");
+  QAGNN_REQUIRE(p.lda1 >= p.Ka1 && (!p.two || p.lda2 >= p.Ka2) && p.ldb >= p.No && p.ldc >= p.No, QAGNN_EINVAL,
+                "gemm_tn: a pitch below its width (lda1=%d Ka1=%d lda2=%d Ka2=%d ldb=%d ldc=%d No=%d)", p.lda1, p.Ka1, p.lda2, p.Ka2, p.ldb, p.ldc,
+                p.No);
   QAGNN_REQUIRE(!p.bsum || (p.groups >= 1 && p.groups <= 4 && (p.groups == 1 || p.b_rowidx)), QAGNN_EINVAL, "gemm_tn: colsum groups=%d (1..4)",
                 p.groups);
   return QAGNN_OK;

@@ -388,6 +388,8 @@ extern "C" int qagnn_head_post_fwd_f32(const float* z, const float* attn, const 
   QAGNN_REQUIRE(p_pool >= 0.f && p_pool < 1.f && p_fc >= 0.f && p_fc < 1.f, QAGNN_EINVAL, "head_post_fwd: dropout probabilities");
   int rc = head_check("head_post_fwd", B, NH, DP, dv, n, Ds, d);
   if (rc != QAGNN_OK) return rc;
+  QAGNN_REQUIRE(ldh >= DP && ldh % 4 == 0 && aligned16(H), QAGNN_EINVAL, "head_post_fwd: ldh=%lld (>= DP=%d, multiple of 4), H 16-byte aligned",
+                (long long)ldh, DP);
   k_head_post_fwd<<<B, HEAD_T, 0, (hipStream_t)stream_>>>(z, attn, BDv, bv, sent, H, ldh, w_fc, b_fc, NH, DP, dv, n, Ds, d, d / 4, DP / 4, p_pool, p_fc,
                                                          seed_pool, seed_fc, seed_epoch_ptr(), out, asum, logits);
   QAGNN_LAUNCH_CHECK("k_head_post_fwd");
@@ -402,6 +404,8 @@ extern "C" int qagnn_head_post_bwd_f32(const float* dlogits, const float* out, c
                 "head_post_bwd: null pointer");
   int rc = head_check("head_post_bwd", B, NH, DP, dv, n, Ds, d);
   if (rc != QAGNN_OK) return rc;
+  QAGNN_REQUIRE(ldh >= DP && ldh % 4 == 0 && aligned16(H), QAGNN_EINVAL, "head_post_bwd: ldh=%lld (>= DP=%d, multiple of 4), H 16-byte aligned",
+                (long long)ldh, DP);
   QAGNN_REQUIRE(ldp >= NH * dv + Ds + d + NH * dv + 1 && ldp <= NH * dv + Ds + d + NH * dv + 1 + 255, QAGNN_EINVAL, "head_post_bwd: pitch of part");
   k_head_post_bwd<<<B, HEAD_T, 0, (hipStream_t)stream_>>>(dlogits, out, asum, BDv, bv, sent, H, ldh, w_fc, NH, DP, dv, n, Ds, d, d / 4, DP / 4, p_pool, p_fc,
                                                          seed_pool, seed_fc, seed_epoch_ptr(), dz, dattn, dout, dsent, dZ, part, ldp);
@@ -411,6 +415,8 @@ extern "C" int qagnn_head_post_bwd_f32(const float* dlogits, const float* out, c
 
 extern "C" int qagnn_add_row0_f32(float* dK, int64_t ld_sub, const float* dZ, int32_t B, int32_t Cc, qagnn_stream_t stream_) {
   QAGNN_REQUIRE(dK && dZ && B > 0 && Cc > 0, QAGNN_EINVAL, "add_row0: bad arguments");
+  QAGNN_REQUIRE(ld_sub >= Cc && ld_sub % 4 == 0 && aligned16(dK) && aligned16(dZ), QAGNN_EINVAL,
+                "add_row0: ld_sub=%lld (>= Cc=%d, multiple of 4), dK / dZ 16-byte aligned", (long long)ld_sub, Cc);
   k_add_row0<<<cdiv(B * Cc, 256), 256, 0, (hipStream_t)stream_>>>(dK, ld_sub, dZ, Cc, B);
   QAGNN_LAUNCH_CHECK("k_add_row0");
   return QAGNN_OK;

@@ -310,7 +310,7 @@ def test_gemm_tn_two_operands(R, Ka1, Ka2, No):
 # profiles/r4_run28_round4_switches_ab.txt, r4_run16_nn2_stagger.txt, r4_run17_tn_ws.txt.)
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize('env,sel', [('QAGNN_GEMM_SPLIT=0', 'test_gemm_tn')])
+@pytest.mark.parametrize('env,sel', [('QAGNN_GEMM_SPLIT=0', 'test_gemm_tn'), ('QAGNN_GEMM_SPLIT=0', 'test_pitched_tn')])
 def test_gemm_kernel_families(env, sel):
     import subprocess
     import sys
@@ -1549,3 +1549,7 @@ def test_native_stack_in_the_three_mfma_form(name, monkeypatch):
 if os.environ.get('QAGNN_VARIANT_CHILD'):
     # the pinned-family child run of test_gemm_kernel_families (-k test_gemm_tn, this file only) takes the non-finite TN tests too
     from test_nonfinite import test_gemm_tn_nonfinite, test_gemm_tn_nonfinite_two_operands  # noqa: E402,F401
+    # ... and, under -k test_pitched_tn, the weight-gradient products on pitched, guarded operands
+    # (test_pitched_operands imports from this module: these imports work only as its LAST statements -- keep them at the very end)
+    from test_pitched_operands import (test_pitched_tn_product, test_pitched_tn_three_mfma_form,  # noqa: E402,F401
+                                       test_pitched_tn_two_operands)
