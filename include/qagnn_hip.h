@@ -66,6 +66,10 @@ int qagnn_abi_version(void);
  * the edge encoder's input one-hot (:419-433) is a function of c alone, C = R*T*T + T classes.
  * All three orders are sorted by (group key, edge id), i.e. deterministic and equal to the reference's CPU
  * summation order inside every group.
+ * Three ways in, one result: int64 edge lists at their exact count (qagnn_graph_prep, qagnn_graph_prep_blocked), int64 edge lists
+ * in buffers of an edge CAPACITY with the count on the device (qagnn_graph_prep_cap), per-sample blobs built at load time, likewise
+ * with a capacity (qagnn_graph_from_blobs).  The two capacity forms have launch shapes that depend on (N, capacity) only: what a
+ * replayed hipGraph of the training step needs.  E, Ep and max_chunks of the struct are then capacities; the true E' is rowptr_s[N].
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct qagnn_graph {
   int32_t N, E, Ep, R, T, C;   /* Ep = E + N */
@@ -121,6 +125,18 @@ int qagnn_graph_prep(qagnn_graph* g, int32_t* storage, const int64_t* edge_index
 int qagnn_graph_prep_blocked(qagnn_graph* g, int32_t* storage, const int64_t* edge_index, const int64_t* edge_type,
                              const int64_t* node_type, int32_t N, int32_t E, int32_t R, int32_t T, int32_t block_n,
                              qagnn_stream_t stream);
+
+/* qagnn_graph_prep_blocked in CAPACITY form, for callers of the int64 edge-list protocol who replay the step as a hipGraph.  The arrays,
+ * g->E / g->Ep / g->max_chunks and every launch shape are laid out for E_cap edges (qagnn_graph_storage_elems(N, E_cap, R, T)); the
+ * batch's true edge count E is the device word *E_dev, read by the kernels.  edge_index holds the sources in [0, E) and the targets at
+ * edge_index + ld_edge (ld_edge >= E_cap: row 1 of a [2][ld_edge] buffer); entries [E, E_cap) of edge_index and edge_type are never
+ * read (under replay they hold the previous batch).  Edge ids are those of the plain call at the true count: e < E the caller's edges,
+ * E + v the self loop of node row v; rowptr_s[N] = rowptr_t[N] = E + N.  A count outside [0, E_cap] is clamped into it on the device
+ * and sets err[0].  The result is bit-identical to qagnn_graph_from_blobs on the same batch at the same capacity (the class order
+ * depends on the capacity), and with E_cap == E to qagnn_graph_prep_blocked. */
+int qagnn_graph_prep_cap(qagnn_graph* g, int32_t* storage, const int64_t* edge_index, int64_t ld_edge, const int64_t* edge_type,
+                         const int64_t* node_type, int32_t N, int32_t E_cap, const int32_t* E_dev /* device, [1] */, int32_t R, int32_t T,
+                         int32_t block_n, qagnn_stream_t stream);
 
 /* The same graph from per-sample blobs built once at LOAD time.  Replaces the per-batch work of
  *   utils/data_utils.py:53-76   2*bs*nc individual .to(device) copies of int64 edge lists

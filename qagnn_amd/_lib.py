@@ -25,10 +25,10 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_hop_fwd_workspace_elems', 'qagnn_hop_bwd_workspace_elems', 'qagnn_hop_fwd_f32', 'qagnn_hop_bwd_f32',
            'qagnn_stack_fwd_f32', 'qagnn_stack_bwd_f32', 'qagnn_absmax_f32', 'qagnn_zero_words', 'qagnn_gemm_tn_h2_f32', 'qagnn_gelu_dropout_fwd_amax_f32', 'qagnn_gelu_dropout_amax_scratch_elems',
            'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows',
-           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32']
+           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32', 'qagnn_graph_prep_cap']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
-ABI_VERSION = 23  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32)
+ABI_VERSION = 24  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY)
 
 _i32, _i64, _f32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p
 
@@ -89,6 +89,7 @@ def load_library(path=LIB_PATH):
     lib.qagnn_graph_storage_elems.argtypes = [_i32, _i32, _i32, _i32]
     lib.qagnn_graph_prep.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     lib.qagnn_graph_prep_blocked.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
+    lib.qagnn_graph_prep_cap.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]
     lib.qagnn_graph_from_blobs.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
     lib.qagnn_node_prep_f32.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]
     lib.qagnn_seed_epoch_advance.argtypes = [_u64, _vp]
@@ -399,6 +400,36 @@ class HipKernels(metaclass=_GuardedMeta):
         G = HipGraph(storage, g, N, E, n_etype, n_ntype, int(block_n))
         ERR_WATCH.poll()  # flags of earlier batches that have landed since
         ERR_WATCH.watch(G.array('err', 4), f'the graph of the batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
+        return G
+
+    def graph_prep_cap(self, batch, node_type, n_etype, n_ntype, block_n=0, storage=None):
+        """batch: data_utils.EdgeListBatch on the device with a capacity (batch.e_cap >= batch.E; edge_index [2, >= e_cap], edge_type
+        [>= e_cap], the count word batch.count).  graph_prep() with the arrays laid out for e_cap edges and the true count read on the
+        device (qagnn_graph_prep_cap): every launch shape depends on (N, e_cap) only, entries [E, e_cap) of the buffers are not read.
+        storage: int32 device storage of at least qagnn_graph_storage_elems(N, e_cap, ...) elements to build into (else allocated)."""
+        ei, et, cnt = batch.edge_index, batch.edge_type, batch.count
+        assert ei.is_cuda and et.is_cuda and ei.dtype == torch.long and et.dtype == torch.long and node_type.dtype == torch.long
+        assert ei.dim() == 2 and ei.size(0) == 2 and ei.stride(1) == 1 and et.is_contiguous() and node_type.is_contiguous()
+        assert cnt is not None and cnt.is_cuda and cnt.dtype == torch.int32 and cnt.numel() == 1, 'EdgeListBatch.count: a one-element int32 device tensor'
+        N, E, e_cap = node_type.numel(), int(batch.E), int(batch.e_cap)
+        assert 0 <= E <= e_cap, f'edge capacity {e_cap} below the batch\'s {E} edges'
+        assert ei.size(1) >= e_cap and et.numel() >= e_cap, f'edge buffers of {ei.size(1)} / {et.numel()} entries below the capacity {e_cap}'
+        ld = ei.stride(0) if ei.size(1) > 1 else ei.size(1)
+        elems = self.lib.qagnn_graph_storage_elems(N, e_cap, n_etype, n_ntype)
+        if storage is None:
+            storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
+        assert storage.is_cuda and storage.dtype == torch.int32 and storage.is_contiguous() and storage.numel() >= elems
+        g = qagnn_graph()
+        if block_n and N % block_n:
+            block_n = 0
+        rc = self.lib.qagnn_graph_prep_cap(C.byref(g), storage.data_ptr(), ei.data_ptr(), ld, et.data_ptr(), node_type.data_ptr(), N, e_cap,
+                                           cnt.data_ptr(), n_etype, n_ntype, int(block_n), self._stream())
+        self._check(rc, 'qagnn_graph_prep_cap')
+        G = HipGraph(storage, g, N, e_cap, n_etype, n_ntype, int(block_n))
+        G.dynamic = True  # E / Ep are capacities: the true E' lives on the device (rowptr_s[N])
+        G.keep = (ei, et, cnt)  # read by the kernels just enqueued
+        ERR_WATCH.poll()
+        ERR_WATCH.watch(G.array('err', 4), f'the graph of the edge-list batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
         return G
 
     def graph_from_blobs(self, packed, node_type):

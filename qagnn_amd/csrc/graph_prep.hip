@@ -26,17 +26,27 @@ void set_error(const char* fmt, ...) {
 // ---- decode + histogram ---------------------------------------------------------------------------------
 // class ids of tens of thousands of self loops collide on a handful of counters: the class histogram is taken from
 // the per-block LDS histograms of k_cls_hist instead of one global atomic per edge.
-__global__ void k_decode_count(const int64_t* __restrict__ edge_index, const int64_t* __restrict__ edge_type,
-                               const int64_t* __restrict__ node_type, int N, int E, int R, int T, int* __restrict__ es,
-                               int* __restrict__ et, int* __restrict__ ec, int* __restrict__ cnt_s, int* __restrict__ cnt_t,
-                               int* __restrict__ err, int block_n) {
+// The batch's edge count of the sorting path.  E_dev == nullptr: the host's E (qagnn_graph_prep_blocked).  Otherwise E is the CAPACITY
+// the arrays and the grids are laid out for and the true count is the device word *E_dev (qagnn_graph_prep_cap), clamped into
+// [0, E]: no index below is ever formed from an unclamped count.
+__device__ __forceinline__ int true_edges(const int* __restrict__ E_dev, int E) {
+  return E_dev ? min(max(*E_dev, 0), E) : E;
+}
+
+// `ld_edge`: the targets are row 1 of edge_index, ld_edge entries behind the sources (E for a dense [2][E] tensor).
+__global__ void k_decode_count(const int64_t* __restrict__ edge_index, int64_t ld_edge, const int64_t* __restrict__ edge_type,
+                               const int64_t* __restrict__ node_type, int N, int E_cap, const int* __restrict__ E_dev, int R, int T,
+                               int* __restrict__ es, int* __restrict__ et, int* __restrict__ ec, int* __restrict__ cnt_s,
+                               int* __restrict__ cnt_t, int* __restrict__ err, int block_n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int E = true_edges(E_dev, E_cap);
+  if (E_dev && e == 0 && *E_dev != E) *err = 1;  // a count outside [0, capacity]: clamped, flagged
   const int Ep = E + N;
   if (e >= Ep) return;
   int s, t, c;
   bool bad = false;
   if (e < E) {
-    int64_t s64 = edge_index[e], t64 = edge_index[(int64_t)E + e], r64 = edge_type[e];
+    int64_t s64 = edge_index[e], t64 = edge_index[ld_edge + e], r64 = edge_type[e];
     bad = s64 < 0 || s64 >= N || t64 < 0 || t64 >= N || r64 < 0 || r64 >= R;
     s = (int)min(max(s64, (int64_t)0), (int64_t)N - 1);
     t = (int)min(max(t64, (int64_t)0), (int64_t)N - 1);
@@ -120,9 +130,9 @@ __global__ __launch_bounds__(1024) void k_scan3(const int* a0, int* o0, int n0, 
 // ---- bucket fill (unordered inside a bucket; fixed up by k_sort_segments) --------------------------------------
 __global__ void k_fill(const int* __restrict__ es, const int* __restrict__ et, const int* __restrict__ rowptr_s,
                        const int* __restrict__ rowptr_t, int* __restrict__ cnt_s, int* __restrict__ cnt_t,
-                       int* __restrict__ tmp_s, int* __restrict__ tmp_t, int Ep) {
+                       int* __restrict__ tmp_s, int* __restrict__ tmp_t, int N, int E_cap, const int* __restrict__ E_dev) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= Ep) return;
+  if (e >= true_edges(E_dev, E_cap) + N) return;
   const int s = es[e], t = et[e];
   tmp_s[rowptr_s[s] + atomicSub(&cnt_s[s], 1) - 1] = e;
   tmp_t[rowptr_t[t] + atomicSub(&cnt_t[t], 1) - 1] = e;
@@ -154,9 +164,10 @@ __global__ __launch_bounds__(256) void k_sort_segments(const int* __restrict__ r
 __global__ void k_payload(const int* __restrict__ es, const int* __restrict__ et, const int* __restrict__ ec,
                           const int* __restrict__ eid_s, const int* __restrict__ eid_t, const int* __restrict__ srcpos,
                           int* __restrict__ tgt_s, int* __restrict__ src_s, int* __restrict__ cls_s, int* __restrict__ src_t,
-                          int* __restrict__ tgt_t, int* __restrict__ cls_t, int* __restrict__ pos_t, int Ep) {
+                          int* __restrict__ tgt_t, int* __restrict__ cls_t, int* __restrict__ pos_t, int N, int E_cap,
+                          const int* __restrict__ E_dev) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= Ep) return;
+  if (p >= true_edges(E_dev, E_cap) + N) return;
   const int e = eid_s[p];
   tgt_s[p] = et[e];
   src_s[p] = es[e];
@@ -518,7 +529,7 @@ static int class_pass(qagnn_graph* g, int32_t* hist, int32_t* gc_cnt, int32_t* g
 }
 
 extern "C" const char* qagnn_last_error(void) { return g_err; }
-extern "C" int qagnn_abi_version(void) { return 23; }
+extern "C" int qagnn_abi_version(void) { return 24; }
 
 extern "C" int64_t qagnn_graph_storage_elems(int32_t N, int32_t E, int32_t R, int32_t T) {
   const int64_t Ep = (int64_t)E + N, C = (int64_t)R * T * T + T;
@@ -545,18 +556,19 @@ extern "C" int qagnn_graph_prep(qagnn_graph* g, int32_t* storage, const int64_t*
   return qagnn_graph_prep_blocked(g, storage, edge_index, edge_type, node_type, N, E, R, T, 0, stream_);
 }
 
-extern "C" int qagnn_graph_prep_blocked(qagnn_graph* g, int32_t* storage, const int64_t* edge_index, const int64_t* edge_type,
-                                        const int64_t* node_type, int32_t N, int32_t E, int32_t R, int32_t T, int32_t block_n,
-                                        qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  QAGNN_REQUIRE(block_n >= 0 && (block_n == 0 || N % block_n == 0), QAGNN_EINVAL, "graph_prep: N=%d is not a multiple of block_n=%d", N, block_n);
-  QAGNN_REQUIRE(g && storage && node_type, QAGNN_EINVAL, "graph_prep: null pointer");
-  QAGNN_REQUIRE(N > 0 && E >= 0 && R > 0 && T > 0, QAGNN_EINVAL, "graph_prep: bad sizes N=%d E=%d R=%d T=%d", N, E, R, T);
-  QAGNN_REQUIRE(E == 0 || (edge_index && edge_type), QAGNN_EINVAL, "graph_prep: null edge arrays with E=%d", E);
-  QAGNN_REQUIRE(aligned16(storage), QAGNN_EINVAL, "graph_prep: storage must be 16-byte aligned");
+// the sorting path: E_dev == nullptr -> E is the batch's edge count; else E is a capacity and *E_dev the count (see true_edges)
+static int prep_sorted(const char* who, qagnn_graph* g, int32_t* storage, const int64_t* edge_index, int64_t ld_edge,
+                       const int64_t* edge_type, const int64_t* node_type, int32_t N, int32_t E, const int32_t* E_dev, int32_t R,
+                       int32_t T, int32_t block_n, hipStream_t stream) {
+  QAGNN_REQUIRE(block_n >= 0 && (block_n == 0 || N % block_n == 0), QAGNN_EINVAL, "%s: N=%d is not a multiple of block_n=%d", who, N, block_n);
+  QAGNN_REQUIRE(g && storage && node_type, QAGNN_EINVAL, "%s: null pointer", who);
+  QAGNN_REQUIRE(N > 0 && E >= 0 && R > 0 && T > 0, QAGNN_EINVAL, "%s: bad sizes N=%d E=%d R=%d T=%d", who, N, E, R, T);
+  QAGNN_REQUIRE(E == 0 || (edge_index && edge_type), QAGNN_EINVAL, "%s: null edge arrays with E=%d", who, E);
+  QAGNN_REQUIRE(ld_edge >= E, QAGNN_EINVAL, "%s: ld_edge=%lld below the %d edges the arrays are laid out for", who, (long long)ld_edge, E);
+  QAGNN_REQUIRE(aligned16(storage), QAGNN_EINVAL, "%s: storage must be 16-byte aligned", who);
   const int64_t Ep64 = (int64_t)E + N, C64 = (int64_t)R * T * T + T;
-  QAGNN_REQUIRE(Ep64 < (1ll << 30), QAGNN_EUNSUPPORTED, "graph_prep: E+N=%lld too large", (long long)Ep64);
-  QAGNN_REQUIRE(C64 <= 8192, QAGNN_EUNSUPPORTED, "graph_prep: %lld edge classes > 8192", (long long)C64);
+  QAGNN_REQUIRE(Ep64 < (1ll << 30), QAGNN_EUNSUPPORTED, "%s: E+N=%lld too large", who, (long long)Ep64);
+  QAGNN_REQUIRE(C64 <= 8192, QAGNN_EUNSUPPORTED, "%s: %lld edge classes > 8192", who, (long long)C64);
   const int Ep = (int)Ep64;
   carved cv = carve(g, storage, N, E, R, T, block_n);
   int32_t *cnt_s = cv.cnt_s, *cnt_t = cv.cnt_t, *es = cv.es, *et = cv.et, *ec = cv.ec, *tmp_s = cv.tmp_s, *tmp_t = cv.tmp_t;
@@ -564,23 +576,39 @@ extern "C" int qagnn_graph_prep_blocked(qagnn_graph* g, int32_t* storage, const 
   const int nblk = cv.nblk, gb = cv.gb, NG = cv.NG, pairs = cv.pairs;
 
   hipError_t he = zero_range(g->cls_count, (size_t)((char*)es - (char*)g->cls_count), stream);
-  if (he != hipSuccess) { set_error("graph_prep: k_zero16 failed: %s", hipGetErrorString(he)); return QAGNN_EHIP; }
+  if (he != hipSuccess) { set_error("%s: k_zero16 failed: %s", who, hipGetErrorString(he)); return QAGNN_EHIP; }
   const int TB = 256;
-  k_decode_count<<<cdiv(Ep, TB), TB, 0, stream>>>(edge_index, edge_type, node_type, N, E, R, T, es, et, ec, cnt_s, cnt_t,
+  k_decode_count<<<cdiv(Ep, TB), TB, 0, stream>>>(edge_index, ld_edge, edge_type, node_type, N, E, E_dev, R, T, es, et, ec, cnt_s, cnt_t,
                                                    g->err, block_n);
   QAGNN_LAUNCH_CHECK("k_decode_count");
   k_scan3<<<2, 1024, 0, stream>>>(cnt_s, g->rowptr_s, N, cnt_t, g->rowptr_t, N, nullptr, nullptr, 0);
   QAGNN_LAUNCH_CHECK("k_scan3");
-  k_fill<<<cdiv(Ep, TB), TB, 0, stream>>>(es, et, g->rowptr_s, g->rowptr_t, cnt_s, cnt_t, tmp_s, tmp_t, Ep);
+  k_fill<<<cdiv(Ep, TB), TB, 0, stream>>>(es, et, g->rowptr_s, g->rowptr_t, cnt_s, cnt_t, tmp_s, tmp_t, N, E, E_dev);
   QAGNN_LAUNCH_CHECK("k_fill");
   k_sort_segments<<<cdiv(2 * (int64_t)N, 4), 256, 0, stream>>>(g->rowptr_s, g->rowptr_t, tmp_s, tmp_t, g->eid_s, eid_t, srcpos, N);
   QAGNN_LAUNCH_CHECK("k_sort_segments");
   k_payload<<<cdiv(Ep, TB), TB, 0, stream>>>(es, et, ec, g->eid_s, eid_t, srcpos, g->tgt_s, g->src_s, g->cls_s, g->src_t,
-                                              g->tgt_t, g->cls_t, g->pos_t, Ep);
+                                              g->tgt_t, g->cls_t, g->pos_t, N, E, E_dev);
   QAGNN_LAUNCH_CHECK("k_payload");
   int rc = xcd_partition(g, stream);
   if (rc != QAGNN_OK) return rc;
   return class_pass(g, hist, gc_cnt, gcptr, nch, nblk, gb, NG, pairs, stream);
+}
+
+extern "C" int qagnn_graph_prep_blocked(qagnn_graph* g, int32_t* storage, const int64_t* edge_index, const int64_t* edge_type,
+                                        const int64_t* node_type, int32_t N, int32_t E, int32_t R, int32_t T, int32_t block_n,
+                                        qagnn_stream_t stream_) {
+  return prep_sorted("graph_prep", g, storage, edge_index, E, edge_type, node_type, N, E, nullptr, R, T, block_n, (hipStream_t)stream_);
+}
+
+// The sorting path in CAPACITY form (the int64 edge-list protocol under a replayed hipGraph, qagnn_amd/graphed.py): same launches,
+// shaped by (N, E_cap); the edge kernels read the true count from *E_dev and leave entries [E, E_cap) of the edge arrays unread.
+extern "C" int qagnn_graph_prep_cap(qagnn_graph* g, int32_t* storage, const int64_t* edge_index, int64_t ld_edge,
+                                    const int64_t* edge_type, const int64_t* node_type, int32_t N, int32_t E_cap, const int32_t* E_dev,
+                                    int32_t R, int32_t T, int32_t block_n, qagnn_stream_t stream_) {
+  QAGNN_REQUIRE(E_dev, QAGNN_EINVAL, "graph_prep_cap: null edge-count pointer");
+  return prep_sorted("graph_prep_cap", g, storage, edge_index, ld_edge, edge_type, node_type, N, E_cap, E_dev, R, T, block_n,
+                     (hipStream_t)stream_);
 }
 
 extern "C" int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const int32_t* blobs, const int32_t* blob_off,

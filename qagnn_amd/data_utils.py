@@ -348,6 +348,56 @@ def batch_graph(edge_index_init, edge_type_init, n_nodes):
     return edge_index, edge_type
 
 
+class EdgeListBatch:
+    """The reference's batched graph -- (edge_index [2, cap], edge_type [cap]), both int64, global node ids g*n + local as batch_graph
+    returns them -- together with its edge count: what QAGNN / LM_QAGNN / graphed.GraphedStep accept wherever they accept the plain pair.
+
+    E       the batch's true edge count, known on the host; entries [E, cap) of the two buffers are padding nobody reads
+    e_cap   (optional) the edge CAPACITY to lay the graph arrays out for, E <= e_cap <= cap.  With it, on the GPU, the graph is built by
+            qagnn_graph_prep_cap: every launch shape depends on (B, n, e_cap) only and the count is read on the device from `count`,
+            which is what a captured hipGraph needs (graphed.GraphedStep sets it; so may a caller who wants one allocation size per bucket).
+            Without it the pair is sliced to its first E entries and takes the plain sorting path.
+    count   a one-element int32 device tensor holding E: created where the batch reaches the device (to()), None on the host."""
+
+    def __init__(self, edge_index, edge_type, E=None, e_cap=None, count=None):
+        assert edge_index.dim() == 2 and edge_index.size(0) == 2 and edge_type.dim() == 1
+        assert edge_index.dtype == torch.long and edge_type.dtype == torch.long
+        self.edge_index, self.edge_type = edge_index, edge_type
+        self.E = int(edge_index.size(1) if E is None else E)
+        self.e_cap = None if e_cap is None else int(e_cap)
+        assert 0 <= self.E <= min(edge_index.size(1), edge_type.numel()), f'E = {self.E} exceeds the edge buffers'
+        assert self.e_cap is None or self.E <= self.e_cap <= min(edge_index.size(1), edge_type.numel()), \
+            f'e_cap = {self.e_cap} must lie between E = {self.E} and the buffers\' {edge_index.size(1)} entries'
+        self.count = None if count is False else count  # (count=False: a holder that is only read on the host side, no device word)
+        if count is None and edge_index.is_cuda:
+            self.count = torch.tensor([self.E], dtype=torch.int32).to(edge_index.device, non_blocking=True)
+
+    @classmethod
+    def from_lists(cls, edge_index_lists, edge_type_lists, n, e_cap=None):
+        """The reference's nested [bs][nc] lists of per-graph [2, E_g] / [E_g] tensors (what its batch generator yields and
+        LM_QAGNN.forward receives), flattened and offset exactly as batch_graph does.  e_cap: pad the buffers to that capacity."""
+        ei, et = batch_graph([g for row in edge_index_lists for g in row], [g for row in edge_type_lists for g in row], n)
+        E = ei.size(1)
+        if e_cap is not None and e_cap > E:
+            ei = torch.nn.functional.pad(ei, (0, e_cap - E))
+            et = torch.nn.functional.pad(et, (0, e_cap - E))
+        return cls(ei, et, E, e_cap)
+
+    @property
+    def device(self):
+        return self.edge_index.device
+
+    def to(self, device, non_blocking=False):
+        device = torch.device(device)
+        ei, et = self.edge_index.to(device, non_blocking=non_blocking), self.edge_type.to(device, non_blocking=non_blocking)
+        count = self.count.to(device, non_blocking=non_blocking) if self.count is not None and device.type == 'cuda' else None
+        return EdgeListBatch(ei, et, self.E, self.e_cap, count)
+
+    def pair(self):
+        """(edge_index [2, E], edge_type [E]): the plain pair, padding cut off (views)."""
+        return self.edge_index[:, :self.E], self.edge_type[:self.E]
+
+
 class MultiGPUSparseAdjDataBatchGenerator(object):
     """Iteration protocol of reference utils/data_utils.py:17-76.
 

@@ -6,9 +6,10 @@ run_qagnn__csqa.sh:16-17; qagnn.py:252-266) the GPU work is < 2 ms while Python 
 forward + loss + backward with one host call.
 
 What makes it legitimate for TRAINING (a new batch every step, not a replay of one batch):
-  * shapes  -- every launch shape of the step depends on (B, n, edge CAPACITY) only: the graph arrives as load-time blobs in a
-    static buffer laid out for `e_cap` >= E edges, and the kernels read the batch's true edge count on the device
-    (qagnn_graph_from_blobs, include/qagnn_hip.h).  One capture per capacity bucket (8 buckets per octave of E: <= 12.5 % slack);
+  * shapes  -- every launch shape of the step depends on (B, n, edge CAPACITY) only: the graph arrives in static buffers laid out for
+    `e_cap` >= E edges -- load-time blobs (qagnn_graph_from_blobs) or the reference's int64 edge lists (qagnn_graph_prep_cap,
+    include/qagnn_hip.h) -- and the kernels read the batch's true edge count on the device.  One capture per capacity bucket (8 buckets
+    per octave of E: <= 12.5 % slack) and kind of graph input;
   * inputs  -- static device buffers, refilled by `copy_` before each replay (the one host-to-device copy per tensor the eager path
     makes too);
   * dropout -- seeds are launch arguments, which a graph replays verbatim; the kernels mix in a device-side epoch word that the
@@ -31,7 +32,7 @@ import math
 import torch
 
 from . import ops
-from .data_utils import PackedGraphBatch
+from .data_utils import EdgeListBatch, PackedGraphBatch
 
 
 def edge_capacity(E, floor=1024):
@@ -42,14 +43,15 @@ def edge_capacity(E, floor=1024):
 
 
 class _Captured:
-    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'blob', 'lw', 'packed', 'logits', 'attn', 'loss', 'grads', 'replays',
+    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'blob', 'lw', 'packed', 'ei', 'et', 'ecount', 'logits', 'attn', 'loss', 'grads', 'replays',
                  'params', 'watched', 'sent_grad')
 
 
 class GraphedStep:
     """step = GraphedStep(model, num_choice);  logits, loss = step(sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths,
     packed, labels, loss_weight)  -- the flattened [B, ...] decoder inputs of QAGNN.forward (reference modeling_qagnn.py:141-189), the
-    graph as a data_utils.PackedGraphBatch (device or host buffer), labels [B / num_choice].
+    graph as a data_utils.PackedGraphBatch (device or host buffer), a data_utils.EdgeListBatch or the reference's plain
+    (edge_index [2, E], edge_type [E]) int64 pair (device or host, pinned or not), labels [B / num_choice].
 
     loss = cross_entropy(logits.view(-1, nc), labels) * loss_weight  (the reference's mini-batch loss, qagnn.py:257-261);
     after the call every trainable parameter's .grad holds this step's gradient (zero_grad implicit), or -- accumulate=True -- the
@@ -82,10 +84,10 @@ class GraphedStep:
     def _key(self, sent, cids, packed):
         trainable = tuple(i for i, p in enumerate(self.model.parameters()) if p.requires_grad)
         return (cids.size(0), cids.size(1), sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad),
-                hash(trainable))
+                hash(trainable), 'blobs' if isinstance(packed, PackedGraphBatch) else 'edge lists')
 
     def _capture(self, key, args):
-        B, n, sent_dim, e_cap, _, sent_rg, _ = key
+        B, n, sent_dim, e_cap, _, sent_rg, _, kind = key
         sent, cids, nt, ns, al, packed, labels, lw = args
         dev, K = self.dev, ops.kernels()
         from ._lib import ERR_WATCH
@@ -99,9 +101,16 @@ class GraphedStep:
         c.al = torch.empty((B,), dtype=torch.long, device=dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev)
         c.lw = torch.ones((), dtype=torch.float32, device=dev)
-        c.blob = torch.zeros(packed.head + 2 * n * B + 3 * e_cap, dtype=torch.int32, device=dev)
-        c.packed = PackedGraphBatch(c.blob, B, packed.E, packed.store, packed.sample_ids, packed.num_choice)
-        c.packed.e_cap = e_cap
+        c.blob = c.ei = c.et = c.ecount = None
+        if kind == 'blobs':
+            c.blob = torch.zeros(packed.head + 2 * n * B + 3 * e_cap, dtype=torch.int32, device=dev)
+            c.packed = PackedGraphBatch(c.blob, B, packed.E, packed.store, packed.sample_ids, packed.num_choice)
+            c.packed.e_cap = e_cap
+        else:  # int64 edge lists in static buffers of the bucket's capacity + the count word the preparation kernels read
+            c.ei = torch.zeros((2, e_cap), dtype=torch.long, device=dev)
+            c.et = torch.zeros((e_cap,), dtype=torch.long, device=dev)
+            c.ecount = torch.zeros((1,), dtype=torch.int32, device=dev)
+            c.packed = EdgeListBatch(c.ei, c.et, packed.E, e_cap, count=c.ecount)
         c.replays = 0
         self._load(c, args)
         # warm-up outside the capture (lazy initialisation: operand-packing plans, LDS attribute raises, allocator pools), on a side
@@ -158,12 +167,23 @@ class GraphedStep:
         c.al.copy_(al, non_blocking=True)
         c.labels.copy_(labels, non_blocking=True)
         c.lw.fill_(float(lw))
+        if c.blob is None:
+            E = packed.E
+            assert E <= c.packed.e_cap
+            c.ei[:, :E].copy_(packed.edge_index[:, :E], non_blocking=True)  # entries [E, e_cap) keep an earlier batch: never read
+            c.et[:E].copy_(packed.edge_type[:E], non_blocking=True)
+            c.ecount.fill_(E)  # (a launch argument, like the loss weight: nothing waits for the device)
+            c.packed.E = E
+            return
         nwords = packed.buf.numel()
         assert nwords <= c.blob.numel() and packed.E <= c.packed.e_cap and packed.B == c.packed.B and packed.n == c.packed.n
         c.blob[:nwords].copy_(packed.buf, non_blocking=True)
 
     def __call__(self, sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight=1.0, accumulate=False):
-        assert isinstance(packed, PackedGraphBatch), 'GraphedStep takes the graph as load-time blobs (data_utils.PackedGraphBatch)'
+        if not isinstance(packed, (PackedGraphBatch, EdgeListBatch)):
+            assert isinstance(packed, (tuple, list)) and len(packed) == 2 and all(isinstance(t, torch.Tensor) for t in packed), \
+                'GraphedStep takes the graph as a PackedGraphBatch, an EdgeListBatch or an (edge_index [2, E], edge_type [E]) pair'
+            packed = EdgeListBatch(packed[0], packed[1], count=False)  # (no count word of its own: the capture's static one is written)
         args = (sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight)
         key = self._key(sent_vecs, concept_ids, packed)
         with torch.cuda.device(self.dev):

@@ -436,7 +436,7 @@ class QAGNN_Message_Passing(nn.Module):
         ntype = node_type.reshape(-1).contiguous()
         if graph is None:
             # subgraph i owns node rows [i*n, (i+1)*n) (LM_QAGNN.batch_graph): lets the edge forward run out of LDS.
-            # A = (edge_index, edge_type) like the reference, or a data_utils.PackedGraphBatch of load-time blobs
+            # A = (edge_index, edge_type) like the reference (or as a data_utils.EdgeListBatch), or a data_utils.PackedGraphBatch of blobs
             graph = ops.build_graph(A, ntype, self.n_etype, self.n_ntype, n)
         per_layer, extras = self.pack_all(L)
         Vh_t, Vh, Vx_t, Vx, bVh, bVx, Wes_t, Wes, bes, We_t_all, We_all, be_all, Wtype_all, bias_all = extras[:14]
@@ -531,7 +531,8 @@ class QAGNN(nn.Module):
     def forward(self, sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, adj, emb_data=None, cache_output=False):
         """
         sent_vecs (B, dim_sent); concept_ids (B, n); node_type_ids (B, n); node_scores (B, n, 1); adj_lengths (B,)
-        adj = (edge_index [2, E] with global node ids g*n + local, edge_type [E]);  returns (B, 1), (n_head*B, n)
+        adj = (edge_index [2, E] with global node ids g*n + local, edge_type [E]), or the same pair with its edge count as a
+        data_utils.EdgeListBatch, or a data_utils.PackedGraphBatch of load-time blobs;  returns (B, 1), (n_head*B, n)
         """
         dev = node_type_ids.device
         n = node_type_ids.size(1)
@@ -617,16 +618,20 @@ class LM_QAGNN(nn.Module):
 
     def forward(self, *inputs, layer_id=-1, cache_output=False, detail=False):
         """inputs = [*lm_tensors (bs, nc, ...), concept_ids, node_type_ids, node_scores, adj_lengths (bs, nc, ...),
-        edge_index, edge_type (nested lists [bs][nc] of [2, E_g] / [E_g])]  ->  logits (bs, nc), pool_attn."""
+        edge_index, edge_type (nested lists [bs][nc] of [2, E_g] / [E_g]; or a data_utils.PackedGraphBatch / EdgeListBatch in place of
+        edge_index, with edge_type None)]  ->  logits (bs, nc), pool_attn."""
         bs, nc = inputs[0].size(0), inputs[0].size(1)
         edge_index_orig, edge_type_orig = inputs[-2:]
         flat = [x.reshape(bs * nc, *x.shape[2:]) for x in inputs[:-2]]
         *lm_inputs, concept_ids, node_type_ids, node_scores, adj_lengths = flat
         dev = node_type_ids.device
-        from .data_utils import PackedGraphBatch
+        from .data_utils import EdgeListBatch, PackedGraphBatch
         if isinstance(edge_index_orig, PackedGraphBatch):
             # the batch generator shipped the graph as one buffer of load-time blobs: batch_graph's offsets are applied in-kernel
             adj = edge_index_orig
+        elif isinstance(edge_index_orig, EdgeListBatch):
+            # already batched (EdgeListBatch.from_lists = batch_graph) and carrying its edge count; handed back as is under `detail`
+            adj = edge_index_orig if edge_index_orig.device == dev else edge_index_orig.to(dev)
         else:
             edge_index = [g for row in edge_index_orig for g in row]  # (:224) nested [bs][nc] -> flat [bs*nc]
             edge_type = [g for row in edge_type_orig for g in row]

@@ -356,9 +356,14 @@ _PREP_STREAMS = {}
 
 def build_graph(adj, node_type, n_etype, n_ntype, block_n):
     """The batch's graph orderings from whatever the caller handed over as `adj`: a data_utils.PackedGraphBatch (load-time
-    blobs, one device buffer) or the reference's (edge_index [2, E], edge_type [E]) int64 pair."""
+    blobs, one device buffer), the reference's (edge_index [2, E], edge_type [E]) int64 pair, or a data_utils.EdgeListBatch (that pair
+    with its edge count: with a capacity it takes the capacity form of the sorting path, where the provider has one)."""
     K = kernels()
-    from .data_utils import PackedGraphBatch
+    from .data_utils import EdgeListBatch, PackedGraphBatch
+    if isinstance(adj, EdgeListBatch):
+        if adj.e_cap is not None and hasattr(K, 'graph_prep_cap') and node_type.is_cuda:
+            return K.graph_prep_cap(adj.to(node_type.device) if adj.device != node_type.device else adj, node_type, n_etype, n_ntype, block_n=block_n)
+        adj = adj.pair()
     packed = adj if isinstance(adj, PackedGraphBatch) else (adj[0] if isinstance(adj[0], PackedGraphBatch) else None)
     if packed is not None:
         assert packed.n == block_n and packed.n_etype == n_etype and packed.n_ntype == n_ntype, 'blob store built for another model shape'
