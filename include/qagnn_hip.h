@@ -15,7 +15,9 @@
  *   - fp32 everywhere ("dtype f32"), int32 graph arrays, int64 only where the reference hands us int64 tensors.
  *   - "head-padded" node rows: a feature row of d = H*dh floats is stored as H groups of HP = roundup4(dh) floats
  *     (pads are zero), DP = H*HP floats per row (d=200,H=4: HP=52, DP=208 -> 832-byte rows, 16-byte aligned heads).
- *     H must be 4 (the reference hard-codes head_count=4, modeling_qagnn.py:387) and dh <= 64.
+ *     H must be 4 (the reference hard-codes head_count=4, modeling_qagnn.py:387) and dh <= 64.  In short H = 4, HP % 4 == 0, dh <= 64:
+ *     held at the edges of that range (HP = 4 .. 64) by tests/test_head_widths.py; the edge kernels and the hop refuse any other pitch
+ *     before anything is enqueued.
  *   - row pitches (lda*, ldb*, ldn*, ldc, ldt, ldx*, ld, ldk, lde, ldg, lddk, ldh, ldp, ld_sub): in floats, a multiple of 4, every row
  *     16-byte aligned, and EVERY PITCH >= THE WIDTH IT STRIDES; a pitch below its width is QAGNN_EINVAL before anything is launched.  A
  *     pitch above the width is a view into a larger buffer: no entry point reads or writes a float outside the rows x width it was

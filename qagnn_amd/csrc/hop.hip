@@ -33,6 +33,7 @@ static int check_hop(const qagnn_hop_args* h, const char* who) {
   QAGNN_REQUIRE(h && h->g, QAGNN_EINVAL, "%s: null argument block / graph", who);
   QAGNN_REQUIRE(h->N == h->g->N && h->N > 0, QAGNN_EINVAL, "%s: N=%d does not match the graph (N=%d)", who, h->N, h->g->N);
   QAGNN_REQUIRE(h->HP > 0 && h->HP % 4 == 0 && h->DP == 4 * h->HP, QAGNN_EINVAL, "%s: DP=%d must be 4*HP (HP=%d)", who, h->DP, h->HP);
+  QAGNN_REQUIRE(h->HP <= 64, QAGNN_EUNSUPPORTED, "%s: head pitch HP=%d must be <= 64 (the edge kernels' lane map)", who, h->HP);
   QAGNN_REQUIRE(h->DP % 16 == 0 && h->SP >= 0 && h->SP % 16 == 0, QAGNN_EUNSUPPORTED,
                 "%s: DP=%d and SP=%d must be multiples of 16 (GEMM k-tile)", who, h->DP, h->SP);
   QAGNN_REQUIRE(h->T >= 1 && h->T <= 4, QAGNN_EUNSUPPORTED, "%s: %d node types (the type-table gradient handles 1..4)", who, h->T);
@@ -115,7 +116,7 @@ static int hop_tn(const qagnn_hop_args* h, const float* A1, int Ka1, const float
 
 // x_ready / s_ready: the words of X / S already hold this call's maxima (an earlier hop of the stack produced them)
 static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready, bool s_ready, qagnn_stream_t stream) {
-  HOP_TRY(check_hop(h, "hop_fwd"));
+  // (h has passed check_hop: both entry points validate every hop before the first enqueue)
   const int N = h->N, DP = h->DP, SP = h->SP, Ep = h->g->Ep;
   Carver w{h->ws, h->ws + h->ws_elems};
   float* score = w.take((int64_t)Ep * 4);
@@ -187,6 +188,7 @@ static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready,
 
 extern "C" int qagnn_hop_fwd_f32(const qagnn_hop_args* h, qagnn_stream_t stream) {
   QAGNN_REQUIRE(h, QAGNN_EINVAL, "hop_fwd: null argument block");
+  HOP_TRY(check_hop(h, "hop_fwd"));  // (before the first enqueue: a refused hop leaves every buffer as it was)
   const HopAmax am = hop_amax_single(h);
   if (am.on) HOP_TRY(qagnn_zero_words(h->amax, QAGNN_HOP_AMAX_WORDS, stream));
   return hop_fwd_one(h, am, h->x_amax != nullptr, h->s_amax != nullptr, stream);
@@ -251,7 +253,7 @@ static int stream_after(hipStream_t to, hipStream_t from, hipEvent_t ev) {
 // from the workspace (d out, d h1, d K|M|Q) lives in buffer set `set`; the caller alternates sets from hop to hop and makes the
 // main stream wait for `*done` before it reuses one, so the side stream may lag the main stream by a whole hop.
 static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss, int set, hipEvent_t* done) {
-  HOP_TRY(check_hop(h, "hop_bwd"));
+  // (h has passed check_hop: stack_bwd_impl validates every hop before the first enqueue)
   QAGNN_REQUIRE(h->dy && h->dWx_t && h->dTT && h->dEkEm && h->dW1t && h->db1 && h->dbn && h->dW2t && h->db2, QAGNN_EINVAL,
                 "hop_bwd: null gradient pointer");
   QAGNN_REQUIRE(h->SP == 0 || h->dWs_t, QAGNN_EINVAL, "hop_bwd: dWs_t missing");
@@ -368,6 +370,8 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
 
 // k hops, last first; the buffer sets alternate and the main stream joins the weight-gradient stream before it returns
 static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main) {
+  // every hop, before an event is recorded or a kernel enqueued: a refused stack leaves every buffer as it was
+  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], k > 1 ? "stack_bwd" : "hop_bwd"));
   SideSync ss;
   HOP_TRY(side_sync_init(&ss, main, (hipStream_t)hops[k - 1].side_stream));
   hipEvent_t done[2] = {nullptr, nullptr};
@@ -403,6 +407,7 @@ extern "C" int qagnn_hop_bwd_f32(const qagnn_hop_args* h, qagnn_stream_t stream)
 // as k calls of qagnn_hop_fwd_f32 / qagnn_hop_bwd_f32 -- one FFI crossing and one autograd node instead of k for host-bound batches.
 extern "C" int qagnn_stack_fwd_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {
   QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_fwd: no hops");
+  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], "stack_fwd"));  // (every hop, before the first enqueue)
   // the hops' amax blocks start at zero: one launch when they are one array (the module mirror's are), one per hop otherwise
   bool any = false, one_array = true;
   for (int l = 0; l < k; ++l) {

@@ -109,7 +109,9 @@ def class_ladder(seed=12, N=40, R=38, T=4):
 GRAPH_CASES = [('big_pad', lambda: padded_graph(7, 320, 200, 128, 400000)), ('rand_small', lambda: rand_graph(1, 50, 300)), ('rand_hub', lambda: rand_graph(2, 700, 9000, hub=True)),
                ('no_edges', lambda: rand_graph(3, 40, 0)), ('one_node', lambda: rand_graph(4, 1, 5)),
                ('medqa_classes', lambda: rand_graph(5, 3000, 40000, R=34)), ('big', lambda: rand_graph(6, 64000, 400000)),
-               ('degree_ladder', degree_ladder), ('class_ladder', class_ladder)]
+               ('degree_ladder', degree_ladder), ('class_ladder', class_ladder),
+               # E' = 66 000 >= 65 536: the 1024-thread launch of k_cls_reduce (csrc/edge_attn.hip) on a graph small enough for every width
+               ('rand_64k', lambda: rand_graph(8, 2000, 64000))]
 
 
 def golden_graph(case):
@@ -214,7 +216,12 @@ GEMM_SHAPES = [(1000, 208, 0, 208), (777, 208, 208, 624), (4100, 624, 0, 208), (
                # 8-column-tile block (and one it leaves to the 4-wave blocks: 7 column tiles); the projection above walks three tiles per block (stores of one tile under the loads of the next)
                (63901, 624, 0, 208), (61003, 320, 0, 200), (60001, 320, 8, 112), (60100, 320, 0, 128),
                # round 5: two more shapes of the unpacked k_gemm_nn2 (4 000 .. 8 191 rows)
-               (6000, 208, 112, 624), (4500, 624, 0, 208)]
+               (6000, 208, 112, 624), (4500, 624, 0, 208),
+               # the hop's products at d = 256 (DP = 256, S 128 wide: 48 column tiles = 13 + 13 + 13 + 9; K1 = 256 is the last width whose
+               # scale / shift prologue the second-generation kernels take), d = 240 (K1 % 32 == 16 with a 128-wide second segment), d = 128 and
+               # d = 16, below and above the packed-B row count; K1 = 264: the prologue declined (first-generation route)
+               (2000, 256, 128, 768), (2000, 256, 0, 256), (2000, 768, 0, 256), (2000, 768, 0, 128), (2000, 240, 128, 720), (2000, 240, 0, 240),
+               (2000, 128, 64, 384), (2000, 16, 16, 48), (9000, 256, 128, 768), (9000, 256, 0, 256), (300, 264, 0, 256)]
 
 
 @pytest.mark.gpu
@@ -257,7 +264,9 @@ def test_gemm_nn(M, K1, K2, No, variant, split):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('R,Ka,No', [(5000, 208, 208), (1030, 624, 208), (2049, 208, 624), (100, 112, 112), (64000, 208, 208), (7, 32, 96),
-                                     (4100, 112, 624), (3000, 200, 204), (2080, 612, 208), (1500, 64, 104)])
+                                     (4100, 112, 624), (3000, 200, 204), (2080, 612, 208), (1500, 64, 104),
+                                     # d = 256 (Ka = 256: a 208-row block plus a 48-row one), d = 240, d = 16
+                                     (2000, 256, 256), (2000, 256, 768), (1500, 240, 720), (2000, 16, 48)])
 @pytest.mark.parametrize('affine', [False, True])
 def test_gemm_tn(R, Ka, No, affine):
     g = torch.Generator().manual_seed(R + Ka)
@@ -283,7 +292,8 @@ def test_gemm_tn(R, Ka, No, affine):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('R,Ka1,Ka2,No', [(64000, 208, 112, 624), (2000, 208, 112, 624), (12800, 208, 208, 208), (5000, 208, 16, 624),
-                                          (700, 32, 16, 96), (1500, 100, 112, 208)])
+                                          (700, 32, 16, 96), (1500, 100, 112, 208),
+                                          (2000, 256, 128, 768), (2000, 240, 128, 720), (2000, 16, 16, 48)])  # d = 256, 240, 16
 def test_gemm_tn_two_operands(R, Ka1, Ka2, No):
     """qagnn_gemm_tn2_f32: [A1 | A2]^T B in one launch (the merged bf16-split launch where both shapes qualify, two plain calls
     otherwise) == the two products, on the fp32 backward-error bound of test_gemm_tn; rows past the operands' widths never leak."""
@@ -471,18 +481,36 @@ def test_sin_basis_matches_host_libm():
     assert (got - ref).abs().max().item() < 5e-7
 
 
-HEAD_DIM = {52: 50, 8: 8, 28: 25, 16: 16}  # head pitch HP -> live floats per head (the rest of a head's slots are zero pads)
+# (head pitch HP, live floats per head dh) -> d = 4 dh; the rest of a head's HP slots are zero pads.  The first four are the widths the
+# tests name by their pitch alone (a bare HP means that pair); WIDTH_LADDER holds the edges of the admitted range HP % 4 == 0, HP <= 64:
+# one active lane per DPP row (HP = 4) with and without a pad, d = 128, K1 % 32 == 16 (HP = 60), no idle lane (HP = 64) with one pad column
+# and with none (tests/test_head_widths.py).
+_DH_OF_PITCH = {52: 50, 8: 8, 28: 25, 16: 16}
+WIDTH_LADDER = [(4, 3), (4, 4), (32, 32), (60, 60), (64, 63), (64, 64)]
+HEAD_DIM = {(HP, dh): 4 * dh for HP, dh in list(_DH_OF_PITCH.items()) + WIDTH_LADDER}
+
+
+def head_dim(HP, dh=None):
+    """live floats per head of a width given as a bare pitch (the four pre-ladder widths) or as the (HP, dh) pair"""
+    dh = _DH_OF_PITCH[HP] if dh is None else dh
+    assert (HP, dh) in HEAD_DIM and HP % 4 == 0 and HP - 4 < dh <= HP, (HP, dh)
+    return dh
+
+
+def side_width(HP):
+    """SP of the hop tests: the 112-wide S of d = 200, else roundup(2 HP, 16) (= 16 at HP = 8, as before the ladder)"""
+    return 112 if HP == 52 else -(-2 * HP // 16) * 16
 
 
 def _graph_of(case_or_name):
     return dict(GRAPH_CASES)[case_or_name]() if case_or_name in dict(GRAPH_CASES) else golden_graph(case_or_name)
 
 
-def edge_inputs(case_or_name, HP, seed):
+def edge_inputs(case_or_name, HP, seed, dh=None):
     ei, et, nt, R, T = _graph_of(case_or_name)
     g = torch.Generator().manual_seed(seed)
     N, C, DP = nt.numel(), R * T * T + T, 4 * HP
-    dh = HEAD_DIM[HP]
+    dh = head_dim(HP, dh)
     mask = (torch.arange(DP) % HP < dh).float()
     KMQ = torch.randn(N, 3 * DP, generator=g) * mask.repeat(3)
     EkEm = torch.randn(C, 2 * DP, generator=g) * mask.repeat(2)
@@ -490,7 +518,7 @@ def edge_inputs(case_or_name, HP, seed):
     return (ei, et, nt, R, T), KMQ, EkEm, G, 1.0 / dh ** 0.5
 
 
-def edge_inputs_offset(case_or_name, HP, seed):
+def edge_inputs_offset(case_or_name, HP, seed, dh=None):
     """Exact scores with a large common offset: every entry is -1, 0 or 1, except the first column of every head, where Q = 32, K = 0 and
     Ek = 16; qscale = 1/4.  Every raw score is then 128 + (an integer of at most dh - 1) / 4, exactly in fp32: exp(score) overflows fp32
     (e^128 > 3.4e38) unless the segment's maximum is subtracted first, score - max is exact, and the softmax stays spread over its segment
@@ -498,7 +526,7 @@ def edge_inputs_offset(case_or_name, HP, seed):
     ei, et, nt, R, T = _graph_of(case_or_name)
     g = torch.Generator().manual_seed(seed)
     N, C, DP = nt.numel(), R * T * T + T, 4 * HP
-    mask = (torch.arange(DP) % HP < HEAD_DIM[HP]).float()
+    mask = (torch.arange(DP) % HP < head_dim(HP, dh)).float()
     tern = lambda *shape: torch.randint(-1, 2, shape, generator=g).float()  # noqa: E731
     KMQ, EkEm, G = tern(N, 3 * DP) * mask.repeat(3), tern(C, 2 * DP) * mask.repeat(2), tern(N, DP) * mask
     for h in range(4):
@@ -510,14 +538,14 @@ EDGE_OUTPUTS = ('aggr', 'a', 'alpha', 'dKMQ', 'dEkEm')
 EDGE_BARS = {'a': 2e-6, 'alpha': 2e-6, 'aggr': 5e-6, 'dKMQ': 2e-5, 'dEkEm': 2e-5}  # of the reference's maximum
 
 
-def _build_edge_case(name, HP, kind):
-    (ei, et, nt, R, T), KMQ, EkEm, G, qs = (edge_inputs_offset if kind == 'offset' else edge_inputs)(name, HP, 21)
+def _build_edge_case(name, HP, kind, dh=None):
+    (ei, et, nt, R, T), KMQ, EkEm, G, qs = (edge_inputs_offset if kind == 'offset' else edge_inputs)(name, HP, 21, dh)
     e = EmuGraph(ei, et, nt, R, T)
     fwd = EMU.edge_attn_fwd(e, KMQ.double(), EkEm.double(), HP, qs)
     ref = dict(zip(EDGE_OUTPUTS, fwd + EMU.edge_attn_bwd(e, KMQ.double(), EkEm.double(), HP, qs, fwd[1], fwd[2], G.double())))
-    case = types.SimpleNamespace(name=name, HP=HP, kind=kind, graph=(ei, et, nt, R, T), e=e, KMQ=KMQ, EkEm=EkEm, G=G, qs=qs, ref=ref,
+    case = types.SimpleNamespace(name=name, HP=HP, dh=head_dim(HP, dh), kind=kind, graph=(ei, et, nt, R, T), e=e, KMQ=KMQ, EkEm=EkEm, G=G, qs=qs, ref=ref,
                                  emu32=None, bars=dict(EDGE_BARS))
-    if kind == 'offset' or name in ('degree_ladder', 'class_ladder'):
+    if kind == 'offset' or name in ('degree_ladder', 'class_ladder') or dh is not None:  # (dh given: a case of the width ladder)
         # The yardstick of the cases added with the ladders: the emulation's own formulas evaluated in float32 (so: the same arithmetic as the
         # kernels up to the order of the sums), each output's worst error against the float64 evaluation, relative to that output's maximum.
         # A new case's bar is the fixed bar or 4 x this, whichever is larger -- 4 for the kernels' other summation order (16-lane DPP trees,
@@ -532,11 +560,12 @@ def _build_edge_case(name, HP, kind):
 _cached_edge_case = functools.lru_cache(maxsize=None)(_build_edge_case)
 
 
-def edge_case(name, HP, kind='randn'):
+def edge_case(name, HP, kind='randn', dh=None):
     """Graph, operands (seed 21), the float64 emulation of all five outputs and the bar of each.  The small cases that several tests share
-    are built once per process; nobody writes to what this returns."""
-    small = kind == 'offset' or name in ('degree_ladder', 'class_ladder', 'rand_small')
-    return (_cached_edge_case if small else _build_edge_case)(name, HP, kind)
+    are built once per process; nobody writes to what this returns.  dh: the live floats per head where the pitch alone does not say
+    (head_dim); such a case takes the ladders' bar rule whatever its graph."""
+    small = (kind == 'offset' and name != 'rand_64k') or name in ('degree_ladder', 'class_ladder', 'rand_small')
+    return (_cached_edge_case if small else _build_edge_case)(name, HP, kind, dh)
 
 
 def _worst_row(case, nm, d):
@@ -575,8 +604,10 @@ def check_edge_outputs(case, got, log=None):
             failures.append(f'{nm} is not finite')
     assert not failures, '; '.join(failures)
     # pads stay exactly zero
-    padmask = (torch.arange(DP) % HP >= HEAD_DIM[HP])
+    padmask = (torch.arange(DP) % HP >= case.dh)  # (empty at dh == HP: the assertions still run, on nothing)
+    assert int(padmask.sum()) == 4 * (HP - case.dh)
     assert (got['aggr'][:, padmask] == 0).all() and (got['dKMQ'][:, padmask.repeat(3)] == 0).all()
+    assert (got['dEkEm'][:, padmask.repeat(2)] == 0).all(), 'pad columns of dEk | dEm are not zero'
     # softmax rows: sum over each source segment of a == 1 (size-independent property)
     seg = torch.zeros(e.N, 4, dtype=torch.float64).index_add_(0, e.src_s.long(), got['a'].double())
     worst = (seg - 1).abs().max(1).values
@@ -600,7 +631,8 @@ def run_edge_kernels(case):
 
 
 def print_figures(label, log):
-    """One line per case for the record of a GPU run (profiles/attention_ladder_gpu_tests.txt; shown by pytest -s, or on failure): per output
+    """One line per case for the record of a GPU run (profiles/attention_ladder_gpu_tests.txt, profiles/head_width_gpu_tests.txt; shown by
+    pytest -s, or on failure): per output
     the worst error / the bar, both as fractions of the reference's maximum, and the float32 emulation's error where the bar rests on it."""
     print(f'FIGURE {label}: ' + ' | '.join(f'{nm} {err:.2e} / {bar:.2e}' + ('' if yard is None else f' (f32 {yard:.2e})') for nm, err, bar, yard in log))
 
@@ -636,7 +668,8 @@ def test_edge_attention_is_deterministic():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('B,n,NH,Cc,p', [(7, 200, 2, 208, 0.0), (3, 37, 4, 32, 0.0), (5, 200, 2, 208, 0.3), (2, 1024, 1, 256, 0.1)])
+@pytest.mark.parametrize('B,n,NH,Cc,p', [(7, 200, 2, 208, 0.0), (3, 37, 4, 32, 0.0), (5, 200, 2, 208, 0.3), (2, 1024, 1, 256, 0.1),
+                                         (3, 37, 2, 256, 0.3)])  # d = 256 with the reference's two pooling heads
 def test_pool_attention_forward_backward(B, n, NH, Cc, p):
     g = torch.Generator().manual_seed(B * 100 + n)
     u, c = torch.randn(B, NH, Cc, generator=g) * 0.3, torch.randn(B, NH, generator=g)
@@ -685,7 +718,8 @@ def test_gather_plan_kernels_equal_the_torch_path(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize('B,n,NH,DP,dv,Ds,d,p1,p2', [(7, 200, 2, 208, 100, 1024, 200, 0.0, 0.0), (5, 200, 2, 208, 100, 1024, 200, 0.1, 0.2),
                                                      (3, 37, 4, 32, 8, 20, 32, 0.3, 0.0), (2, 300, 1, 256, 64, 0, 100, 0.0, 0.4),
-                                                     (320, 200, 2, 208, 100, 768, 200, 0.1, 0.2)])
+                                                     (320, 200, 2, 208, 100, 768, 200, 0.1, 0.2),
+                                                     (3, 37, 2, 256, 128, 40, 256, 0.1, 0.2)])  # d = DP = NH dv = 256 = HEAD_T (csrc/pool.hip)
 def test_head_post_forward_backward(B, n, NH, DP, dv, Ds, d, p1, p2):
     """qagnn_head_post_{fwd,bwd}_f32 + qagnn_add_row0_f32 against the float64 emulation (same counter-based masks)."""
     g = torch.Generator().manual_seed(B * 100 + n + NH)
@@ -720,23 +754,27 @@ def test_head_post_forward_backward(B, n, NH, DP, dv, Ds, d, p1, p2):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name,HP,mode', [('csqa_b10', 52, 'train'), ('csqa_b10', 52, 'eval'), ('small_train', 8, 'train'),
-                                          ('rand_hub', 52, 'train_noact'), ('medqa_b8', 52, 'train_noS'), ('big', 52, 'train'),
-                                          ('big_pad', 52, 'train'), ('degree_ladder', 52, 'train')])
-def test_fused_hop_equals_composed_path(name, HP, mode, monkeypatch):
+@pytest.mark.parametrize('name,HP,dh,mode',
+                         # (the cases from before the width ladder keep their ids, name-HP-mode)
+                         [pytest.param(nm, HP, _DH_OF_PITCH[HP], mode, id=f'{nm}-{HP}-{mode}') for nm, HP, mode in (
+                             ('csqa_b10', 52, 'train'), ('csqa_b10', 52, 'eval'), ('small_train', 8, 'train'), ('rand_hub', 52, 'train_noact'),
+                             ('medqa_b8', 52, 'train_noS'), ('big', 52, 'train'), ('big_pad', 52, 'train'), ('degree_ladder', 52, 'train'))] +
+                         # the ends of the admitted range and d = 128 (pairs of WIDTH_LADDER; SP = roundup(2 HP, 16))
+                         [pytest.param(nm, HP, dh, 'train', id=f'{nm}-{HP}x{dh}-train') for nm in ('rand_small', 'degree_ladder')
+                          for HP, dh in ((4, 3), (32, 32), (64, 63), (64, 64))])
+def test_fused_hop_equals_composed_path(name, HP, dh, mode, monkeypatch):
     """qagnn_hop_{fwd,bwd}_f32 (csrc/hop.hip) sequences the library's own launchers: every forward buffer, every gradient and
     the BatchNorm running buffers must be BIT-identical to composing the per-kernel entry points from Python
     (ops.hop_*_composed, the definition of the hop that the host-logic tests hold against the oracle)."""
     from qagnn_amd import ops
-    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5)
+    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5, dh)
     K = hip()
     monkeypatch.setattr(K, 'gemm_split', 1)  # (the three-MFMA form lives in the native hop only: test_native_hop_in_the_three_mfma_form)
     dev = 'cuda'
     g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
     gen = torch.Generator().manual_seed(77)
     N, DP, C = nt.numel(), 4 * HP, R * T * T + T
-    dh = {52: 50, 8: 8}[HP]
-    SP = 0 if mode == 'train_noS' else (112 if HP == 52 else 16)
+    SP = 0 if mode == 'train_noS' else side_width(HP)
     rnd = lambda *shape, s=0.3: (torch.randn(*shape, generator=gen) * s).to(dev)  # noqa: E731
     Wx_t, Ws_t = rnd(DP, 3 * DP, s=0.1), (rnd(SP, 3 * DP, s=0.1) if SP else None)
     W1t, W2t = rnd(DP, DP, s=0.1), rnd(DP, DP, s=0.1)
@@ -1168,7 +1206,10 @@ def test_gemm_nn_three_mfma_form(M, K1, K2, No, variant, kind):
 TN_H2_SHAPES = [pytest.param(*v, id='-'.join(map(str, v[:4])) + ('' if v[4] == 'form' or v[0] == 700 else '-fallback')) for v in (
     (64000, 208, 112, 624, 'form'), (64000, 208, 0, 208, 'form'), (20000, 208, 0, 624, 'form'), (5000, 112, 0, 624, 'form'),
     (2049, 208, 0, 208, 'form'), (12800, 208, 208, 208, 'form'), (700, 32, 0, 96, 'fallback: 700 rows, 32 columns of A, 96 of B'),
-    (1, 208, 0, 208, 'fallback: 1 row'), (60, 208, 112, 624, 'fallback: 60 rows'), (257, 624, 0, 208, 'fallback: 257 rows'))]
+    (1, 208, 0, 208, 'fallback: 1 row'), (60, 208, 112, 624, 'fallback: 60 rows'), (257, 624, 0, 208, 'fallback: 257 rows'),
+    # d = 256: >= 1024 rows, >= 64 columns of every A, >= 104 of B -- the split kernels take both (tools/gemm_routes.py: 'two operands, 10
+    # subgraphs' and 'split, 32-row chunks' are the same routes at d = 200)
+    (2000, 256, 128, 768, 'form'), (2000, 256, 0, 256, 'form'))]
 
 
 @pytest.mark.gpu
@@ -1273,28 +1314,32 @@ def test_gemm_tn_reduced_precision_form(R, Ka1, Ka2, No, kind, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['big', 'big_pad', 'csqa_b10-everywhere', 'small_train-everywhere', 'degree_ladder-everywhere'])
+@pytest.mark.parametrize('name', ['big', 'big_pad', 'csqa_b10-everywhere', 'small_train-everywhere', 'degree_ladder-everywhere',
+                                  'degree_ladder-everywhere-64x64', 'degree_ladder-everywhere-32x32'])
 def test_native_hop_in_the_three_mfma_form(name, monkeypatch):
     """The natively sequenced hop with gemm_split = 2 (every large product in the three-MFMA form, the operand maxima travelling from the
     producing kernels) against the same hop with the exact 3 x bf16 products: every forward buffer and every gradient within fp32
     round-off of each other, none bit-identical (the form did run), everything finite; the amax words hold the true maxima.
     *-everywhere: a golden case's graph (2 000 / 120 node rows; d = 200 and d = 32) with the row threshold at 1 (helpers.form_everywhere);
-    degree_ladder (329 rows, d = 200): the per-node maxima of the edge kernels on their one-edge, register, chunked and hub rows."""
-    name, _, form = name.partition('-')
+    degree_ladder (329 rows, d = 200): the per-node maxima of the edge kernels on their one-edge, register, chunked and hub rows.
+    *-everywhere-64x64 / -32x32: the same at (HP, dh) = (64, 64) and (32, 32) (DP = 256, 128): no fused BatchNorm statistics outside 193 .. 208 columns, so no
+    bound of relu(bn(h1)) -- the second MLP product stays exact inside an otherwise three-MFMA hop (the `bound == 0.0` branch below)."""
+    name, form, width = (name.split('-') + ['', ''])[:3]
+    HP = 8 if name == 'small_train' else 52
+    HP, dh = map(int, width.split('x')) if width else (HP, _DH_OF_PITCH[HP])
     hip()
     with (helpers.form_everywhere() if form else contextlib.nullcontext()):
-        _native_hop_vs_exact(name, bool(form), monkeypatch)
+        _native_hop_vs_exact(name, bool(form), monkeypatch, HP, dh)
 
 
-def _native_hop_vs_exact(name, small, monkeypatch):
+def _native_hop_vs_exact(name, small, monkeypatch, HP, dh):
     from qagnn_amd import ops
-    HP = 8 if name == 'small_train' else 52
-    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5)
+    (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5, dh)
     K = ops.kernels()
     dev = 'cuda'
     g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
     gen = torch.Generator().manual_seed(78)
-    N, DP, C, SP = nt.numel(), 4 * HP, R * T * T + T, 112 if HP == 52 else 16
+    N, DP, C, SP = nt.numel(), 4 * HP, R * T * T + T, side_width(HP)
     assert (N >= 8192) != small and K.PACK_MIN_M == (1 if small else 8192)
     rnd = lambda *shape, s=0.3: (torch.randn(*shape, generator=gen) * s).to(dev)  # noqa: E731
     Wx_t, Ws_t, W1t, W2t = rnd(DP, 3 * DP, s=0.1), rnd(SP, 3 * DP, s=0.1), rnd(DP, DP, s=0.1), rnd(DP, DP, s=0.1)
@@ -1346,7 +1391,11 @@ def _native_hop_vs_exact(name, small, monkeypatch):
 # d = 64 (trunc_eval), incl. the hop MLP's (DP, 0, DP) at d = 32 and 64; K1 = 16 < 32 (one partial k-tile).  Row counts around the 128 / 256-row tiles, one row, and one below the default.
 SMALL_M = [1, 60, 255, 256, 257, 2000, 8191]
 GOLDEN_TRIPLES = [(208, 112, 624), (208, 208, 208), (624, 0, 208), (208, 0, 208), (32, 16, 96), (32, 0, 32), (96, 0, 16), (16, 0, 16),
-                  (64, 32, 192), (64, 0, 64)]
+                  (64, 32, 192), (64, 0, 64),
+                  # the same products of a hop -- projection [DP | SP] -> 3 DP, its two data gradients 3 DP -> DP and 3 DP -> SP, the MLP's
+                  # DP -> DP -- at the widths of the ladder, SP = roundup(2 HP, 16): d = 256, 240, 128, 16 ((16, 0, 16) is above)
+                  (256, 128, 768), (768, 0, 256), (768, 0, 128), (256, 0, 256), (240, 128, 720), (720, 0, 240), (720, 0, 128), (240, 0, 240),
+                  (128, 64, 384), (384, 0, 128), (384, 0, 64), (128, 0, 128), (16, 16, 48), (48, 0, 16)]
 
 
 @pytest.fixture

@@ -135,18 +135,22 @@ def _case_args(case_dict):
 RUN_SCRIPT_DROPOUT = dict(p_emb=0.2, p_gnn=0.2, p_fc=0.2, p_attn=0.1, p_pool=0.1)
 
 
-def oracle_vs_package(case_dict, device=None, dropout=None):
+def oracle_vs_package(case_dict, device=None, dropout=None, seen=None):
     """Same seeded inputs through the package (HIP kernels through the C ABI) and through the CPU oracle: forward values against
     the fp32 oracle at FWD, every gradient against the float64 yardstick (helpers.F64Ref).
 
     dropout = dict(p_emb, p_gnn, p_fc, p_attn, p_pool): the package runs its train-mode step with these rates; the seeds its ten dropout
     sites draw are recorded, their keep masks recomputed on the host (the kernels' counter hash) and installed in the oracle, which then
-    computes the same function -- the configuration bench.py times, held to the same bars as the p = 0 cases."""
+    computes the same function -- the configuration bench.py times, held to the same bars as the p = 0 cases.
+
+    seen: a dict that receives the package model under 'model' (for assertions on the branches its forward took)."""
     device = device or DEVICE
     args, _ = _case_args(case_dict)
     cfg = case_dict['cfg']
     B, n = case_dict['nq'] * case_dict['nc'], case_dict['n']
     model = _package_model(case_dict, device, dropout)
+    if seen is not None:
+        seen['model'] = model
     dargs = [a.to(device) for a in args]
     with helpers.SeedRecorder() as rec, helpers.recorded_forward(cfg['concept_dim']) as relu_in:
         logits, attn = model(*dargs[:5], (dargs[5], dargs[6]))
@@ -170,12 +174,51 @@ def oracle_vs_package(case_dict, device=None, dropout=None):
     return ref.check_all(grads, what=f"{case_dict['shape']} B={B}{tag} grad::", min_checked=20, **helpers.kink_args(relu_in, cfg, args[5], args[6], args[2]))
 
 
-@pytest.mark.parametrize('train,form', helpers.with_forms([True, False]), indirect=['form'])
-def test_oracle_parity_odd_shapes(train, form):
-    """d = 100 (dim_per_head 25, the parser default gnn_dim), n = 37 node slots, 3 layers, ragged tiny graphs."""
-    case = dict(shape='tiny', nq=3, nc=4, n=37, n_rel=17, std=0.6, train=train, seed=31,
-                cfg=helpers.model_cfg(d=100, k=3, sent_dim=40, n_concept=500, concept_in_dim=24))
-    oracle_vs_package(case)
+# d -> (L.HP, L.ones_col, the stack's _tab_col): the width-dependent branches of the Python layer that the tiny case takes at each d.
+# ones_col = -1: no pad column for the ones of relu(bn(h1)), db2 by column reduction; _tab_col = -1: no room in S's padding for the node-type
+# indicators (roundup(d / 2, 16) - d / 2 < n_ntype = 4), dTT by grouped column reduction.  d = 100, the width this test started with, takes
+# neither; the rest is the width ladder of tests/test_head_widths.py.
+WIDTH_BRANCHES = {100: (28, 25, 50), 16: (4, -1, 8), 128: (32, -1, -1), 240: (60, -1, 120), 252: (64, 63, -1), 256: (64, -1, -1)}
+
+
+def tiny_case(d, train, seed=31, concept_in_dim=24):
+    """nq = 3, nc = 4, n = 37 node slots, 3 layers, ragged tiny graphs (dim_per_head = d / 4)"""
+    return dict(shape='tiny', nq=3, nc=4, n=37, n_rel=17, std=0.6, train=train, seed=seed,
+                cfg=helpers.model_cfg(d=d, k=3, sent_dim=40, n_concept=500, concept_in_dim=concept_in_dim))
+
+
+def check_width_branches(d, model):
+    """the branches the case at width d is meant to take (WIDTH_BRANCHES), read off the layout and the stack after a forward"""
+    L = ops.HeadLayout(d, 'cpu')
+    (tab_col,) = {m._tab_col for m in model.modules() if hasattr(m, '_tab_col')}
+    assert (L.HP, L.ones_col, tab_col) == WIDTH_BRANCHES[d], (d, L.HP, L.ones_col, tab_col)
+
+
+def _report_line(label, report):
+    worst = max(report, key=report.get)
+    print(f'FIGURE {label}: {len(report)} gradient tensors on the float64 yardstick, worst {report[worst]:.2e} of scale ({worst})')
+
+
+# (the d = 100 cases keep the ids they had before the width axis: True, True-everywhere, False, False-everywhere)
+@pytest.mark.parametrize('d,train,form', [pytest.param(d, t, f, id=('' if d == 100 else f'd{d}-') + str(t) + ('' if f == 'default' else '-' + f))
+                                          for d in WIDTH_BRANCHES for t in (True, False) for f in helpers.FORMS], indirect=['form'])
+def test_oracle_parity_odd_shapes(d, train, form):
+    """d = 100 (dim_per_head 25, the parser default gnn_dim), n = 37 node slots, 3 layers, ragged tiny graphs -- and the same case at the
+    widths of the ladder: d = 16 (HP = 4), 128, 240, 252 (HP = 64 with one pad column) and 256 (HP = dh = 64: DP = d, NH dv = 256)."""
+    seen = {}
+    report = oracle_vs_package(tiny_case(d, train), seen=seen)
+    check_width_branches(d, seen['model'])
+    _report_line(f'module[d={d}-{"train" if train else "eval"}-{form}]', report)
+
+
+@pytest.mark.parametrize('form', helpers.FORMS, indirect=True)
+def test_oracle_parity_dropout_at_d256(form):
+    """The dropout rates of the run scripts at d = 256: the keep-mask index spaces of the hop (N x DP with DP = d = 256: no pad column to
+    skip) and of the pooler (NH dv = 256) replayed on the oracle, at the bars of the p = 0 cases."""
+    seen = {}
+    report = oracle_vs_package(tiny_case(256, True, seed=33, concept_in_dim=32), dropout=RUN_SCRIPT_DROPOUT, seen=seen)
+    check_width_branches(256, seen['model'])
+    _report_line(f'module[d=256-dropout-{form}]', report)
 
 
 @pytest.mark.parametrize('train,form', helpers.with_forms([True, False]), indirect=['form'])
@@ -989,7 +1032,9 @@ def test_module_parity_under_the_non_default_kernel_families(env):
     if os.environ.get('QAGNN_VARIANT_CHILD'):
         pytest.skip('already inside a variant run')
     child_env = dict(os.environ, QAGNN_VARIANT_CHILD='1', **dict(kv.split('=') for kv in env.split()))
-    sel = ('test_qagnn_matches_reference and (csqa_b10 or sapbert_b4 or small_train) or test_oracle_parity_odd_shapes or '
+    # (of the width ladder of test_oracle_parity_odd_shapes the child takes d = 256 only, next to d = 100: the run stays inside its time)
+    sel = ('test_qagnn_matches_reference and (csqa_b10 or sapbert_b4 or small_train) or '
+           'test_oracle_parity_odd_shapes and not ([d16- or [d128- or [d240- or [d252-) or '  # (whole id prefixes: "[d16-", never a substring)
            'test_message_passing_stack_matches_reference and (medqa_b8 or roberta_b5)')
     r = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-m', 'gpu', '-q', '-x', '-p', 'no:cacheprovider', '-k', sel],
                        env=child_env, cwd=helpers.ROOT, capture_output=True, text=True, timeout=800)

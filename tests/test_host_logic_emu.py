@@ -426,14 +426,17 @@ def test_emb_data_and_cache_output_on_cpu():
     T.emb_data_and_cache_output_vs_oracle(device='cpu')
 
 
-@pytest.mark.parametrize('train', [True, False])
-def test_gpu_parity_harness_on_cpu(train):
+# (the d = 100 cases keep the ids they had before the width axis: True, False)
+@pytest.mark.parametrize('d,train', [pytest.param(d, t, id=('' if d == 100 else f'd{d}-') + str(t))
+                                     for d in (100, 16, 128, 240, 252, 256) for t in (True, False)])
+def test_gpu_parity_harness_on_cpu(d, train):
     """The oracle-vs-package harness of tests/test_hip_parity.py (forward at FWD, gradients on the float64 yardstick), run here
-    with the torch emulation of the kernels: checks the harness and the host logic on an odd-sized case outside the fixtures."""
+    with the torch emulation of the kernels: checks the harness and the host logic on an odd-sized case outside the fixtures, at d = 100
+    and at the widths of the ladder (tests/test_head_widths.py) with the branch each is meant to take (T.WIDTH_BRANCHES)."""
     import test_hip_parity as T
-    case = dict(shape='tiny', nq=3, nc=4, n=37, n_rel=17, std=0.6, train=train, seed=31,
-                cfg=helpers.model_cfg(d=100, k=3, sent_dim=40, n_concept=500, concept_in_dim=24))
-    report = T.oracle_vs_package(case, device='cpu')
+    seen = {}
+    report = T.oracle_vs_package(T.tiny_case(d, train), device='cpu', seen=seen)
+    T.check_width_branches(d, seen['model'])
     assert len(report) > 20 and max(report.values()) < 1e-3
 
 
