@@ -289,6 +289,9 @@ int qagnn_gemm_tn_colsum_f32(const float* A, int32_t lda, const float* B, int32_
  *   mode 2: out[0][c] = sum_r dY[r][c],  out[1][c] = sum_r dY[r][c] * (H[r][c]-mean[c])*invstd[c]
  *           with dY = dR * [H*scale+shift > 0]   (BatchNorm+ReLU backward reductions; X = dR, X2 = H)
  * workspace: qagnn_colreduce_workspace_elems floats.  ldx >= Cc, ldx2 >= Cc (mode 2); `out` is [groups or 1 or 2][Cc], contiguous.
+ * Any R > 0: the launch shape is chosen from R alone (8 rows per wave below 32 768 rows, 32 from there on), so every pass over the same
+ * rows -- qagnn_bn_relu_bwd_colsum_f32's by-product included -- sums in one order; the row counts where that shape, a ragged last block,
+ * the final sum's partitions and the tile merge of qagnn_bn_stats_finalize_f32 change are held by tests/test_row_counts.py.
  * ------------------------------------------------------------------------------------------------------------ */
 int64_t qagnn_colreduce_workspace_elems(int32_t R, int32_t Cc, int32_t groups);
 int qagnn_colreduce_f32(int32_t mode, const float* X, int32_t ldx, const float* X2, int32_t ldx2, int32_t R, int32_t Cc,

@@ -289,6 +289,9 @@ template <bool BWD>
 __device__ __forceinline__ float4 gelu_dropout_one(const float* __restrict__ X, const float* __restrict__ dY, int64_t i, float p, uint64_t seed, float inv) {
   return gelu_dropout_val<BWD>(ld4(X + i * 4), BWD ? ld4(dY + i * 4) : make_float4(1.f, 1.f, 1.f, 1.f), i, p, seed, inv);
 }
+// The backward has ONE instantiation, the AMAX one (amax_part == nullptr: the plain call, no maxima left): as two, the compiler contracted
+// gelu_grad_f differently in each (28 against 30 fused multiply-adds per float4) and the plain form's dX was an ulp away from the AMAX
+// form's, the one the training step runs (tests/test_row_counts.py: test_gelu_dropout_at_the_element_count_edges).
 template <bool BWD, bool AMAX = false>
 __global__ __launch_bounds__(256) void k_gelu_dropout(const float* __restrict__ X, const float* __restrict__ dY, float* __restrict__ out, int64_t n4,
                                                       float p, uint64_t seed, const unsigned long long* __restrict__ epoch,
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(256) void k_gelu_dropout(const float* __restrict__ 
     const float m = wave_amax_lane63(absmax4(o));
     if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) amax_part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (threadIdx.x == 0 && amax_part) amax_part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   }
 }
 
@@ -577,7 +580,7 @@ int launch_gelu_dropout(const float* X, const float* dY, float* out, int64_t n, 
   if (amax && !amax_part) { set_error("gelu_dropout: the maximum needs its scratch"); return QAGNN_EINVAL; }
   if (dY) {
     if (amax) k_gelu_dropout<true, true><<<grid, 256, 0, stream>>>(X, dY, out, n / 4, p, seed, seed_epoch_ptr(), amax_part);
-    else k_gelu_dropout<true><<<grid, 256, 0, stream>>>(X, dY, out, n / 4, p, seed, seed_epoch_ptr());
+    else k_gelu_dropout<true, true><<<grid, 256, 0, stream>>>(X, dY, out, n / 4, p, seed, seed_epoch_ptr(), nullptr);
   } else {
     if (amax) k_gelu_dropout<false, true><<<grid, 256, 0, stream>>>(X, nullptr, out, n / 4, p, seed, seed_epoch_ptr(), amax_part);
     else k_gelu_dropout<false><<<grid, 256, 0, stream>>>(X, nullptr, out, n / 4, p, seed, seed_epoch_ptr());

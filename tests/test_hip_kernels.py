@@ -111,7 +111,11 @@ GRAPH_CASES = [('big_pad', lambda: padded_graph(7, 320, 200, 128, 400000)), ('ra
                ('medqa_classes', lambda: rand_graph(5, 3000, 40000, R=34)), ('big', lambda: rand_graph(6, 64000, 400000)),
                ('degree_ladder', degree_ladder), ('class_ladder', class_ladder),
                # E' = 66 000 >= 65 536: the 1024-thread launch of k_cls_reduce (csrc/edge_attn.hip) on a graph small enough for every width
-               ('rand_64k', lambda: rand_graph(8, 2000, 64000))]
+               ('rand_64k', lambda: rand_graph(8, 2000, 64000)),
+               # N within one of a round of block_exclusive_scan (1024 threads x SCAN_ITEMS = 8192 entries, csrc/graph_prep.hip), and one past
+               # the row count where the column reductions change form (32 768, csrc/elementwise.hip) with N % 4 == 1: tests/test_row_counts.py
+               ('rand_8191', lambda: rand_graph(8191, 8191, 20000)), ('rand_8192', lambda: rand_graph(8192, 8192, 20000)),
+               ('rand_8193', lambda: rand_graph(8193, 8193, 20000)), ('rand_33k', lambda: rand_graph(9, 32769, 100000))]
 
 
 def golden_graph(case):
@@ -266,7 +270,10 @@ def test_gemm_nn(M, K1, K2, No, variant, split):
 @pytest.mark.parametrize('R,Ka,No', [(5000, 208, 208), (1030, 624, 208), (2049, 208, 624), (100, 112, 112), (64000, 208, 208), (7, 32, 96),
                                      (4100, 112, 624), (3000, 200, 204), (2080, 612, 208), (1500, 64, 104),
                                      # d = 256 (Ka = 256: a 208-row block plus a 48-row one), d = 240, d = 16
-                                     (2000, 256, 256), (2000, 256, 768), (1500, 240, 720), (2000, 16, 48)])
+                                     (2000, 256, 256), (2000, 256, 768), (1500, 240, 720), (2000, 16, 48),
+                                     # at and next to the row counts where the route changes family (R >= 1024, tn_split_ok) and its
+                                     # shortest chunk (R > 4096, tn_min_chunk; csrc/gemm_dispatch.hip)
+                                     (1023, 208, 208), (1024, 208, 208), (1025, 208, 208), (4095, 208, 208), (4096, 208, 208), (4097, 208, 208)])
 @pytest.mark.parametrize('affine', [False, True])
 def test_gemm_tn(R, Ka, No, affine):
     g = torch.Generator().manual_seed(R + Ka)
@@ -293,7 +300,8 @@ def test_gemm_tn(R, Ka, No, affine):
 @pytest.mark.gpu
 @pytest.mark.parametrize('R,Ka1,Ka2,No', [(64000, 208, 112, 624), (2000, 208, 112, 624), (12800, 208, 208, 208), (5000, 208, 16, 624),
                                           (700, 32, 16, 96), (1500, 100, 112, 208),
-                                          (2000, 256, 128, 768), (2000, 240, 128, 720), (2000, 16, 16, 48)])  # d = 256, 240, 16
+                                          (2000, 256, 128, 768), (2000, 240, 128, 720), (2000, 16, 16, 48),  # d = 256, 240, 16
+                                          (1024, 208, 112, 624), (4097, 208, 112, 624)])  # the first split row count; the first long-chunk one
 def test_gemm_tn_two_operands(R, Ka1, Ka2, No):
     """qagnn_gemm_tn2_f32: [A1 | A2]^T B in one launch (the merged bf16-split launch where both shapes qualify, two plain calls
     otherwise) == the two products, on the fp32 backward-error bound of test_gemm_tn; rows past the operands' widths never leak."""
@@ -641,7 +649,7 @@ def print_figures(label, log):
 @pytest.mark.parametrize('name,HP', [('csqa_b10', 52), ('medqa_b8', 52), ('small_train', 8), ('rand_hub', 52), ('rand_small', 28),
                                      ('no_edges', 16), ('one_node', 52), ('big', 52), ('big_pad', 52),
                                      ('degree_ladder', 52), ('degree_ladder', 8), ('degree_ladder', 28), ('class_ladder', 52),
-                                     ('class_ladder', 16)])
+                                     ('class_ladder', 16), ('rand_33k', 52)])
 def test_edge_attention_forward_backward(name, HP):
     case = edge_case(name, HP)
     log = []
@@ -758,7 +766,9 @@ def test_head_post_forward_backward(B, n, NH, DP, dv, Ds, d, p1, p2):
                          # (the cases from before the width ladder keep their ids, name-HP-mode)
                          [pytest.param(nm, HP, _DH_OF_PITCH[HP], mode, id=f'{nm}-{HP}-{mode}') for nm, HP, mode in (
                              ('csqa_b10', 52, 'train'), ('csqa_b10', 52, 'eval'), ('small_train', 8, 'train'), ('rand_hub', 52, 'train_noact'),
-                             ('medqa_b8', 52, 'train_noS'), ('big', 52, 'train'), ('big_pad', 52, 'train'), ('degree_ladder', 52, 'train'))] +
+                             ('medqa_b8', 52, 'train_noS'), ('big', 52, 'train'), ('big_pad', 52, 'train'), ('degree_ladder', 52, 'train'),
+                             # N = 32 769: every reduction of the hop in its big form with a one-row last block (tests/test_row_counts.py)
+                             ('rand_33k', 52, 'train'))] +
                          # the ends of the admitted range and d = 128 (pairs of WIDTH_LADDER; SP = roundup(2 HP, 16))
                          [pytest.param(nm, HP, dh, 'train', id=f'{nm}-{HP}x{dh}-train') for nm in ('rand_small', 'degree_ladder')
                           for HP, dh in ((4, 3), (32, 32), (64, 63), (64, 64))])
@@ -1006,7 +1016,7 @@ def test_node_prep_on_unquantised_scores():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('M', [64000, 2000, 129, 77])
+@pytest.mark.parametrize('M', [64000, 2000, 129, 77, 8065, 8193])  # (the last two: 64 and 65 tiles with a one-row last tile)
 def test_gemm_column_statistics_and_bn_stats_finalize(M):
     """BatchNorm batch statistics as a by-product of the GEMM that writes the BatchNorm input (qagnn_gemm_nn_args.colstat_part:
     per 128-row tile x0 | S1 | S2) + qagnn_bn_stats_finalize_f32 (pairwise combination of the tiles, invstd / scale / shift, running
