@@ -18,6 +18,10 @@
  *     H must be 4 (the reference hard-codes head_count=4, modeling_qagnn.py:387) and dh <= 64.  In short H = 4, HP % 4 == 0, dh <= 64:
  *     held at the edges of that range (HP = 4 .. 64) by tests/test_head_widths.py; the edge kernels and the hop refuse any other pitch
  *     before anything is enqueued.
+ *   - node types and edge classes: T node types, R relations, C = R*T*T + T edge classes.  Graph preparation and the edge kernels take any
+ *     R > 0, T > 0 with C <= 8192 (more: QAGNN_EUNSUPPORTED before anything is launched); the hop and the grouped column reductions
+ *     (qagnn_colreduce_f32 mode 0, the bsum by-product of qagnn_gemm_tn_colsum_f32) take T, `groups` in 1 .. 4.  Held at T = 1 .. 4 and at
+ *     C = 2 .. 8192 by tests/test_class_counts.py.
  *   - row pitches (lda*, ldb*, ldn*, ldc, ldt, ldx*, ld, ldk, lde, ldg, lddk, ldh, ldp, ld_sub): in floats, a multiple of 4, every row
  *     16-byte aligned, and EVERY PITCH >= THE WIDTH IT STRIDES; a pitch below its width is QAGNN_EINVAL before anything is launched.  A
  *     pitch above the width is a view into a larger buffer: no entry point reads or writes a float outside the rows x width it was

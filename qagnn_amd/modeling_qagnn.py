@@ -87,6 +87,18 @@ def edge_class_features(n_etype, n_ntype, device, dtype=torch.float32):
     return _CLASS_FEATS[key]
 
 
+MAX_NTYPE, MAX_EDGE_CLASSES = 4, 8192  # what libqagnn_hip admits (include/qagnn_hip.h: T in 1..4 for the hop, R*T*T + T <= 8192 edge classes)
+
+
+def check_type_counts(n_ntype, n_etype):
+    """Raise where the kernels would refuse (or, on another provider, where nothing would): the counts are fixed at construction."""
+    if not 1 <= n_ntype <= MAX_NTYPE:
+        raise NotImplementedError(f'n_ntype={n_ntype}: the hop kernels handle 1..{MAX_NTYPE} node types (the reference value is 4)')
+    if n_etype < 1 or n_etype * n_ntype * n_ntype + n_ntype > MAX_EDGE_CLASSES:
+        raise NotImplementedError(f'n_etype={n_etype}, n_ntype={n_ntype}: {n_etype * n_ntype * n_ntype + n_ntype} edge classes; '
+                                  f'the graph preparation handles 2..{MAX_EDGE_CLASSES}')
+
+
 def _edge_class_features(n_etype, n_ntype, device):
     """Input rows of the edge encoder for every edge class (the one-hot concat of modeling_qagnn.py:419-433).
 
@@ -204,6 +216,7 @@ class GATConvE(nn.Module):
             raise NotImplementedError('only aggr="add" (the reference default) is implemented')
         if head_count != ops.H_HEADS:
             raise NotImplementedError('the edge kernels are written for head_count=4 (the reference value)')
+        check_type_counts(n_ntype, n_etype)
         self.args = args
         assert emb_dim % 2 == 0
         self.emb_dim = emb_dim
@@ -344,6 +357,7 @@ class QAGNN_Message_Passing(nn.Module):
         super().__init__()
         assert input_size == output_size
         self.args = args
+        check_type_counts(n_ntype, n_etype)
         self.n_ntype, self.n_etype = n_ntype, n_etype
         assert input_size == hidden_size
         self.hidden_size = hidden_size

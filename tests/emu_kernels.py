@@ -14,7 +14,9 @@ CLS_CHUNK, CLS_BLK, CLS_GROUPS = 64, 1024, 32  # QAGNN_CLS_CHUNK, CLS_BLK (graph
 class EmuGraph:
     """Same arrays, same canonical order (group key, then edge id) as qagnn_graph_prep."""
 
-    def __init__(self, edge_index, edge_type, node_type, R, T, block_n=0):
+    def __init__(self, edge_index, edge_type, node_type, R, T, block_n=0, e_cap=None):
+        """e_cap: the edge CAPACITY the library lays the arrays out for (qagnn_graph_prep_cap, qagnn_graph_from_blobs with a capacity): the
+        position groups, and with them n_groups, chunkptr's length and max_chunks, follow E_cap + N; every array holds the true E + N edges."""
         self.block_n = block_n
         dev = node_type.device
         N, E = node_type.numel(), edge_index.size(1)
@@ -37,7 +39,9 @@ class EmuGraph:
         self.src_t, self.cls_t, self.pos_t = es[eid_t].int(), ec[eid_t].int(), srcpos[eid_t].int()
         self.tgt_t = et[eid_t].int()
         # class order: (position group, class)-major -- a group is gb consecutive 1024-position blocks of the source order
-        nblk = (self.Ep + CLS_BLK - 1) // CLS_BLK
+        cap_p = self.Ep if e_cap is None else e_cap + N
+        assert cap_p >= self.Ep
+        nblk = (cap_p + CLS_BLK - 1) // CLS_BLK
         gb = max(1, (nblk + CLS_GROUPS - 1) // CLS_GROUPS)
         self.n_groups = (nblk + gb - 1) // gb
         grp = (torch.arange(self.Ep, device=dev) // CLS_BLK) // gb
@@ -52,12 +56,28 @@ class EmuGraph:
         nch = (gc_cnt + CLS_CHUNK - 1) // CLS_CHUNK
         self.chunkptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), nch.cumsum(0)]).int()
         self.n_chunks = int(nch.sum())
-        self.max_chunks = self.Ep // CLS_CHUNK + pairs + 1
+        self.max_chunks = cap_p // CLS_CHUNK + pairs + 1
         pair_of_chunk = torch.repeat_interleave(torch.arange(pairs, device=dev), nch)
         within = torch.arange(self.n_chunks, device=dev) - self.chunkptr.long()[pair_of_chunk]
         self.chunk_cls = (pair_of_chunk % self.C).int()
         self.chunk_beg = (gcptr[pair_of_chunk] + within * CLS_CHUNK).int()
         self.chunk_len = torch.minimum(torch.full_like(within, CLS_CHUNK), gcptr[pair_of_chunk + 1] - self.chunk_beg.long()).int()
+
+    def xcd_base(self):
+        """k_xcd_partition (csrc/graph_prep.hip), the words err[4 .. 12]: eight contiguous runs of 4-node blocks, each an eighth of the work
+        4 rowptr_s[i] - 3 i, none longer than edge_xcd_cap(N) = 1.25 equal shares"""
+        N, rp = self.N, self.rowptr_s.tolist()
+        nbk = (N + 3) >> 2
+        cap = ((((nbk + 7) >> 3) * 5) + 3) >> 2
+        work = lambda lb: 4 * rp[min(4 * lb, N)] - 3 * min(4 * lb, N)  # noqa: E731
+        W, base, prev = 4 * rp[N] - 3 * N, [0], 0
+        for k in range(1, 8):
+            target = (W * k + 7) // 8
+            b = next(lb for lb in range(nbk + 1) if lb == nbk or work(lb) >= target)
+            b = max(max(min(b, prev + cap), nbk - (8 - k) * cap), prev)
+            base.append(b)
+            prev = b
+        return base + [nbk]
 
 
 def _chk(*tensors):

@@ -226,11 +226,11 @@ def test_edge_attention_refuses_a_pitch_outside_the_range(HP):
     assert all(bool((t == CANARY).all()) for t in outs), 'the refused backward wrote to an output'
 
 
-def _canaried_hop(K, g, nt, HP, backward):
-    """a complete qagnn_hop_args at pitch HP on graph g whose every output, saved buffer and workspace holds the canary
-    -> (struct, the canaried tensors, everything that must stay alive)"""
+def _canaried_hop(K, g, nt, HP, backward, T=4):
+    """a complete qagnn_hop_args at pitch HP (and a node-type table of T rows) on graph g whose every output, saved buffer and workspace
+    holds the canary -> (struct, the canaried tensors, everything that must stay alive)"""
     from qagnn_amd import _lib
-    DP, SP, T = 4 * HP, -(-2 * HP // 16) * 16, 4
+    DP, SP = 4 * HP, -(-2 * HP // 16) * 16
     gen = torch.Generator().manual_seed(HP)
     rnd = lambda *shape: (torch.randn(*shape, generator=gen) * 0.1).cuda()  # noqa: E731
     Wx_t, Ws_t, W1t, W2t = rnd(DP, 3 * DP), rnd(SP, 3 * DP), rnd(DP, DP), rnd(DP, DP)

@@ -297,6 +297,62 @@ def test_gemm_tn(R, Ka, No, affine):
         assert (cs.cpu().double() - ref_cs).abs().max().item() <= 8 * EPS * B.abs().sum(0).max().item() + 1e-6
 
 
+# The by-product variant never takes the bf16-split kernels (tn_route, csrc/gemm_dispatch.hip: `split = !r.colsum && ...`), so its kernel
+# follows from the widths alone: k_gemm_tn_strip where pick_nt(No) == 13 (No % 208 == 0) and pick_tn_waves(Ka) is 7, 13 or 16, else k_gemm_tn.
+#   (7, 32, 96)        k_gemm_tn, 2 column tiles (No % 32 == 0), one chunk of 7 rows
+#   (100, 112, 112)    k_gemm_tn, 7 column tiles
+#   (300, 112, 208)    k_gemm_tn_strip, 7 waves (Ka = 112)
+#   (1030, 624, 208)   k_gemm_tn_strip, 13 waves, three row blocks, a ragged last chunk
+#   (5000, 208, 208)   k_gemm_tn_strip, 13 waves, chunks of 256 rows (R > 4096)
+#   (1030, 256, 208)   k_gemm_tn_strip, 16 waves (Ka = 256)
+TN_GROUP_SHAPES = [(7, 32, 96), (100, 112, 112), (300, 112, 208), (1030, 624, 208), (5000, 208, 208), (1030, 256, 208)]
+GUARD = 7.0
+
+
+def check_grouped_sums(got_with_guard, ref, bar, groups, what):
+    """a [groups + 1, Cc] buffer: the first `groups` rows are the grouped column sums, contiguous; the last row is the guard, GUARD all over.
+    -> the worst error as a fraction of the bar"""
+    got = got_with_guard.detach().cpu()
+    assert got.shape == (groups + 1, ref.size(1)) and ref.shape == (groups, ref.size(1))
+    err = (got[:groups].double() - ref).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float('inf')), err).max().item()
+    assert err <= bar, f'{what}: grouped column sums off by {err:.3e}, bound {bar:.3e}'
+    assert bool((got[groups] == GUARD).all()), f'{what}: the row behind the {groups} group rows was written'
+    return err / bar
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('R,Ka,No', TN_GROUP_SHAPES)
+@pytest.mark.parametrize('affine', [False, True])
+@pytest.mark.parametrize('groups', [2, 3])
+def test_gemm_tn_group_counts(R, Ka, No, affine, groups):
+    """The bsum by-product of qagnn_gemm_tn_colsum_f32 at 2 and 3 groups (test_gemm_tn: 1 and 4), written into a [groups + 1, No] buffer
+    whose last row is a guard: the product inside test_gemm_tn's bound, bsum [groups, No] contiguous inside its column-sum bound, the guard
+    row untouched (a kernel that stored group g at a stride of 4 rows, or all 4 accumulators, would write it or leave rows unwritten)."""
+    from qagnn_amd._lib import _ptr
+    g = torch.Generator().manual_seed(R + Ka + groups)
+    A, B = torch.randn(R, Ka, generator=g), torch.randn(R, No, generator=g)
+    kw = dict(a_scale=torch.randn(Ka, generator=g), a_shift=torch.randn(Ka, generator=g)) if affine else {}
+    idx = (torch.arange(R) % groups)[torch.randperm(R, generator=g)]  # every group, also at R = 7
+    K = hip()
+    out, ws = K._tn_out_ws(R, Ka, No, None, 'cuda')
+    bsum = torch.full((groups + 1, No), GUARD, device='cuda')
+    Ac, Bc, ic = A.cuda(), B.cuda(), idx.cuda()
+    kwc = {k: v.cuda() for k, v in kw.items()}
+    rc = K.lib.qagnn_gemm_tn_colsum_f32(Ac.data_ptr(), Ka, Bc.data_ptr(), No, out.data_ptr(), No, R, Ka, No, _ptr(kwc.get('a_scale')),
+                                        _ptr(kwc.get('a_shift')), None, 0, bsum.data_ptr(), ic.data_ptr(), groups, ws.data_ptr(), K._stream())
+    torch.cuda.synchronize()
+    assert rc == 0, K.lib.qagnn_last_error().decode()
+    ref = EMU.gemm_tn(A.double(), B.double(), **{k: v.double() for k, v in kw.items()})
+    Ae = torch.relu(A * kw['a_scale'] + kw['a_shift']) if affine else A
+    bound = 16 * EPS * (Ae.abs().double().t() @ B.abs().double()) + 1e-6
+    err = (out.cpu().double() - ref).abs()
+    assert bool((err <= bound).all()), f'max err {err.max().item():.3e}, worst bound ratio {(err / bound).max().item():.2f}'
+    ratio = check_grouped_sums(bsum, EMU.colsum(B.double(), idx, groups), 8 * EPS * B.abs().sum(0).max().item() + 1e-6, groups, 'bsum')
+    print(f'FIGURE gemm_tn_groups[{R}x{Ka}x{No}, groups = {groups}, affine = {affine}]: product {(err / bound).max().item():.2e} | '
+          f'bsum {ratio:.2e} of the bounds')
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('R,Ka1,Ka2,No', [(64000, 208, 112, 624), (2000, 208, 112, 624), (12800, 208, 208, 208), (5000, 208, 16, 624),
                                           (700, 32, 16, 96), (1500, 100, 112, 208),
@@ -510,7 +566,12 @@ def side_width(HP):
     return 112 if HP == 52 else -(-2 * HP // 16) * 16
 
 
+EXTRA_GRAPHS = {}  # name -> builder of (ei, et, nt, R, T): graphs other test modules register for edge_inputs / edge_case (tests/test_class_counts.py)
+
+
 def _graph_of(case_or_name):
+    if case_or_name in EXTRA_GRAPHS:
+        return EXTRA_GRAPHS[case_or_name]()
     return dict(GRAPH_CASES)[case_or_name]() if case_or_name in dict(GRAPH_CASES) else golden_graph(case_or_name)
 
 
@@ -776,8 +837,16 @@ def test_fused_hop_equals_composed_path(name, HP, dh, mode, monkeypatch):
     """qagnn_hop_{fwd,bwd}_f32 (csrc/hop.hip) sequences the library's own launchers: every forward buffer, every gradient and
     the BatchNorm running buffers must be BIT-identical to composing the per-kernel entry points from Python
     (ops.hop_*_composed, the definition of the hop that the host-logic tests hold against the oracle)."""
-    from qagnn_amd import ops
     (ei, et, nt, R, T), _, _, _, qs = edge_inputs(name, HP, 5, dh)
+    fused_hop_vs_composed((ei, et, nt, R, T), qs, HP, dh, mode, monkeypatch)
+
+
+def fused_hop_vs_composed(graph, qs, HP, dh, mode, monkeypatch, tab_col=-1):
+    """The body of test_fused_hop_equals_composed_path on any graph (ei, et, nt, R, T): T rows of TT, R T^2 + T rows of Ek | Em.
+    tab_col >= 0: columns [tab_col, tab_col + T) of S hold the node-type indicators over zero rows of Ws_t (ops.type_indicators) and dTT
+    is those rows of dWs_t; -1: dTT by the grouped column reduction with groups = T.  -> the fused path's gradients."""
+    from qagnn_amd import ops
+    ei, et, nt, R, T = graph
     K = hip()
     monkeypatch.setattr(K, 'gemm_split', 1)  # (the three-MFMA form lives in the native hop only: test_native_hop_in_the_three_mfma_form)
     dev = 'cuda'
@@ -792,6 +861,11 @@ def test_fused_hop_equals_composed_path(name, HP, dh, mode, monkeypatch):
            W1t, W1t.t().contiguous(), rnd(DP), 1 + rnd(DP), rnd(DP), W2t, W2t.t().contiguous(), rnd(DP), rnd(DP), 0.5 + rnd(DP).abs())
     X, S, dy = rnd(N, DP, s=1.0), (rnd(N, SP, s=1.0) if SP else None), rnd(N, DP, s=1.0)
     ntype = nt.cuda()
+    if tab_col >= 0:
+        assert SP and tab_col + T <= SP
+        S[:, tab_col:tab_col + T] = torch.nn.functional.one_hot(ntype, T).float()
+        Ws_t[tab_col:tab_col + T] = 0
+        prm = prm[:3] + (Ws_t.t().contiguous(),) + prm[4:]
     batch_stats, apply_act = mode != 'eval', mode != 'train_noact'
     p, seed = (0.2, 12345) if apply_act else (0.0, 0)
     pos = torch.nonzero(torch.arange(DP) % HP < dh).flatten().to(dev)
@@ -801,7 +875,7 @@ def test_fused_hop_equals_composed_path(name, HP, dh, mode, monkeypatch):
                N / max(N - 1.0, 1.0)) if batch_stats else None
         args = (g, HP, qs, X, S, ntype, prm, batch_stats, 1e-5, p, seed, apply_act)
         y, saved = K.hop_fwd(*args, run) if fused else ops.hop_fwd_composed(K, *args, run)
-        grads = (K.hop_bwd if fused else lambda *a: ops.hop_bwd_composed(K, *a))(*args, saved, dy, True, True)
+        grads = (K.hop_bwd if fused else lambda *a: ops.hop_bwd_composed(K, *a))(*args, saved, dy, True, True, None, None, tab_col)
         torch.cuda.synchronize()
         res.append(([y] + list(saved), grads, run[:3] if run else ()))
     (f_fwd, f_bwd, f_run), (c_fwd, c_bwd, c_run) = res
@@ -826,12 +900,13 @@ def test_fused_hop_equals_composed_path(name, HP, dh, mode, monkeypatch):
     for fused in (True, False):
         _, saved = K.hop_fwd(*args, None) if fused else ops.hop_fwd_composed(K, *args, None)
         ax, as_ = base_x.clone(), (base_s.clone() if SP else None)
-        out = (K.hop_bwd if fused else lambda *a: ops.hop_bwd_composed(K, *a))(*args, saved, dy, True, True, ax, as_)
+        out = (K.hop_bwd if fused else lambda *a: ops.hop_bwd_composed(K, *a))(*args, saved, dy, True, True, ax, as_, tab_col)
         assert out[0] is ax and (out[1] is as_)
         tot.append((ax, as_))
     assert torch.equal(tot[0][0], tot[1][0]) and (not SP or torch.equal(tot[0][1], tot[1][1]))
     err = (tot[0][0] - (base_x + f_bwd[0])).abs().max().item()
     assert err <= 1e-5 * (f_bwd[0].abs().max().item() + base_x.abs().max().item()), err
+    return dict(zip(names_b, f_bwd))
 
 
 @pytest.mark.gpu

@@ -440,6 +440,21 @@ def test_gpu_parity_harness_on_cpu(d, train):
     assert len(report) > 20 and max(report.values()) < 1e-3
 
 
+def _class_count_cases():
+    import test_class_counts as TCC
+    return [pytest.param(d, T, R, t, id=f'd{d}-T{T}-R{R}-{"train" if t else "eval"}') for d, T, R in TCC.MODULE_CASES for t in (True, False)]
+
+
+@pytest.mark.parametrize('d,T,R,train', _class_count_cases())
+def test_class_count_parity_harness_on_cpu(d, T, R, train):
+    """The module cases of tests/test_class_counts.py (n_ntype = 1 .. 4, n_etype = 1 .. 600, the _tab_col branch on its boundary at d = 28)
+    through the same harness with the torch emulation: the remapped inputs, the class arithmetic of the Python layer and the oracle agree
+    without a GPU.  The bars are oracle_vs_package's own; the caps below are those of test_gpu_parity_harness_on_cpu."""
+    import test_class_counts as TCC
+    report = TCC.module_vs_oracle(d, T, R, train, device='cpu')
+    assert len(report) > 20 and max(report.values()) < 1e-3
+
+
 def test_dropout_parity_harness_on_cpu():
     """The mask-replay harness of tests/test_hip_parity.py (dropout 0.2 / 0.1 on the package side, the kernels' keep masks recomputed on
     the host and installed in the oracle) with the torch emulation of the kernels, whose dropout is the same counter hash."""

@@ -43,8 +43,8 @@ CONSTANT_PATTERNS = {
 }
 
 
-def _find(name):
-    fn, pattern = CONSTANT_PATTERNS[name]
+def _find(name, patterns=None):
+    fn, pattern = (patterns or CONSTANT_PATTERNS)[name]
     with open(os.path.join(helpers.ROOT, 'qagnn_amd', 'csrc', fn)) as f:
         found = set(re.findall(pattern, f.read()))
     return int(found.pop()) if len(found) == 1 else None
