@@ -72,9 +72,10 @@ int qagnn_abi_version(void);
  * the edge encoder's input one-hot (:419-433) is a function of c alone, C = R*T*T + T classes.
  * All three orders are sorted by (group key, edge id), i.e. deterministic and equal to the reference's CPU
  * summation order inside every group.
- * Three ways in, one result: int64 edge lists at their exact count (qagnn_graph_prep, qagnn_graph_prep_blocked), int64 edge lists
+ * Four ways in, one result: int64 edge lists at their exact count (qagnn_graph_prep, qagnn_graph_prep_blocked), int64 edge lists
  * in buffers of an edge CAPACITY with the count on the device (qagnn_graph_prep_cap), per-sample blobs built at load time, likewise
- * with a capacity (qagnn_graph_from_blobs).  The two capacity forms have launch shapes that depend on (N, capacity) only: what a
+ * with a capacity, either concatenated per batch by the host (qagnn_graph_from_blobs) or read where they lie in a device-resident store
+ * of the whole dataset (qagnn_graph_from_store).  The capacity forms have launch shapes that depend on (N, capacity) only: what a
  * replayed hipGraph of the training step needs.  E, Ep and max_chunks of the struct are then capacities; the true E' is rowptr_s[N].
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct qagnn_graph {
@@ -163,6 +164,48 @@ int qagnn_graph_prep_cap(qagnn_graph* g, int32_t* storage, const int64_t* edge_i
 int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const int32_t* blobs, const int32_t* blob_off /* [B+1] */,
                            const int32_t* edge_off /* [B+1] */, const int64_t* node_type /* [B*n] */, int32_t B, int32_t n, int32_t E,
                            int32_t R, int32_t T, qagnn_stream_t stream);
+
+/* The dataset's graphs resident on the device: a batch is then a list of sample ids, and the host neither assembles nor copies blobs.
+ * Everything a sample contributes to a batch is static per dataset: its blob (layout above) and its row of the four node fields of
+ * QAGNN.forward.  The struct holds DEVICE pointers the caller owns and leaves unchanged while a call that got them may be running:
+ *   blobs        int32 [W]      all S samples' blobs, concatenated
+ *   blob_off     int64 [S+1]    word offset of sample s in blobs (64-bit: a store may exceed 2^31 words); blob_off[S] = W; sample s holds
+ *                               (blob_off[s+1] - blob_off[s] - 2n) / 3 edges
+ *   concept_ids  int64 [S][n],  node_type int64 [S][n],  node_scores fp32 [S][n],  adj_len int64 [S] */
+typedef struct qagnn_store {
+  const int32_t* blobs;
+  const int64_t* blob_off;
+  const int64_t* concept_ids;
+  const int64_t* node_type;
+  const float* node_scores;
+  const int64_t* adj_len;
+  int32_t S, n;
+  int64_t W;
+} qagnn_store;
+
+/* The batch's node fields and edge offsets out of the store, one launch: row g of the three [B][n] outputs and adj_len_out[g] are copies
+ * of the store's row ids[g] (16-byte vector copies over the stretch of a row where source and destination are aligned alike, single
+ * words around it); edge_off_out [B+1] is the exclusive prefix sum of the samples' edge counts in batch order, edge_off_out[B] the batch's
+ * true E -- integer, computed by one workgroup, deterministic.  ids is a DEVICE int32 [B]; an id outside [0, S) is clamped into it before
+ * any address is formed from it and sets err[0] (err: int32 [4] the caller zeroed; only err[0] is written, and only with 1), so does a
+ * blob extent that is no list of < 65536 edges.  Offsets into the store are 64-bit throughout.  1 <= B <= 32768.  No allocation, no
+ * synchronisation: capture-safe. */
+int qagnn_store_gather(const qagnn_store* st, const int32_t* ids /* device [B] */, int32_t B, int64_t* concept_ids_out /* [B][n] */,
+                       int64_t* node_type_out /* [B][n] */, float* node_scores_out /* [B][n] */, int64_t* adj_len_out /* [B] */,
+                       int32_t* edge_off_out /* [B+1] */, int32_t* err /* [4] */, qagnn_stream_t stream);
+
+/* qagnn_graph_from_blobs with sample g's blob read where it lies in the store, at st->blobs + st->blob_off[ids[g]] (the id clamped into
+ * [0, S) first; a clamped one sets g->err[0]): the same kernel body instantiated for the other way of finding the blob, the same
+ * validation, zeroing by kernel, class order and XCD partition behind it, hence arrays bit-identical to qagnn_graph_from_blobs on the
+ * concatenation of the same samples at the same capacity E.  edge_off is qagnn_store_gather's edge_off_out for the same ids, node_type
+ * its node_type_out ([B*n]); n is st->n.  E is a capacity as there: edge_off[B] must not exceed it -- the caller knows the samples' edge
+ * counts from the table it uploaded.  That contract is the caller's for CLAMPED ids too: edge_off counts the samples the ids were clamped
+ * to, so a capacity sized from ids outside [0, S) by some other rule may fall short of it; the kernels do not check (as
+ * qagnn_graph_from_blobs does not), and data_utils.DeviceGraphStore.batch refuses such ids on the host before a capacity is derived.
+ * No allocation, no synchronisation: capture-safe. */
+int qagnn_graph_from_store(qagnn_graph* g, int32_t* storage, const qagnn_store* st, const int32_t* ids /* device [B] */,
+                           const int32_t* edge_off /* [B+1] */, const int64_t* node_type /* [B*n] */, int32_t B, int32_t E, int32_t R,
+                           int32_t T, qagnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Dense fp32 MFMA GEMMs (v_mfma_f32_16x16x4_f32).  Replace the cuBLAS SGEMMs of

@@ -25,10 +25,11 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_hop_fwd_workspace_elems', 'qagnn_hop_bwd_workspace_elems', 'qagnn_hop_fwd_f32', 'qagnn_hop_bwd_f32',
            'qagnn_stack_fwd_f32', 'qagnn_stack_bwd_f32', 'qagnn_absmax_f32', 'qagnn_zero_words', 'qagnn_gemm_tn_h2_f32', 'qagnn_gelu_dropout_fwd_amax_f32', 'qagnn_gelu_dropout_amax_scratch_elems',
            'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows',
-           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32', 'qagnn_graph_prep_cap']
+           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32', 'qagnn_graph_prep_cap',
+           'qagnn_store_gather', 'qagnn_graph_from_store']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
-ABI_VERSION = 24  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY)
+ABI_VERSION = 25  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY; 25: qagnn_store, qagnn_store_gather, qagnn_graph_from_store -- the dataset's graphs resident on the device)
 
 _i32, _i64, _f32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p
 
@@ -39,6 +40,12 @@ class qagnn_graph(C.Structure):
                                     'cls_count', 'src_c', 'tgt_c', 'pos_c', 'chunk_cls', 'chunk_beg',
                                     'chunk_len', 'n_chunks', 'chunkptr')] +
                 [('max_chunks', _i32), ('err', _vp), ('block_n', _i32), ('n_groups', _i32)])
+
+
+class qagnn_store(C.Structure):
+    """Mirror of qagnn_store in include/qagnn_hip.h: device pointers of a data_utils.DeviceGraphStore."""
+    _fields_ = ([(n, _vp) for n in ('blobs', 'blob_off', 'concept_ids', 'node_type', 'node_scores', 'adj_len')] +
+                [('S', _i32), ('n', _i32), ('W', _i64)])
 
 
 GATHER_MAX = 160
@@ -91,6 +98,8 @@ def load_library(path=LIB_PATH):
     lib.qagnn_graph_prep_blocked.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
     lib.qagnn_graph_prep_cap.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]
     lib.qagnn_graph_from_blobs.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
+    lib.qagnn_store_gather.argtypes = [C.POINTER(qagnn_store), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.qagnn_graph_from_store.argtypes = [C.POINTER(qagnn_graph), _vp, C.POINTER(qagnn_store), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
     lib.qagnn_node_prep_f32.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]
     lib.qagnn_seed_epoch_advance.argtypes = [_u64, _vp]
     lib.qagnn_seed_epoch_set.argtypes = [_u64, _vp]
@@ -456,6 +465,64 @@ class HipKernels(metaclass=_GuardedMeta):
         G.keep = packed.buf  # the blobs are read by the kernel just enqueued
         ERR_WATCH.poll()
         ERR_WATCH.watch(G.array('err', 4), f'the graph of the blob batch with B={B} samples, E={packed.E} edges (edge endpoint / relation id / node type)')
+        return G
+
+    def _cstore(self, store):
+        """the qagnn_store of a data_utils.DeviceGraphStore on the GPU (built once per store, kept on it)"""
+        st = getattr(store, '_cstruct', None)
+        if st is None:
+            for t, dt in ((store.blobs, torch.int32), (store.blob_off, torch.long), (store.concept_ids, torch.long), (store.node_type_ids, torch.long),
+                          (store.node_scores, torch.float32), (store.adj_lengths, torch.long)):
+                assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == store.blobs.device
+            assert store.blob_off.numel() == store.S + 1 and store.concept_ids.shape == (store.S, store.n) == store.node_type_ids.shape \
+                and store.node_scores.shape == (store.S, store.n) and store.adj_lengths.shape == (store.S,)
+            st = store._cstruct = qagnn_store(store.blobs.data_ptr(), store.blob_off.data_ptr(), store.concept_ids.data_ptr(),
+                                              store.node_type_ids.data_ptr(), store.node_scores.data_ptr(), store.adj_lengths.data_ptr(),
+                                              store.S, store.n, store.blobs.numel())
+        return st
+
+    def store_gather(self, store, ids):
+        """store: data_utils.DeviceGraphStore on the GPU; ids: int32 device tensor [B] of sample ids.  -> (concept_ids [B, n] int64, node_type_ids
+        [B, n] int64, node_scores [B, n] fp32, adj_lengths [B] int64, edge_off [B + 1] int32, flags [4] int32): the batch's rows of the store and
+        the exclusive prefix sum of its samples' edge counts, one launch (qagnn_store_gather).  An id outside the store is clamped on the
+        device and reported through ERR_WATCH."""
+        assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and ids.device == store.blobs.device
+        B, n, dev = ids.numel(), store.n, ids.device
+        cids = torch.empty((B, n), dtype=torch.long, device=dev)
+        nt = torch.empty((B, n), dtype=torch.long, device=dev)
+        ns = torch.empty((B, n), dtype=torch.float32, device=dev)
+        al = torch.empty((B,), dtype=torch.long, device=dev)
+        edge_off = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+        flags = torch.zeros(4, dtype=torch.int32, device=dev)  # (a fresh flag per call, like node_prep's)
+        rc = self.lib.qagnn_store_gather(C.byref(self._cstore(store)), ids.data_ptr(), B, cids.data_ptr(), nt.data_ptr(), ns.data_ptr(),
+                                         al.data_ptr(), edge_off.data_ptr(), flags.data_ptr(), self._stream())
+        self._check(rc, 'qagnn_store_gather')
+        ERR_WATCH.poll()
+        ERR_WATCH.watch(flags, f'the sample ids of a batch of {B} (an id outside the device store\'s {store.S} samples)')
+        return cids, nt, ns, al, edge_off, flags
+
+    def graph_from_store(self, batch, node_type):
+        """batch: data_utils.StoreBatch on the GPU; node_type [B*n] int64, the batch's (batch.fields()[1]).  graph_from_blobs() with every
+        sample's blob read where it lies in the device store (qagnn_graph_from_store); the edge offsets are those of the batch's gather.
+        batch.e_cap (optional, >= batch.E): the edge capacity, as PackedGraphBatch.e_cap."""
+        assert node_type.is_cuda and node_type.dtype == torch.long and node_type.is_contiguous()
+        store, B, n, R, T = batch.dstore, batch.B, batch.n, batch.n_etype, batch.n_ntype
+        edge_off = batch.gathered()[4]
+        E = batch.E if batch.e_cap is None else int(batch.e_cap)
+        assert E >= batch.E, f'edge capacity {E} below the batch\'s {batch.E} edges'
+        N = B * n
+        assert node_type.numel() == N and batch.ids.numel() == B and edge_off.numel() == B + 1
+        elems = self.lib.qagnn_graph_storage_elems(N, E, R, T)
+        storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
+        g = qagnn_graph()
+        rc = self.lib.qagnn_graph_from_store(C.byref(g), storage.data_ptr(), C.byref(self._cstore(store)), batch.ids.data_ptr(), edge_off.data_ptr(),
+                                             node_type.data_ptr(), B, E, R, T, self._stream())
+        self._check(rc, 'qagnn_graph_from_store')
+        G = HipGraph(storage, g, N, E, R, T, n)
+        G.dynamic = batch.e_cap is not None
+        G.keep = (store, batch.ids, edge_off)  # read by the kernels just enqueued
+        ERR_WATCH.poll()
+        ERR_WATCH.watch(G.array('err', 4), f'the graph of the store batch with B={B} samples, E={batch.E} edges (sample id / blob field / node type)')
         return G
 
     def seed_epoch_advance(self, delta=1):

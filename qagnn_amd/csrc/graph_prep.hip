@@ -203,8 +203,30 @@ __device__ __forceinline__ int seg_owner(const int* __restrict__ rp, int n, int 
   return lo;
 }
 
-__global__ __launch_bounds__(256) void k_blob_assemble(const int32_t* __restrict__ blobs, const int32_t* __restrict__ blob_off,
-                                                       const int32_t* __restrict__ edge_off, const int64_t* __restrict__ node_type,
+// How a workgroup finds its sample's blob.  packed_blobs: the batch's blobs were concatenated by the host (GraphBlobStore.pack), sample g
+// lies at word blob_off[g] of that buffer.  store_blobs: the whole dataset's blobs lie on the device (qagnn_store), the batch is the id
+// list; sample g lies at word st.blob_off[ids[g]] of the store -- a 64-bit offset, added to the pointer as such -- and an id outside
+// [0, S) is clamped BEFORE the table is read and flagged.
+struct packed_blobs {
+  const int32_t* __restrict__ blobs;
+  const int32_t* __restrict__ blob_off;
+  __device__ __forceinline__ const int32_t* find(int g, bool& bad) const { return blobs + blob_off[g]; }
+};
+struct store_blobs {
+  const int32_t* __restrict__ blobs;
+  const int64_t* __restrict__ blob_off;
+  const int32_t* __restrict__ ids;
+  int S;
+  __device__ __forceinline__ const int32_t* find(int g, bool& bad) const {
+    const int id = ids[g], idc = min(max(id, 0), S - 1);
+    bad = bad || id != idc;
+    return blobs + blob_off[idc];
+  }
+};
+
+template <class Blobs>
+__global__ __launch_bounds__(256) void k_blob_assemble(const Blobs src, const int32_t* __restrict__ edge_off,
+                                                       const int64_t* __restrict__ node_type,
                                                        int n, int B, int R, int T, int* __restrict__ rowptr_s,
                                                        int* __restrict__ tgt_s, int* __restrict__ src_s, int* __restrict__ cls_s,
                                                        int* __restrict__ eid_s, int* __restrict__ rowptr_t, int* __restrict__ src_t,
@@ -216,7 +238,8 @@ __global__ __launch_bounds__(256) void k_blob_assemble(const int32_t* __restrict
   int* const rp_t = rp + n + 1;
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int E = edge_off[B];  // the batch's edge count, read on the device: the host only fixes the CAPACITY of the arrays (hipGraph replay)
-  const int32_t* blob = blobs + blob_off[g];
+  bool bad = false;
+  const int32_t* blob = src.find(g, bad);
   const int Eoff = edge_off[g], Eg = edge_off[g + 1] - Eoff, node0 = g * n, Epoff = Eoff + node0;
   const int32_t *cnt_s = blob, *cnt_t = blob + n;
   const uint32_t* w0 = reinterpret_cast<const uint32_t*>(blob + 2 * n);
@@ -244,7 +267,7 @@ __global__ __launch_bounds__(256) void k_blob_assemble(const int32_t* __restrict
     }
   if (tid == 255) { rp_s[n] = run_s; rp_t[n] = run_t; }
   __syncthreads();
-  bool bad = rp_s[n] != Eg || rp_t[n] != Eg;
+  bad = bad || rp_s[n] != Eg || rp_t[n] != Eg;
   // node rows: segment starts and the self loops
   for (int v = tid; v < n; v += 256) {
     rowptr_s[node0 + v] = Epoff + rp_s[v] + v;
@@ -271,6 +294,77 @@ __global__ __launch_bounds__(256) void k_blob_assemble(const int32_t* __restrict
     const int ct = min((int)(w0[posc] >> 16), C_real - 1);
     cls_t[q] = ct;
   }
+  if (bad) *err = 1;
+}
+
+// ---- a batch out of the device-resident store (qagnn_store): node fields + edge offsets -------------------------------------------
+// `nw` 32-bit words from s to d by the 256 threads of a block: 16-byte vectors over the stretch where both pointers are 16-byte aligned
+// (they must be misaligned alike for one to exist), scalar words in front of it, behind it, and throughout when they are not.
+__device__ __forceinline__ void copy_words(const int32_t* __restrict__ s, int32_t* __restrict__ d, int nw, int tid) {
+  const uintptr_t sa = (uintptr_t)s, da = (uintptr_t)d;
+  if (((sa ^ da) & 15) != 0) {
+    for (int i = tid; i < nw; i += 256) d[i] = s[i];
+    return;
+  }
+  const int head = min(nw, (int)(((16 - (sa & 15)) & 15) >> 2)), nv = (nw - head) >> 2;
+  const int4* __restrict__ sv = reinterpret_cast<const int4*>(s + head);
+  int4* __restrict__ dv = reinterpret_cast<int4*>(d + head);
+  for (int i = tid; i < nv; i += 256) dv[i] = sv[i];
+  if (tid < head) d[tid] = s[tid];
+  for (int i = head + 4 * nv + tid; i < nw; i += 256) d[i] = s[i];
+}
+
+// Blocks 0 .. B-1: row ids[g] of the store's three node fields and its adj_len word -> row g of the batch's.  Block B: edge_off = the
+// exclusive scan of the samples' edge counts (blob words - 2n degree words, 3 words per edge), 256 samples per round, edge_off[B] = the
+// batch's E.  Every id is clamped into [0, S) before it forms an address; one that had to be, or a blob extent that is no edge list of
+// < 65536 edges (the blob format's limit), sets err[0].  All offsets into the store are 64-bit.
+__global__ __launch_bounds__(256) void k_store_gather(const int64_t* __restrict__ blob_off, const int64_t* __restrict__ st_cids,
+                                                      const int64_t* __restrict__ st_nt, const float* __restrict__ st_ns,
+                                                      const int64_t* __restrict__ st_al, int S, int n, const int32_t* __restrict__ ids,
+                                                      int B, int64_t* __restrict__ cids, int64_t* __restrict__ nt,
+                                                      float* __restrict__ ns, int64_t* __restrict__ al, int32_t* __restrict__ edge_off,
+                                                      int* __restrict__ err) {
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g < B) {
+    const int id = ids[g], idc = min(max(id, 0), S - 1);
+    const int64_t srow = (int64_t)idc * n, drow = (int64_t)g * n;
+    copy_words(reinterpret_cast<const int32_t*>(st_cids + srow), reinterpret_cast<int32_t*>(cids + drow), 2 * n, tid);
+    copy_words(reinterpret_cast<const int32_t*>(st_nt + srow), reinterpret_cast<int32_t*>(nt + drow), 2 * n, tid);
+    copy_words(reinterpret_cast<const int32_t*>(st_ns + srow), reinterpret_cast<int32_t*>(ns + drow), n, tid);
+    if (tid == 0) {
+      al[g] = st_al[idc];
+      if (id != idc) *err = 1;
+    }
+    return;
+  }
+  __shared__ int wtot[4];
+  const int lane = tid & 63, wid = tid >> 6;
+  int carry = 0;  // (the same value in every thread)
+  bool bad = false;
+  for (int base = 0; base < B; base += 256) {
+    const int i = base + tid;
+    int cnt = 0;
+    if (i < B) {
+      const int idc = min(max(ids[i], 0), S - 1);
+      const int64_t words = blob_off[idc + 1] - blob_off[idc] - 2 * (int64_t)n;
+      bad = bad || words < 0 || words % 3 != 0 || words >= 3 * (int64_t)65536;
+      cnt = (int)min(max(words / 3, (int64_t)0), (int64_t)65535);
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (lane == 63) wtot[wid] = incl;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wid; ++w) before += wtot[w];
+    if (i < B) edge_off[i] = carry + before + incl - cnt;
+    carry += wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    __syncthreads();
+  }
+  if (tid == 0) edge_off[B] = carry;
   if (bad) *err = 1;
 }
 
@@ -529,7 +623,7 @@ static int class_pass(qagnn_graph* g, int32_t* hist, int32_t* gc_cnt, int32_t* g
 }
 
 extern "C" const char* qagnn_last_error(void) { return g_err; }
-extern "C" int qagnn_abi_version(void) { return 24; }
+extern "C" int qagnn_abi_version(void) { return 25; }
 
 extern "C" int64_t qagnn_graph_storage_elems(int32_t N, int32_t E, int32_t R, int32_t T) {
   const int64_t Ep = (int64_t)E + N, C = (int64_t)R * T * T + T;
@@ -611,26 +705,64 @@ extern "C" int qagnn_graph_prep_cap(qagnn_graph* g, int32_t* storage, const int6
                      (hipStream_t)stream_);
 }
 
-extern "C" int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const int32_t* blobs, const int32_t* blob_off,
-                                      const int32_t* edge_off, const int64_t* node_type, int32_t B, int32_t n, int32_t E, int32_t R,
-                                      int32_t T, qagnn_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  QAGNN_REQUIRE(g && storage && blobs && blob_off && edge_off && node_type, QAGNN_EINVAL, "graph_from_blobs: null pointer");
-  QAGNN_REQUIRE(B > 0 && n > 0 && E >= 0 && R > 0 && T > 0, QAGNN_EINVAL, "graph_from_blobs: bad sizes B=%d n=%d E=%d R=%d T=%d", B, n, E, R, T);
-  QAGNN_REQUIRE(n < 65536 && (int64_t)R * T * T < 65536, QAGNN_EUNSUPPORTED, "graph_from_blobs: n=%d or R*T*T=%d does not fit the 16-bit blob fields", n, R * T * T);
-  QAGNN_REQUIRE((size_t)(2 * (n + 1)) * sizeof(int) <= 64 * 1024, QAGNN_EUNSUPPORTED, "graph_from_blobs: n=%d node slots per sample exceed the LDS scan", n);
-  QAGNN_REQUIRE(aligned16(storage), QAGNN_EINVAL, "graph_from_blobs: storage must be 16-byte aligned");
+// qagnn_graph_from_blobs / qagnn_graph_from_store: one body, the kernel instantiated for how a sample's blob is found
+template <class Blobs>
+static int from_blobs(const char* who, qagnn_graph* g, int32_t* storage, const Blobs src, const int32_t* edge_off, const int64_t* node_type,
+                      int32_t B, int32_t n, int32_t E, int32_t R, int32_t T, hipStream_t stream) {
+  QAGNN_REQUIRE(B > 0 && n > 0 && E >= 0 && R > 0 && T > 0, QAGNN_EINVAL, "%s: bad sizes B=%d n=%d E=%d R=%d T=%d", who, B, n, E, R, T);
+  QAGNN_REQUIRE(n < 65536 && (int64_t)R * T * T < 65536, QAGNN_EUNSUPPORTED, "%s: n=%d or R*T*T=%d does not fit the 16-bit blob fields", who, n, R * T * T);
+  QAGNN_REQUIRE((size_t)(2 * (n + 1)) * sizeof(int) <= 64 * 1024, QAGNN_EUNSUPPORTED, "%s: n=%d node slots per sample exceed the LDS scan", who, n);
+  QAGNN_REQUIRE(aligned16(storage), QAGNN_EINVAL, "%s: storage must be 16-byte aligned", who);
   const int64_t N64 = (int64_t)B * n, Ep64 = (int64_t)E + N64, C64 = (int64_t)R * T * T + T;
-  QAGNN_REQUIRE(Ep64 < (1ll << 30), QAGNN_EUNSUPPORTED, "graph_from_blobs: E+N=%lld too large", (long long)Ep64);
-  QAGNN_REQUIRE(C64 <= 8192, QAGNN_EUNSUPPORTED, "graph_from_blobs: %lld edge classes > 8192", (long long)C64);
+  QAGNN_REQUIRE(Ep64 < (1ll << 30), QAGNN_EUNSUPPORTED, "%s: E+N=%lld too large", who, (long long)Ep64);
+  QAGNN_REQUIRE(C64 <= 8192, QAGNN_EUNSUPPORTED, "%s: %lld edge classes > 8192", who, (long long)C64);
   carved cv = carve(g, storage, (int)N64, E, R, T, n);
   hipError_t he = zero_range(g->cls_count, (size_t)((char*)cv.es - (char*)g->cls_count), stream);
-  if (he != hipSuccess) { set_error("graph_from_blobs: k_zero16 failed: %s", hipGetErrorString(he)); return QAGNN_EHIP; }
-  k_blob_assemble<<<B, 256, (size_t)(2 * (n + 1)) * sizeof(int), stream>>>(blobs, blob_off, edge_off, node_type, n, B, R, T, g->rowptr_s,
-                                                                           g->tgt_s, g->src_s, g->cls_s, g->eid_s, g->rowptr_t, g->src_t, g->tgt_t,
-                                                                           g->cls_t, g->pos_t, g->err);
+  if (he != hipSuccess) { set_error("%s: k_zero16 failed: %s", who, hipGetErrorString(he)); return QAGNN_EHIP; }
+  k_blob_assemble<Blobs><<<B, 256, (size_t)(2 * (n + 1)) * sizeof(int), stream>>>(src, edge_off, node_type, n, B, R, T, g->rowptr_s,
+                                                                                  g->tgt_s, g->src_s, g->cls_s, g->eid_s, g->rowptr_t, g->src_t,
+                                                                                  g->tgt_t, g->cls_t, g->pos_t, g->err);
   QAGNN_LAUNCH_CHECK("k_blob_assemble");
   int rc = xcd_partition(g, stream);
   if (rc != QAGNN_OK) return rc;
   return class_pass(g, cv.hist, cv.gc_cnt, cv.gcptr, cv.nch, cv.nblk, cv.gb, cv.NG, cv.pairs, stream);
+}
+
+extern "C" int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const int32_t* blobs, const int32_t* blob_off,
+                                      const int32_t* edge_off, const int64_t* node_type, int32_t B, int32_t n, int32_t E, int32_t R,
+                                      int32_t T, qagnn_stream_t stream_) {
+  QAGNN_REQUIRE(g && storage && blobs && blob_off && edge_off && node_type, QAGNN_EINVAL, "graph_from_blobs: null pointer");
+  return from_blobs("graph_from_blobs", g, storage, packed_blobs{blobs, blob_off}, edge_off, node_type, B, n, E, R, T, (hipStream_t)stream_);
+}
+
+static int check_store(const char* who, const qagnn_store* st) {
+  QAGNN_REQUIRE(st, QAGNN_EINVAL, "%s: null store", who);
+  QAGNN_REQUIRE(st->blobs && st->blob_off && st->concept_ids && st->node_type && st->node_scores && st->adj_len, QAGNN_EINVAL,
+                "%s: null pointer in the store", who);
+  QAGNN_REQUIRE(st->S > 0 && st->n > 0 && st->W >= 0, QAGNN_EINVAL, "%s: bad store sizes S=%d n=%d W=%lld", who, st->S, st->n, (long long)st->W);
+  return QAGNN_OK;
+}
+
+extern "C" int qagnn_store_gather(const qagnn_store* st, const int32_t* ids, int32_t B, int64_t* concept_ids_out, int64_t* node_type_out,
+                                  float* node_scores_out, int64_t* adj_len_out, int32_t* edge_off_out, int32_t* err, qagnn_stream_t stream_) {
+  int rc = check_store("store_gather", st);
+  if (rc != QAGNN_OK) return rc;
+  QAGNN_REQUIRE(ids && concept_ids_out && node_type_out && node_scores_out && adj_len_out && edge_off_out && err, QAGNN_EINVAL,
+                "store_gather: null pointer");
+  // (a sample holds < 65536 edges: the int32 offsets of up to 32768 samples cannot overflow)
+  QAGNN_REQUIRE(B > 0 && B <= 32768, QAGNN_EINVAL, "store_gather: B=%d outside 1..32768", B);
+  k_store_gather<<<B + 1, 256, 0, (hipStream_t)stream_>>>(st->blob_off, st->concept_ids, st->node_type, st->node_scores, st->adj_len, st->S,
+                                                          st->n, ids, B, concept_ids_out, node_type_out, node_scores_out, adj_len_out,
+                                                          edge_off_out, err);
+  QAGNN_LAUNCH_CHECK("k_store_gather");
+  return QAGNN_OK;
+}
+
+extern "C" int qagnn_graph_from_store(qagnn_graph* g, int32_t* storage, const qagnn_store* st, const int32_t* ids, const int32_t* edge_off,
+                                      const int64_t* node_type, int32_t B, int32_t E, int32_t R, int32_t T, qagnn_stream_t stream_) {
+  int rc = check_store("graph_from_store", st);
+  if (rc != QAGNN_OK) return rc;
+  QAGNN_REQUIRE(g && storage && ids && edge_off && node_type, QAGNN_EINVAL, "graph_from_store: null pointer");
+  return from_blobs("graph_from_store", g, storage, store_blobs{st->blobs, st->blob_off, ids, st->S}, edge_off, node_type, B, st->n, E, R, T,
+                    (hipStream_t)stream_);
 }

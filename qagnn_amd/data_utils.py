@@ -334,6 +334,179 @@ class PackedGraphBatch:
         return bei.to(dev), bet.to(dev)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The dataset's graphs resident on the device.  The blobs and the four node fields of a sample are static per dataset, and CSQA train
+# is ~0.85 GB of blobs + 0.17 GB of node fields: uploaded ONCE, a batch is then the list of its sample ids -- per batch the host sums B
+# edge counts and copies B int32 words; libqagnn_hip's qagnn_store_gather copies the batch's rows of the node fields and scans its edge
+# offsets, qagnn_graph_from_store reads every sample's blob where it lies (include/qagnn_hip.h).
+# ---------------------------------------------------------------------------------------------------------------------
+class DeviceGraphStore:
+    """A GraphBlobStore and the per-sample node fields as device tensors: blobs int32 [W], blob_off int64 [S + 1], concept_ids /
+    node_type_ids int64 [S, n], node_scores fp32 [S, n], adj_lengths int64 [S].  Build with from_host(); batch() names a batch."""
+
+    def __init__(self, store, blobs, blob_off, concept_ids, node_type_ids, node_scores, adj_lengths):
+        self.store, self.blobs, self.blob_off = store, blobs, blob_off
+        self.concept_ids, self.node_type_ids, self.node_scores, self.adj_lengths = concept_ids, node_type_ids, node_scores, adj_lengths
+        self.S, self.n, self.n_etype, self.n_ntype = len(store), store.n, store.n_etype, store.n_ntype
+
+    def __len__(self):
+        return self.S
+
+    @property
+    def device(self):
+        return self.blobs.device
+
+    @property
+    def nbytes(self):
+        """bytes the store holds on its device"""
+        return sum(t.numel() * t.element_size() for t in (self.blobs, self.blob_off, self.concept_ids, self.node_type_ids, self.node_scores,
+                                                           self.adj_lengths))
+
+    @classmethod
+    def from_host(cls, store, concept_ids, node_type_ids, node_scores, adj_lengths, device):
+        """store: the host GraphBlobStore (kept: edge counts, lazy list decoding, to_packed()); the four per-sample tensors as the loaders
+        return them, [S, n(, 1)] / [S] or [Q, nc, n(, 1)] / [Q, nc] (flattened like LM_QAGNN.forward flattens).  One upload.  (A
+        memory-mapped or read-only store.data is first copied whole into host memory -- about 0.85 GB for CSQA train -- and uploaded
+        from there.)"""
+        S, n = len(store), store.n
+        if S == 0:
+            raise ValueError('an empty blob store cannot be uploaded')
+        off = np.asarray(store.off, dtype=np.int64)
+        W = int(np.asarray(store.data).shape[0])
+        words = np.diff(off)
+        if off.shape != (S + 1,) or off[0] != 0 or (words < 0).any() or off[-1] != W:
+            raise ValueError(f'blob offset table is not a monotone table of {S} samples over the store\'s {W} words')
+        if ((words - 2 * n) != 3 * np.asarray(store.edge_count, dtype=np.int64)).any():
+            raise ValueError('blob extents disagree with the store\'s edge counts (2n degree words + 3 words per edge)')
+        cids, nt, al = torch.as_tensor(concept_ids), torch.as_tensor(node_type_ids), torch.as_tensor(adj_lengths)
+        ns = torch.as_tensor(node_scores)
+        if ns.dim() >= 2 and ns.size(-1) == 1 and ns.numel() == S * n:
+            ns = ns.squeeze(-1)
+        for name, t, width in (('concept_ids', cids, n), ('node_type_ids', nt, n), ('node_scores', ns, n), ('adj_lengths', al, None)):
+            if (width is not None and (t.dim() < 2 or t.size(-1) != width)) or t.numel() != S * (width or 1):
+                raise ValueError(f'{name} of shape {tuple(t.shape)} does not hold {S} samples of n = {n} node slots')
+        device = torch.device(device)
+        data = store.data if isinstance(store.data, np.ndarray) and not isinstance(store.data, np.memmap) and store.data.flags.writeable \
+            and store.data.dtype == np.int32 and store.data.flags.c_contiguous else np.array(store.data, dtype=np.int32)
+        up = lambda t, dt, shape: t.reshape(shape).to(dt).contiguous().to(device)  # noqa: E731
+        return cls(store, torch.from_numpy(data).to(device), torch.from_numpy(off.copy()).to(device), up(cids, torch.long, (S, n)),
+                   up(nt, torch.long, (S, n)), up(ns, torch.float32, (S, n)), up(al, torch.long, (S,)))
+
+    STAGING = 8  # pinned id buffers in rotation: one is rewritten only after the copy out of it, STAGING batches ago, has completed
+
+    def _stage(self, ids32):
+        """ids32 (numpy int32 [B]) -> int32 tensor on the store's device by one non-blocking copy out of a reused pinned buffer"""
+        if self.device.type != 'cuda':
+            return torch.from_numpy(ids32)
+        ring = self.__dict__.setdefault('_ring', [None] * self.STAGING)
+        slot = self.__dict__['_slot'] = (self.__dict__.get('_slot', -1) + 1) % self.STAGING
+        entry = ring[slot]
+        if entry is None or entry[0].numel() < ids32.size:
+            entry = ring[slot] = (torch.empty(max(ids32.size, 512), dtype=torch.int32).pin_memory(), torch.cuda.Event())
+        else:
+            entry[1].synchronize()
+        buf, ev = entry
+        buf.numpy()[:ids32.size] = ids32
+        with torch.cuda.device(self.device):
+            t = buf[:ids32.size].to(self.device, non_blocking=True)
+            ev.record()
+        return t
+
+    def batch(self, sample_ids, num_choice=1):
+        """-> StoreBatch of the samples `sample_ids` (a sequence or a numpy array; any order, repeats allowed).  Host work: a range check,
+        the sum of B edge counts and one copy of B int32 words; IndexError for an id outside [0, S) before anything is enqueued."""
+        ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+        if ids.size == 0 or ids.min() < 0 or ids.max() >= self.S:
+            raise IndexError(f'sample ids must be a non-empty list inside [0, {self.S})')
+        return StoreBatch(self, ids, num_choice, self._stage(ids.astype(np.int32)), int(self.store.edge_count[ids].sum()))
+
+
+class StoreBatch:
+    """A batch named by its sample ids in a DeviceGraphStore: what the batch generator yields in place of the nested edge lists when it was
+    given a device store, and what LM_QAGNN / QAGNN / graphed.GraphedStep accept as `adj` beside PackedGraphBatch and EdgeListBatch.
+
+    ids     int32 tensor [B] on the store's device       E      the batch's edge count (host sum of the store's edge counts)
+    e_cap   (optional, >= E) the edge CAPACITY to lay the graph arrays out for, as PackedGraphBatch.e_cap"""
+
+    def __init__(self, dstore, sample_ids, num_choice, ids, E, e_cap=None):
+        self.dstore, self.store, self.ids, self.E, self.e_cap = dstore, dstore.store, ids, int(E), e_cap
+        self._sample_ids, self.num_choice, self.B = sample_ids, num_choice, ids.numel()
+        self.n, self.n_etype, self.n_ntype = dstore.n, dstore.n_etype, dstore.n_ntype
+        self._gathered = self._packed = None
+
+    @property
+    def device(self):
+        return self.ids.device
+
+    @property
+    def sample_ids(self):
+        """the batch's sample ids as a list of Python ints (made on first use: the hot path never asks)"""
+        if not isinstance(self._sample_ids, list):
+            self._sample_ids = [int(i) for i in self._sample_ids]
+        return self._sample_ids
+
+    @sample_ids.setter
+    def sample_ids(self, value):
+        self._sample_ids = value
+
+    def adopt(self, other):
+        """This holder's id tensor has been overwritten with `other`'s ids: take over its host-side description (edge count, sample ids)."""
+        assert other.dstore is self.dstore and other.B == self.B
+        self.E, self._sample_ids = other.E, other._sample_ids
+
+    def reset(self):
+        """Forget the memoised gather and packed form: for a holder whose id tensor is rewritten in place (graphed.GraphedStep's static
+        buffer), so that the next fields() and the graph built behind it again share ONE fresh gather."""
+        self._gathered = self._packed = None
+
+    def gathered(self):
+        """(concept_ids [B, n], node_type_ids [B, n], node_scores [B, n], adj_lengths [B], edge_off [B + 1] int32, device flags or None):
+        ONE gather per batch -- the node fields and the graph (ops.build_graph) share it.  On the GPU qagnn_store_gather; on a CPU store, or
+        under a kernel provider without it, plain torch indexing."""
+        if self._gathered is None:
+            d = self.dstore
+            K = None
+            if self.device.type == 'cuda':
+                from . import ops
+                K = ops.kernels()
+            if K is not None and hasattr(K, 'store_gather'):
+                self._gathered = K.store_gather(d, self.ids)
+            else:
+                idx = self.ids.long()
+                cnt = (d.blob_off[idx + 1] - d.blob_off[idx] - 2 * d.n) // 3
+                edge_off = torch.cat([cnt.new_zeros(1), cnt.cumsum(0)]).int()
+                self._gathered = (d.concept_ids[idx], d.node_type_ids[idx], d.node_scores[idx], d.adj_lengths[idx], edge_off, None)
+        return self._gathered
+
+    def fields(self):
+        """(concept_ids [B, n], node_type_ids [B, n], node_scores [B, n, 1], adj_lengths [B]): the flattened decoder inputs of QAGNN.forward"""
+        cids, nt, ns, al = self.gathered()[:4]
+        return cids, nt, ns.unsqueeze(2), al
+
+    def to_packed(self):
+        """The same batch as a PackedGraphBatch, assembled on the host out of the host store (GraphBlobStore.pack) and copied to the
+        batch's device: what a kernel provider without graph_from_store is handed."""
+        if self._packed is None:
+            on_gpu = self.device.type == 'cuda'
+            buf, B, E = self.store.pack(self.sample_ids, pin=on_gpu)
+            assert (B, E) == (self.B, self.E)
+            self._packed = PackedGraphBatch(buf.to(self.device, non_blocking=True) if on_gpu else buf, B, E, self.store, self.sample_ids, self.num_choice)
+        if self.e_cap is not None:
+            self._packed.e_cap = self.e_cap
+        return self._packed
+
+    def nested_lists(self, device=None):
+        """(edge_index, edge_type) as nested lists [bs][nc] of int64 tensors: the reference generator's protocol."""
+        return PackedGraphBatch.nested_lists(self, device)
+
+    def batched(self, device=None):
+        """(edge_index [2, E], edge_type [E]) as LM_QAGNN.batch_graph would return them."""
+        ei, et = self.nested_lists()
+        bei, bet = batch_graph([g for row in ei for g in row], [g for row in et for g in row], self.n)
+        dev = device if device is not None else self.device
+        return bei.to(dev), bet.to(dev)
+
+
 def batch_graph(edge_index_init, edge_type_init, n_nodes):
     """LM_QAGNN.batch_graph (reference modeling_qagnn.py:244-251): offset subgraph i by i*n and concatenate.
 
@@ -408,9 +581,22 @@ class MultiGPUSparseAdjDataBatchGenerator(object):
     """
 
     def __init__(self, args, mode, device0, device1, batch_size, indexes, qids, labels,
-                 tensors0=[], lists0=[], tensors1=[], lists1=[], adj_data=None, graph_blobs=None, num_choice=None):
+                 tensors0=[], lists0=[], tensors1=[], lists1=[], adj_data=None, graph_blobs=None, num_choice=None, device_store=None,
+                 gather_fields=True):
         """graph_blobs (GraphBlobStore, optional): the batch's graph then travels as ONE int32 buffer of load-time blobs
-        (12 B/edge) and is yielded as (PackedGraphBatch, None) in place of (edge_index, edge_type); `adj_data` may be None."""
+        (12 B/edge) and is yielded as (PackedGraphBatch, None) in place of (edge_index, edge_type); `adj_data` may be None.
+        device_store (DeviceGraphStore on device1, optional): nothing of the graph or of the four node tensors travels per batch but the
+        sample ids -- (StoreBatch, None) is yielded in place of (edge_index, edge_type), and the four tensors of `tensors1` (concept_ids,
+        node_type_ids, node_scores, adj_lengths; read for num_choice only, may be left out) are StoreBatch.fields() in [bs, nc, ...] shapes.
+        gather_fields=False: None is yielded in those four places and nothing is enqueued per batch but the id copy -- for consumers that
+        gather for themselves (graphed.GraphedStep does, inside its captured graph, and would ignore the generator's copies)."""
+        if device_store is not None:
+            assert len(tensors1) in (0, 4), 'with a device store, tensors1 is the four node tensors of the reference loader (or empty)'
+            full = lambda d: torch.device(d.type, d.index if d.index is not None else (torch.cuda.current_device() if d.type == 'cuda' else 0))  # noqa: E731
+            assert full(torch.device(device1)) == full(device_store.device), f'the device store lives on {device_store.device}, not on device1 = {device1}'
+            if num_choice is None and not tensors1:
+                raise ValueError('num_choice is needed when tensors1 is left out')
+        self.device_store, self.gather_fields = device_store, gather_fields
         if graph_blobs is None and adj_data is not None and getattr(adj_data[0], 'store', None) is not None:
             graph_blobs, num_choice = adj_data[0].store, adj_data[0].num_choice  # adj_data from load_flat_cache()
         self.graph_blobs, self.num_choice = graph_blobs, num_choice
@@ -473,10 +659,15 @@ class MultiGPUSparseAdjDataBatchGenerator(object):
             batch_qids = [self.qids[idx] for idx in batch_indexes]
             batch_labels = self._to_device(self.labels[batch_indexes], self.device1)
             batch_tensors0 = [self._to_device(x[batch_indexes], self.device0) for x in self.tensors0]
-            batch_tensors1 = [self._to_device(x[batch_indexes], self.device1) for x in self.tensors1]
+            batch_tensors1 = [self._to_device(x[batch_indexes], self.device1) for x in self.tensors1] if self.device_store is None else None
             batch_lists0 = [self._to_device([x[i] for i in batch_indexes], self.device0) for x in self.lists0]
             batch_lists1 = [self._to_device([x[i] for i in batch_indexes], self.device1) for x in self.lists1]
-            if self.graph_blobs is not None:
+            if self.device_store is not None:
+                nc = self.num_choice or self.tensors1[0].size(1)
+                ids = (np.asarray(batch_indexes, dtype=np.int64)[:, None] * nc + np.arange(nc, dtype=np.int64)).reshape(-1)
+                edge_index, edge_type = self.device_store.batch(ids, nc), None
+                batch_tensors1 = [x.view(b - a, nc, *x.shape[1:]) for x in edge_index.fields()] if self.gather_fields else [None] * 4
+            elif self.graph_blobs is not None:
                 nc = self.num_choice or (self.tensors1[0].size(1) if self.tensors1 else 1)
                 ids = [int(q) * nc + c for q in batch_indexes for c in range(nc)]
                 on_gpu = torch.device(self.device1).type == 'cuda'

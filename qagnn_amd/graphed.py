@@ -7,8 +7,9 @@ forward + loss + backward with one host call.
 
 What makes it legitimate for TRAINING (a new batch every step, not a replay of one batch):
   * shapes  -- every launch shape of the step depends on (B, n, edge CAPACITY) only: the graph arrives in static buffers laid out for
-    `e_cap` >= E edges -- load-time blobs (qagnn_graph_from_blobs) or the reference's int64 edge lists (qagnn_graph_prep_cap,
-    include/qagnn_hip.h) -- and the kernels read the batch's true edge count on the device.  One capture per capacity bucket (8 buckets
+    `e_cap` >= E edges -- load-time blobs (qagnn_graph_from_blobs), the reference's int64 edge lists (qagnn_graph_prep_cap,
+    include/qagnn_hip.h) or sample ids into a device-resident store (qagnn_store_gather + qagnn_graph_from_store INSIDE the captured
+    graph: the static input is the id list) -- and the kernels read the batch's true edge count on the device.  One capture per capacity bucket (8 buckets
     per octave of E: <= 12.5 % slack) and kind of graph input;
   * inputs  -- static device buffers, refilled by `copy_` before each replay (the one host-to-device copy per tensor the eager path
     makes too);
@@ -32,7 +33,7 @@ import math
 import torch
 
 from . import ops
-from .data_utils import EdgeListBatch, PackedGraphBatch
+from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
 
 
 def edge_capacity(E, floor=1024):
@@ -43,15 +44,16 @@ def edge_capacity(E, floor=1024):
 
 
 class _Captured:
-    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'blob', 'lw', 'packed', 'ei', 'et', 'ecount', 'logits', 'attn', 'loss', 'grads', 'replays',
+    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'blob', 'ids', 'lw', 'packed', 'ei', 'et', 'ecount', 'logits', 'attn', 'loss', 'grads', 'replays',
                  'params', 'watched', 'sent_grad')
 
 
 class GraphedStep:
     """step = GraphedStep(model, num_choice);  logits, loss = step(sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths,
     packed, labels, loss_weight)  -- the flattened [B, ...] decoder inputs of QAGNN.forward (reference modeling_qagnn.py:141-189), the
-    graph as a data_utils.PackedGraphBatch (device or host buffer), a data_utils.EdgeListBatch or the reference's plain
-    (edge_index [2, E], edge_type [E]) int64 pair (device or host, pinned or not), labels [B / num_choice].
+    graph as a data_utils.PackedGraphBatch (device or host buffer), a data_utils.EdgeListBatch, the reference's plain
+    (edge_index [2, E], edge_type [E]) int64 pair (device or host, pinned or not) or a data_utils.StoreBatch (the four node tensors may
+    then be None: the captured graph gathers them from the store itself), labels [B / num_choice].
 
     loss = cross_entropy(logits.view(-1, nc), labels) * loss_weight  (the reference's mini-batch loss, qagnn.py:257-261);
     after the call every trainable parameter's .grad holds this step's gradient (zero_grad implicit), or -- accumulate=True -- the
@@ -76,6 +78,9 @@ class GraphedStep:
 
     # -- the eager step that gets captured -------------------------------------------------------------------------------------------
     def _step(self, c):
+        if c.ids is not None:
+            c.packed.reset()  # the gather is part of the step: it reads the static id buffer, the model consumes its outputs in place
+            c.cids, c.nt, c.ns, c.al = c.packed.fields()
         logits, attn = self.model(c.sent, c.cids, c.nt, c.ns, c.al, c.packed)
         loss = torch.nn.functional.cross_entropy(logits.view(-1, self.nc), c.labels) * c.lw
         loss.backward()
@@ -83,8 +88,11 @@ class GraphedStep:
 
     def _key(self, sent, cids, packed):
         trainable = tuple(i for i, p in enumerate(self.model.parameters()) if p.requires_grad)
-        return (cids.size(0), cids.size(1), sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad),
-                hash(trainable), 'blobs' if isinstance(packed, PackedGraphBatch) else 'edge lists')
+        if isinstance(packed, StoreBatch):
+            B, n, kind = packed.B, packed.n, ('store', id(packed.dstore))
+        else:
+            B, n, kind = cids.size(0), cids.size(1), 'blobs' if isinstance(packed, PackedGraphBatch) else 'edge lists'
+        return (B, n, sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad), hash(trainable), kind)
 
     def _capture(self, key, args):
         B, n, sent_dim, e_cap, _, sent_rg, _, kind = key
@@ -95,14 +103,21 @@ class GraphedStep:
         c.params = [p for p in self.model.parameters() if p.requires_grad]
         c.watched, c.sent_grad = [], None
         c.sent = torch.empty((B, sent_dim), dtype=torch.float32, device=dev, requires_grad=sent_rg)
-        c.cids = torch.empty((B, n), dtype=torch.long, device=dev)
-        c.nt = torch.empty((B, n), dtype=torch.long, device=dev)
-        c.ns = torch.empty((B, n, 1), dtype=torch.float32, device=dev)
-        c.al = torch.empty((B,), dtype=torch.long, device=dev)
+        store_kind = isinstance(kind, tuple)
+        c.cids = c.nt = c.ns = c.al = None  # (a store batch: outputs of the captured gather)
+        if not store_kind:
+            c.cids = torch.empty((B, n), dtype=torch.long, device=dev)
+            c.nt = torch.empty((B, n), dtype=torch.long, device=dev)
+            c.ns = torch.empty((B, n, 1), dtype=torch.float32, device=dev)
+            c.al = torch.empty((B,), dtype=torch.long, device=dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev)
         c.lw = torch.ones((), dtype=torch.float32, device=dev)
-        c.blob = c.ei = c.et = c.ecount = None
-        if kind == 'blobs':
+        c.blob = c.ei = c.et = c.ecount = c.ids = None
+        if store_kind:  # the static input is the id list; gather and graph assembly run inside the captured graph and read it
+            assert packed.device == dev, 'the device store must live on the model\'s device'
+            c.ids = torch.zeros((B,), dtype=torch.int32, device=dev)
+            c.packed = StoreBatch(packed.dstore, packed.sample_ids, packed.num_choice, c.ids, packed.E, e_cap)
+        elif kind == 'blobs':
             c.blob = torch.zeros(packed.head + 2 * n * B + 3 * e_cap, dtype=torch.int32, device=dev)
             c.packed = PackedGraphBatch(c.blob, B, packed.E, packed.store, packed.sample_ids, packed.num_choice)
             c.packed.e_cap = e_cap
@@ -161,12 +176,17 @@ class GraphedStep:
         sent, cids, nt, ns, al, packed, labels, lw = args
         with torch.no_grad():
             c.sent.copy_(sent, non_blocking=True)
+        c.labels.copy_(labels, non_blocking=True)
+        c.lw.fill_(float(lw))
+        if c.ids is not None:  # a store batch: B int32 words; the node fields are gathered on the device, by the replayed graph
+            assert packed.E <= c.packed.e_cap
+            c.ids.copy_(packed.ids, non_blocking=True)
+            c.packed.adopt(packed)
+            return
         c.cids.copy_(cids, non_blocking=True)
         c.nt.copy_(nt, non_blocking=True)
         c.ns.copy_(ns.reshape(c.ns.shape), non_blocking=True)
         c.al.copy_(al, non_blocking=True)
-        c.labels.copy_(labels, non_blocking=True)
-        c.lw.fill_(float(lw))
         if c.blob is None:
             E = packed.E
             assert E <= c.packed.e_cap
@@ -180,9 +200,9 @@ class GraphedStep:
         c.blob[:nwords].copy_(packed.buf, non_blocking=True)
 
     def __call__(self, sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight=1.0, accumulate=False):
-        if not isinstance(packed, (PackedGraphBatch, EdgeListBatch)):
+        if not isinstance(packed, (PackedGraphBatch, EdgeListBatch, StoreBatch)):
             assert isinstance(packed, (tuple, list)) and len(packed) == 2 and all(isinstance(t, torch.Tensor) for t in packed), \
-                'GraphedStep takes the graph as a PackedGraphBatch, an EdgeListBatch or an (edge_index [2, E], edge_type [E]) pair'
+                'GraphedStep takes the graph as a PackedGraphBatch, an EdgeListBatch, a StoreBatch or an (edge_index [2, E], edge_type [E]) pair'
             packed = EdgeListBatch(packed[0], packed[1], count=False)  # (no count word of its own: the capture's static one is written)
         args = (sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight)
         key = self._key(sent_vecs, concept_ids, packed)

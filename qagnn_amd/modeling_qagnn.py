@@ -546,8 +546,12 @@ class QAGNN(nn.Module):
         """
         sent_vecs (B, dim_sent); concept_ids (B, n); node_type_ids (B, n); node_scores (B, n, 1); adj_lengths (B,)
         adj = (edge_index [2, E] with global node ids g*n + local, edge_type [E]), or the same pair with its edge count as a
-        data_utils.EdgeListBatch, or a data_utils.PackedGraphBatch of load-time blobs;  returns (B, 1), (n_head*B, n)
+        data_utils.EdgeListBatch, or a data_utils.PackedGraphBatch of load-time blobs, or a data_utils.StoreBatch of sample ids into a
+        device-resident store (the four node tensors may then be None: they are the batch's own, StoreBatch.fields());
+        returns (B, 1), (n_head*B, n)
         """
+        if concept_ids is None and node_type_ids is None and node_scores is None and adj_lengths is None:
+            concept_ids, node_type_ids, node_scores, adj_lengths = adj.fields()  # (a StoreBatch; shares one gather with the graph)
         dev = node_type_ids.device
         n = node_type_ids.size(1)
         ce = self.concept_emb
@@ -632,16 +636,17 @@ class LM_QAGNN(nn.Module):
 
     def forward(self, *inputs, layer_id=-1, cache_output=False, detail=False):
         """inputs = [*lm_tensors (bs, nc, ...), concept_ids, node_type_ids, node_scores, adj_lengths (bs, nc, ...),
-        edge_index, edge_type (nested lists [bs][nc] of [2, E_g] / [E_g]; or a data_utils.PackedGraphBatch / EdgeListBatch in place of
-        edge_index, with edge_type None)]  ->  logits (bs, nc), pool_attn."""
+        edge_index, edge_type (nested lists [bs][nc] of [2, E_g] / [E_g]; or a data_utils.PackedGraphBatch / EdgeListBatch / StoreBatch in
+        place of edge_index, with edge_type None)]  ->  logits (bs, nc), pool_attn."""
         bs, nc = inputs[0].size(0), inputs[0].size(1)
         edge_index_orig, edge_type_orig = inputs[-2:]
         flat = [x.reshape(bs * nc, *x.shape[2:]) for x in inputs[:-2]]
         *lm_inputs, concept_ids, node_type_ids, node_scores, adj_lengths = flat
         dev = node_type_ids.device
-        from .data_utils import EdgeListBatch, PackedGraphBatch
-        if isinstance(edge_index_orig, PackedGraphBatch):
-            # the batch generator shipped the graph as one buffer of load-time blobs: batch_graph's offsets are applied in-kernel
+        from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
+        if isinstance(edge_index_orig, (PackedGraphBatch, StoreBatch)):
+            # the batch generator shipped the graph as one buffer of load-time blobs (or as sample ids into the store of all of them on
+            # the device): batch_graph's offsets are applied in-kernel
             adj = edge_index_orig
         elif isinstance(edge_index_orig, EdgeListBatch):
             # already batched (EdgeListBatch.from_lists = batch_graph) and carrying its edge count; handed back as is under `detail`
@@ -657,7 +662,7 @@ class LM_QAGNN(nn.Module):
         logits = logits.view(bs, nc)
         if not detail:
             return logits, attn
-        if isinstance(edge_index_orig, PackedGraphBatch):
+        if isinstance(edge_index_orig, (PackedGraphBatch, StoreBatch)):
             edge_index_orig, edge_type_orig = edge_index_orig.nested_lists()  # what the reference returns here (:237-239)
         return logits, attn, concept_ids.view(bs, nc, -1), node_type_ids.view(bs, nc, -1), edge_index_orig, edge_type_orig
 

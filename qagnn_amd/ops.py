@@ -357,9 +357,16 @@ _PREP_STREAMS = {}
 def build_graph(adj, node_type, n_etype, n_ntype, block_n):
     """The batch's graph orderings from whatever the caller handed over as `adj`: a data_utils.PackedGraphBatch (load-time
     blobs, one device buffer), the reference's (edge_index [2, E], edge_type [E]) int64 pair, or a data_utils.EdgeListBatch (that pair
-    with its edge count: with a capacity it takes the capacity form of the sorting path, where the provider has one)."""
+    with its edge count: with a capacity it takes the capacity form of the sorting path, where the provider has one), or a
+    data_utils.StoreBatch (sample ids into a device-resident store: the blobs are read where they lie; a provider without
+    graph_from_store is handed the same batch packed on the host, StoreBatch.to_packed)."""
     K = kernels()
-    from .data_utils import EdgeListBatch, PackedGraphBatch
+    from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
+    if isinstance(adj, StoreBatch):
+        assert adj.n == block_n and adj.n_etype == n_etype and adj.n_ntype == n_ntype, 'device store built for another model shape'
+        if hasattr(K, 'graph_from_store') and node_type.is_cuda:
+            return K.graph_from_store(adj, node_type)
+        adj = adj.to_packed()
     if isinstance(adj, EdgeListBatch):
         if adj.e_cap is not None and hasattr(K, 'graph_prep_cap') and node_type.is_cuda:
             return K.graph_prep_cap(adj.to(node_type.device) if adj.device != node_type.device else adj, node_type, n_etype, n_ntype, block_n=block_n)
