@@ -353,6 +353,157 @@ def install_keep_masks(omodel, masks, ps):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Dropout masks as random variables (tests/test_dropout_masks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# The bit-for-bit comparisons above restate the kernels' index formula, so they cannot see a mask that is wrong as a random variable: one
+# mask in two sites, a head index that is ignored, a period of one row pitch.  These helpers hold a keep mask (bool, True = kept) to what
+# n independent draws give.  A draw is kept with probability q = 1 - ceil(p 2^24) / 2^24 (uniform01 is k / 2^24, dropped on `< p`), and a
+# count of n draws with success probability q' may differ from n q' by at most MASK_Z sqrt(n q' (1 - q')): q' = q for a rate, q^2 for
+# the joint count of two masks or of a mask with itself at a lag.  MASK_Z = 6: a two-sided normal tail of 2e-9 per assertion, and the
+# seeds of the tests are fixed, so a test passes for ever or fails for ever.  Nothing is tuned: the same helpers run on the numpy twin at
+# the GPU tests' seeds, shapes and rates, and on doctored masks (test_dropout_masks.py, `-m "not gpu"`).
+MASK_Z = 6.0
+MASK_LAGS = (1, 2, 3, 4, 64, 256)  # + the row pitch and the per-head / per-sample strides of the site
+
+
+def keep_probability(p):
+    """q of a site with dropout rate p (taken as the float the kernels get): 2^24 q of the 2^24 values of a draw are kept"""
+    import math
+    return 1.0 - math.ceil(float(np.float32(p)) * 16777216.0) / 16777216.0
+
+
+def count_z(count, n, q):
+    """|count - n q| in units of sqrt(n q (1 - q)) (inf for a count that differs where the draw is certain)"""
+    sd = (n * q * (1.0 - q)) ** 0.5
+    d = abs(float(count) - n * q)
+    return d / sd if sd > 0 else (0.0 if d == 0 else float('inf'))
+
+
+def _np_mask(m):
+    return (m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)).astype(bool)
+
+
+def mask_rate_z(mask, p):
+    m = _np_mask(mask)
+    return count_z(m.sum(), m.size, keep_probability(p))
+
+
+def _pooled_lines_z(counts, r, q):
+    """worst z over lines of r draws each with `counts` kept.  The bar is a statement about a count only where it is at least one count
+    wide, MASK_Z sqrt(r q (1 - q)) >= 1: below that a single kept (or dropped) element of a short line at an extreme rate lies "outside"
+    it although it happens in every mask (one kept element among 64 draws at q = 2^-12: 7.9 standard deviations, probability 1.6 % per
+    line), and the twin could meet the bar only with a mask that keeps nothing.  So neighbouring lines are pooled, as few as give the pool
+    1 / (MASK_Z^2 q (1 - q)) draws -- no pooling at all for lines of 4 draws or more at p = 0.2 and 0.5, lines of 114 draws or more at
+    q = 2^-12 -- and the bar is applied to the pools."""
+    import math
+    g = max(1, math.ceil(1.0 / (MASK_Z ** 2 * q * (1.0 - q) * r))) if 0.0 < q < 1.0 else len(counts)
+    pools = np.array_split(np.asarray(counts), max(1, len(counts) // g))
+    return max(count_z(c.sum(), c.size * r, q) for c in pools)
+
+
+def mask_row_col_z(mask, p):
+    """worst z over the rows and over the columns of a mask seen as [rows, last axis] (short lines pooled: _pooled_lines_z)"""
+    m = _np_mask(mask)
+    m = m.reshape(-1, m.shape[-1])
+    q = keep_probability(p)
+    return max(_pooled_lines_z(m.sum(1), m.shape[1], q), _pooled_lines_z(m.sum(0), m.shape[0], q))
+
+
+def mask_joint_z(a, b, p, lags=(0,), p_b=None):
+    """worst z of the joint keep counts of two masks of one shape, element i of `a` with element i + lag of `b` (flat, row-major), for
+    every lag of `lags` in both directions: independent masks keep both with probability q_a q_b.  lag 0: the two sites share a mask;
+    the others: one is the other moved by a few elements."""
+    a, b = _np_mask(a).reshape(-1), _np_mask(b).reshape(-1)
+    assert a.size == b.size
+    qq = keep_probability(p) * keep_probability(p if p_b is None else p_b)
+    worst = 0.0
+    for lag in sorted({s * int(l) for l in lags for s in (1, -1)}):
+        x, y = (a[:a.size - lag], b[lag:]) if lag >= 0 else (a[-lag:], b[:b.size + lag])
+        if x.size:
+            worst = max(worst, count_z(np.count_nonzero(x & y), x.size, qq))
+    return worst
+
+
+def mask_lag_z(mask, p, lags):
+    """worst z of the joint keep count of a mask with itself at every lag of `lags` (flat, row-major): a repeated or mis-strided index
+    keeps both ends of a pair together"""
+    m = _np_mask(mask).reshape(-1)
+    return mask_joint_z(m, m, p, [l for l in lags if 0 < l < m.size])
+
+
+def mask_figures(mask, p, strides=()):
+    """{'rate', 'row/col', 'lag'}: the z of every single-mask helper; strides: the site's row pitch, per-head and per-sample strides"""
+    return {'rate': mask_rate_z(mask, p), 'row/col': mask_row_col_z(mask, p), 'lag': mask_lag_z(mask, p, tuple(MASK_LAGS) + tuple(strides))}
+
+
+def check_mask(mask, p, strides, what, log=None):
+    """every single-mask helper under MASK_Z -> the worst z"""
+    fig = mask_figures(mask, p, strides)
+    if log is not None:
+        log.append((what, fig))
+    bad = {k: v for k, v in fig.items() if not v <= MASK_Z}
+    assert not bad, f'{what}: ' + ', '.join(f'{k} z = {v:.2f}' for k, v in bad.items()) + f' > {MASK_Z} (p = {p})'
+    return max(fig.values())
+
+
+def check_independent(a, b, p, strides, what, log=None):
+    """two masks of one shape and rate are independent at lag 0 and at every lag of the site, both directions -> the worst z"""
+    z = mask_joint_z(a, b, p, (0,) + tuple(MASK_LAGS) + tuple(strides))
+    if log is not None:
+        log.append((what, {'joint': z}))
+    assert z <= MASK_Z, f'{what}: joint z = {z:.2f} > {MASK_Z} (p = {p})'
+    return z
+
+
+def twin_mask(seed, shape, p, epoch=0):
+    """keep_mask at a seed epoch: epoch_seed() of csrc/common.h adds epoch * 0xD1B54A32D192ED03 (mod 2^64) to the seed where p > 0"""
+    if p <= 0:
+        return torch.ones(*shape, dtype=torch.bool)
+    return keep_mask((int(seed) + int(epoch) * 0xD1B54A32D192ED03) % (1 << 64), shape, p)
+
+
+class SeedSpy:
+    """Kernel-provider proxy (ops.set_kernels) that keeps, in call order, (entry point, [(p, seed), ...]) of every call that takes a dropout
+    seed; the calls run unchanged.  with SeedSpy() as spy: <steps>  -> spy.calls"""
+    ARGS = {'gelu_dropout_fwd': ((1, 2),), 'gelu_dropout_bwd': ((2, 3),), 'hop_fwd': ((9, 10),), 'hop_bwd': ((9, 10),),
+            'stack_fwd': ((9, 10),), 'stack_bwd': ((9, 10),), 'pool_attn_fwd': ((5, 6),), 'pool_attn_bwd': ((3, 4),),
+            'head_post_fwd': ((9, 11), (10, 12)), 'head_post_bwd': ((9, 11), (10, 12))}
+
+    def __init__(self, inner=None):
+        self._given = inner
+
+    def __enter__(self):
+        from qagnn_amd import ops
+        self._ops = ops
+        self._inner = self._given if self._given is not None else ops.kernels()
+        self.name, self.calls = self._inner.name, []
+        self._old = ops.set_kernels(self)
+        return self
+
+    def __exit__(self, *exc):
+        self._ops.set_kernels(self._old)
+        return False
+
+    def __getattr__(self, attr):
+        fn = getattr(self._inner, attr)
+        if attr not in self.ARGS:
+            return fn
+
+        def spied(*a, **kw):
+            got = []
+            for ip, iseed in self.ARGS[attr]:
+                p, s = a[ip], a[iseed]
+                got += [(float(p), int(x)) for x in s] if isinstance(s, (list, tuple)) else [(float(p), int(s))]
+            self.calls.append((attr, got))
+            return fn(*a, **kw)
+        return spied
+
+    def seeds(self, suffix):
+        """the seeds of the calls whose name ends in `suffix` ('_fwd' / '_bwd') that ran with p > 0, in call order"""
+        return [s for name, got in self.calls if name.endswith(suffix) for p, s in got if p > 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # ReLU kinks at bench size: the candidate's subgradient choice, replayed on the oracle
 # ---------------------------------------------------------------------------------------------------------------------
 # Every GATConvE.mlp (and the shared edge encoder) is Linear -> BatchNorm -> ReLU -> Linear.  At 320 subgraphs a forward has 64 M
