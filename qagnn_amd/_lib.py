@@ -390,6 +390,30 @@ class HipKernels(metaclass=_GuardedMeta):
             raise RuntimeError(f'{what} failed (code {rc}): {self.lib.qagnn_last_error().decode()}')
 
     # -- graph -------------------------------------------------------------------------------------------------
+    def _graph_alloc(self, N, E, R, T, device, storage=None):
+        """-> (storage, g): int32 device storage for the arrays of a graph of N node rows laid out for E edges -- the caller's, if it is
+        large enough, else allocated -- and the struct the builder fills in."""
+        elems = self.lib.qagnn_graph_storage_elems(N, E, R, T)
+        if storage is None:
+            storage = torch.empty(elems, dtype=torch.int32, device=device)
+        assert storage.is_cuda and storage.dtype == torch.int32 and storage.is_contiguous() and storage.numel() >= elems
+        return storage, qagnn_graph()
+
+    def _graph_done(self, rc, entry, storage, g, N, E, R, T, block_n, dynamic, keep, what):
+        """The builders' common tail.  dynamic: E / Ep are capacities, the true E' lives on the device (rowptr_s[N] = sum of cls_count);
+        keep: what the kernels just enqueued read; what: the batch, as a reported validation flag names it."""
+        self._check(rc, entry)
+        G = HipGraph(storage, g, N, E, R, T, block_n)
+        G.dynamic, G.keep = dynamic, keep
+        ERR_WATCH.poll()  # flags of earlier batches that have landed since
+        ERR_WATCH.watch(G.array('err', 4), f'the graph of {what}')
+        return G
+
+    @staticmethod
+    def _block_n(block_n, N):
+        """the sorting builders' block size: 0 (no block structure promised) unless it divides the node rows"""
+        return int(block_n) if block_n and N % block_n == 0 else 0
+
     def graph_prep(self, edge_index, edge_type, node_type, n_etype, n_ntype, block_n=0):
         """block_n = n > 0: the caller expects subgraph i to own node rows [i*n, (i+1)*n) (LM_QAGNN.batch_graph); whether the
         edges really respect that is recorded in a device flag and decides, on the device, which edge kernel runs."""
@@ -397,19 +421,13 @@ class HipKernels(metaclass=_GuardedMeta):
         assert edge_index.dim() == 2 and edge_index.size(0) == 2
         edge_index, edge_type, node_type = edge_index.contiguous(), edge_type.contiguous(), node_type.contiguous()
         N, E = node_type.numel(), edge_index.size(1)
-        elems = self.lib.qagnn_graph_storage_elems(N, E, n_etype, n_ntype)
-        storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
-        g = qagnn_graph()
-        if block_n and N % block_n:
-            block_n = 0
+        storage, g = self._graph_alloc(N, E, n_etype, n_ntype, node_type.device)
+        block_n = self._block_n(block_n, N)
         rc = self.lib.qagnn_graph_prep_blocked(C.byref(g), storage.data_ptr(), _ptr(edge_index) if E else None,
                                                _ptr(edge_type) if E else None, node_type.data_ptr(), N, E, n_etype, n_ntype,
-                                               int(block_n), self._stream())
-        self._check(rc, 'qagnn_graph_prep_blocked')
-        G = HipGraph(storage, g, N, E, n_etype, n_ntype, int(block_n))
-        ERR_WATCH.poll()  # flags of earlier batches that have landed since
-        ERR_WATCH.watch(G.array('err', 4), f'the graph of the batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
-        return G
+                                               block_n, self._stream())
+        return self._graph_done(rc, 'qagnn_graph_prep_blocked', storage, g, N, E, n_etype, n_ntype, block_n, False, None,
+                                f'the batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
 
     def graph_prep_cap(self, batch, node_type, n_etype, n_ntype, block_n=0, storage=None):
         """batch: data_utils.EdgeListBatch on the device with a capacity (batch.e_cap >= batch.E; edge_index [2, >= e_cap], edge_type
@@ -424,22 +442,12 @@ class HipKernels(metaclass=_GuardedMeta):
         assert 0 <= E <= e_cap, f'edge capacity {e_cap} below the batch\'s {E} edges'
         assert ei.size(1) >= e_cap and et.numel() >= e_cap, f'edge buffers of {ei.size(1)} / {et.numel()} entries below the capacity {e_cap}'
         ld = ei.stride(0) if ei.size(1) > 1 else ei.size(1)
-        elems = self.lib.qagnn_graph_storage_elems(N, e_cap, n_etype, n_ntype)
-        if storage is None:
-            storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
-        assert storage.is_cuda and storage.dtype == torch.int32 and storage.is_contiguous() and storage.numel() >= elems
-        g = qagnn_graph()
-        if block_n and N % block_n:
-            block_n = 0
+        storage, g = self._graph_alloc(N, e_cap, n_etype, n_ntype, node_type.device, storage)
+        block_n = self._block_n(block_n, N)
         rc = self.lib.qagnn_graph_prep_cap(C.byref(g), storage.data_ptr(), ei.data_ptr(), ld, et.data_ptr(), node_type.data_ptr(), N, e_cap,
-                                           cnt.data_ptr(), n_etype, n_ntype, int(block_n), self._stream())
-        self._check(rc, 'qagnn_graph_prep_cap')
-        G = HipGraph(storage, g, N, e_cap, n_etype, n_ntype, int(block_n))
-        G.dynamic = True  # E / Ep are capacities: the true E' lives on the device (rowptr_s[N])
-        G.keep = (ei, et, cnt)  # read by the kernels just enqueued
-        ERR_WATCH.poll()
-        ERR_WATCH.watch(G.array('err', 4), f'the graph of the edge-list batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
-        return G
+                                           cnt.data_ptr(), n_etype, n_ntype, block_n, self._stream())
+        return self._graph_done(rc, 'qagnn_graph_prep_cap', storage, g, N, e_cap, n_etype, n_ntype, block_n, True, (ei, et, cnt),
+                                f'the edge-list batch with N={N} node rows, E={E} edges (edge endpoint / relation id / node type)')
 
     def graph_from_blobs(self, packed, node_type):
         """packed: data_utils.PackedGraphBatch on the device (the batch's load-time blobs); node_type [B*n] int64.
@@ -448,24 +456,16 @@ class HipKernels(metaclass=_GuardedMeta):
         of a capacity bucket (qagnn_amd.graphed)."""
         assert packed.buf.is_cuda and packed.buf.dtype == torch.int32 and node_type.dtype == torch.long and node_type.is_contiguous()
         B, n, R, T = packed.B, packed.n, packed.n_etype, packed.n_ntype
-        e_cap = getattr(packed, 'e_cap', None)
-        E = packed.E if e_cap is None else int(e_cap)
+        E = packed.E if packed.e_cap is None else int(packed.e_cap)
         assert E >= packed.E, f'edge capacity {E} below the batch\'s {packed.E} edges'
         N = B * n
         assert node_type.numel() == N
-        elems = self.lib.qagnn_graph_storage_elems(N, E, R, T)
-        storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
-        g = qagnn_graph()
+        storage, g = self._graph_alloc(N, E, R, T, node_type.device)
         base = packed.buf.data_ptr()
         rc = self.lib.qagnn_graph_from_blobs(C.byref(g), storage.data_ptr(), base + 4 * packed.head, base, base + 4 * (B + 1),
                                              node_type.data_ptr(), B, n, E, R, T, self._stream())
-        self._check(rc, 'qagnn_graph_from_blobs')
-        G = HipGraph(storage, g, N, E, R, T, n)
-        G.dynamic = e_cap is not None  # E / Ep are capacities: the true E' lives on the device (rowptr_s[N] = sum of cls_count)
-        G.keep = packed.buf  # the blobs are read by the kernel just enqueued
-        ERR_WATCH.poll()
-        ERR_WATCH.watch(G.array('err', 4), f'the graph of the blob batch with B={B} samples, E={packed.E} edges (edge endpoint / relation id / node type)')
-        return G
+        return self._graph_done(rc, 'qagnn_graph_from_blobs', storage, g, N, E, R, T, n, packed.e_cap is not None, packed.buf,
+                                f'the blob batch with B={B} samples, E={packed.E} edges (edge endpoint / relation id / node type)')
 
     def _cstore(self, store):
         """the qagnn_store of a data_utils.DeviceGraphStore on the GPU (built once per store, kept on it)"""
@@ -512,18 +512,11 @@ class HipKernels(metaclass=_GuardedMeta):
         assert E >= batch.E, f'edge capacity {E} below the batch\'s {batch.E} edges'
         N = B * n
         assert node_type.numel() == N and batch.ids.numel() == B and edge_off.numel() == B + 1
-        elems = self.lib.qagnn_graph_storage_elems(N, E, R, T)
-        storage = torch.empty(elems, dtype=torch.int32, device=node_type.device)
-        g = qagnn_graph()
+        storage, g = self._graph_alloc(N, E, R, T, node_type.device)
         rc = self.lib.qagnn_graph_from_store(C.byref(g), storage.data_ptr(), C.byref(self._cstore(store)), batch.ids.data_ptr(), edge_off.data_ptr(),
                                              node_type.data_ptr(), B, E, R, T, self._stream())
-        self._check(rc, 'qagnn_graph_from_store')
-        G = HipGraph(storage, g, N, E, R, T, n)
-        G.dynamic = batch.e_cap is not None
-        G.keep = (store, batch.ids, edge_off)  # read by the kernels just enqueued
-        ERR_WATCH.poll()
-        ERR_WATCH.watch(G.array('err', 4), f'the graph of the store batch with B={B} samples, E={batch.E} edges (sample id / blob field / node type)')
-        return G
+        return self._graph_done(rc, 'qagnn_graph_from_store', storage, g, N, E, R, T, n, batch.e_cap is not None, (store, batch.ids, edge_off),
+                                f'the store batch with B={B} samples, E={batch.E} edges (sample id / blob field / node type)')
 
     def seed_epoch_advance(self, delta=1):
         """Advance this device's dropout seed epoch (see qagnn_seed_epoch_advance): the last launch of a captured training step."""

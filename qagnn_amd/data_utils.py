@@ -302,20 +302,8 @@ class GraphBlobStore:
         return cls(np.load(prefix + '.blobs.npy', mmap_mode='r' if mmap else None), meta[4:4 + S + 1], meta[4 + S + 1:4 + 2 * S + 1], n, R, T)
 
 
-class PackedGraphBatch:
-    """A batch's graph on the device as ONE buffer of sample blobs (see GraphBlobStore.pack): what the batch generator yields
-    in place of the nested edge lists when it was given a blob store, and what LM_QAGNN / QAGNN accept as `adj`.  The
-    reference's nested per-graph lists are recovered lazily (host side) for the callers that want them."""
-
-    def __init__(self, buf, B, E, store, sample_ids, num_choice):
-        self.buf, self.B, self.E, self.store = buf, B, E, store
-        self.sample_ids, self.num_choice = list(sample_ids), num_choice
-        self.n, self.n_etype, self.n_ntype = store.n, store.n_etype, store.n_ntype
-        self.head = (2 * (B + 1) + 3) // 4 * 4
-
-    @property
-    def device(self):
-        return self.buf.device
+class _BlobLists:
+    """The reference's edge lists of a batch named by `sample_ids` in the host blob `store` (PackedGraphBatch, StoreBatch), decoded on the host."""
 
     def nested_lists(self, device=None):
         """(edge_index, edge_type) as nested lists [bs][nc] of int64 tensors: the reference generator's protocol."""
@@ -330,8 +318,49 @@ class PackedGraphBatch:
         """(edge_index [2, E], edge_type [E]) as LM_QAGNN.batch_graph would return them."""
         ei, et = self.nested_lists()
         bei, bet = batch_graph([g for row in ei for g in row], [g for row in et for g in row], self.n)
-        dev = device if device is not None else self.buf.device
+        dev = device if device is not None else self.device
         return bei.to(dev), bet.to(dev)
+
+
+# What every holder of a batch's graph (PackedGraphBatch, StoreBatch, EdgeListBatch: GRAPH_HOLDERS below) answers for its own layout:
+#   build(K, node_type, n_etype, n_ntype, block_n)  the prepared graph, through the kernel provider K (ops.build_graph)
+#   capture_kind()                                  the hashable that tells captures of graphed.GraphedStep on different inputs apart
+#   static_twin(B, n, e_cap, device)                a holder of the same kind over zeroed static buffers of that edge capacity
+#   refill(src)                                     copy batch `src` into this twin's buffers (non-blocking) and take over its description
+#   own_fields                                      the four node tensors are the holder's own (fields() after reset()), not the caller's
+class PackedGraphBatch(_BlobLists):
+    """A batch's graph on the device as ONE buffer of sample blobs (see GraphBlobStore.pack): what the batch generator yields
+    in place of the nested edge lists when it was given a blob store, and what LM_QAGNN / QAGNN accept as `adj`.  The
+    reference's nested per-graph lists are recovered lazily (host side) for the callers that want them.
+    e_cap (optional, >= E): the edge CAPACITY to lay the graph arrays out for (_lib.HipKernels.graph_from_blobs)."""
+    own_fields = False
+
+    def __init__(self, buf, B, E, store, sample_ids, num_choice, e_cap=None):
+        self.buf, self.B, self.E, self.store, self.e_cap = buf, B, E, store, e_cap
+        self.sample_ids, self.num_choice = list(sample_ids), num_choice
+        self.n, self.n_etype, self.n_ntype = store.n, store.n_etype, store.n_ntype
+        self.head = (2 * (B + 1) + 3) // 4 * 4
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def build(self, K, node_type, n_etype, n_ntype, block_n):
+        assert self.n == block_n and self.n_etype == n_etype and self.n_ntype == n_ntype, 'blob store built for another model shape'
+        return K.graph_from_blobs(self, node_type)
+
+    def capture_kind(self):
+        return 'blobs'
+
+    def static_twin(self, B, n, e_cap, device):
+        buf = torch.zeros(self.head + 2 * n * B + 3 * e_cap, dtype=torch.int32, device=device)
+        return PackedGraphBatch(buf, B, self.E, self.store, self.sample_ids, self.num_choice, e_cap)
+
+    def refill(self, src):
+        nwords = src.buf.numel()
+        assert nwords <= self.buf.numel() and src.E <= self.e_cap and src.B == self.B and src.n == self.n
+        self.buf[:nwords].copy_(src.buf, non_blocking=True)
+        self.E, self.sample_ids = src.E, list(src.sample_ids)  # (the description follows the words: nested_lists(), the validation label)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -421,12 +450,13 @@ class DeviceGraphStore:
         return StoreBatch(self, ids, num_choice, self._stage(ids.astype(np.int32)), int(self.store.edge_count[ids].sum()))
 
 
-class StoreBatch:
+class StoreBatch(_BlobLists):
     """A batch named by its sample ids in a DeviceGraphStore: what the batch generator yields in place of the nested edge lists when it was
     given a device store, and what LM_QAGNN / QAGNN / graphed.GraphedStep accept as `adj` beside PackedGraphBatch and EdgeListBatch.
 
     ids     int32 tensor [B] on the store's device       E      the batch's edge count (host sum of the store's edge counts)
     e_cap   (optional, >= E) the edge CAPACITY to lay the graph arrays out for, as PackedGraphBatch.e_cap"""
+    own_fields = True
 
     def __init__(self, dstore, sample_ids, num_choice, ids, E, e_cap=None):
         self.dstore, self.store, self.ids, self.E, self.e_cap = dstore, dstore.store, ids, int(E), e_cap
@@ -491,20 +521,28 @@ class StoreBatch:
             buf, B, E = self.store.pack(self.sample_ids, pin=on_gpu)
             assert (B, E) == (self.B, self.E)
             self._packed = PackedGraphBatch(buf.to(self.device, non_blocking=True) if on_gpu else buf, B, E, self.store, self.sample_ids, self.num_choice)
-        if self.e_cap is not None:
-            self._packed.e_cap = self.e_cap
+        self._packed.e_cap = self.e_cap
         return self._packed
 
-    def nested_lists(self, device=None):
-        """(edge_index, edge_type) as nested lists [bs][nc] of int64 tensors: the reference generator's protocol."""
-        return PackedGraphBatch.nested_lists(self, device)
+    def build(self, K, node_type, n_etype, n_ntype, block_n):
+        assert self.n == block_n and self.n_etype == n_etype and self.n_ntype == n_ntype, 'device store built for another model shape'
+        if hasattr(K, 'graph_from_store') and node_type.is_cuda:
+            return K.graph_from_store(self, node_type)
+        return self.to_packed().build(K, node_type, n_etype, n_ntype, block_n)
 
-    def batched(self, device=None):
-        """(edge_index [2, E], edge_type [E]) as LM_QAGNN.batch_graph would return them."""
-        ei, et = self.nested_lists()
-        bei, bet = batch_graph([g for row in ei for g in row], [g for row in et for g in row], self.n)
-        dev = device if device is not None else self.device
-        return bei.to(dev), bet.to(dev)
+    def capture_kind(self):
+        return 'store', id(self.dstore)
+
+    def static_twin(self, B, n, e_cap, device):
+        """the static input is the id list: gather and graph assembly read it, inside the captured graph"""
+        assert self.device == device, 'the device store must live on the model\'s device'
+        return StoreBatch(self.dstore, self.sample_ids, self.num_choice, torch.zeros((B,), dtype=torch.int32, device=device), self.E, e_cap)
+
+    def refill(self, src):
+        """B int32 words; the node fields are gathered on the device, by the replayed graph"""
+        assert src.E <= self.e_cap
+        self.ids.copy_(src.ids, non_blocking=True)
+        self.adopt(src)
 
 
 def batch_graph(edge_index_init, edge_type_init, n_nodes):
@@ -531,6 +569,7 @@ class EdgeListBatch:
             which is what a captured hipGraph needs (graphed.GraphedStep sets it; so may a caller who wants one allocation size per bucket).
             Without it the pair is sliced to its first E entries and takes the plain sorting path.
     count   a one-element int32 device tensor holding E: created where the batch reaches the device (to()), None on the host."""
+    own_fields = False
 
     def __init__(self, edge_index, edge_type, E=None, e_cap=None, count=None):
         assert edge_index.dim() == 2 and edge_index.size(0) == 2 and edge_type.dim() == 1
@@ -569,6 +608,31 @@ class EdgeListBatch:
     def pair(self):
         """(edge_index [2, E], edge_type [E]): the plain pair, padding cut off (views)."""
         return self.edge_index[:, :self.E], self.edge_type[:self.E]
+
+    def build(self, K, node_type, n_etype, n_ntype, block_n):
+        b = self if self.device == node_type.device else self.to(node_type.device)
+        if b.e_cap is not None and hasattr(K, 'graph_prep_cap') and node_type.is_cuda:
+            return K.graph_prep_cap(b, node_type, n_etype, n_ntype, block_n=block_n)
+        return K.graph_prep(*b.pair(), node_type, n_etype, n_ntype, block_n=block_n)  # (no capacity form: the pair, sliced to its E entries)
+
+    def capture_kind(self):
+        return 'edge lists'
+
+    def static_twin(self, B, n, e_cap, device):
+        """int64 edge lists in static buffers of the capacity + the count word the preparation kernels read"""
+        return EdgeListBatch(torch.zeros((2, e_cap), dtype=torch.long, device=device), torch.zeros((e_cap,), dtype=torch.long, device=device),
+                             self.E, e_cap, count=torch.zeros((1,), dtype=torch.int32, device=device))
+
+    def refill(self, src):
+        E = src.E
+        assert E <= self.e_cap
+        self.edge_index[:, :E].copy_(src.edge_index[:, :E], non_blocking=True)  # entries [E, e_cap) keep an earlier batch: never read
+        self.edge_type[:E].copy_(src.edge_type[:E], non_blocking=True)
+        self.count.fill_(E)  # (a launch argument, like the loss weight: nothing waits for the device)
+        self.E = E
+
+
+GRAPH_HOLDERS = (PackedGraphBatch, EdgeListBatch, StoreBatch)
 
 
 class MultiGPUSparseAdjDataBatchGenerator(object):

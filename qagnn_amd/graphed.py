@@ -33,7 +33,7 @@ import math
 import torch
 
 from . import ops
-from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
+from .data_utils import GRAPH_HOLDERS, EdgeListBatch
 
 
 def edge_capacity(E, floor=1024):
@@ -44,8 +44,8 @@ def edge_capacity(E, floor=1024):
 
 
 class _Captured:
-    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'blob', 'ids', 'lw', 'packed', 'ei', 'et', 'ecount', 'logits', 'attn', 'loss', 'grads', 'replays',
-                 'params', 'watched', 'sent_grad')
+    # packed: the static twin of the graph input (data_utils: static_twin / refill), the holder the captured step reads
+    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'lw', 'packed', 'logits', 'attn', 'loss', 'grads', 'replays', 'params', 'watched', 'sent_grad')
 
 
 class GraphedStep:
@@ -78,7 +78,7 @@ class GraphedStep:
 
     # -- the eager step that gets captured -------------------------------------------------------------------------------------------
     def _step(self, c):
-        if c.ids is not None:
+        if c.packed.own_fields:
             c.packed.reset()  # the gather is part of the step: it reads the static id buffer, the model consumes its outputs in place
             c.cids, c.nt, c.ns, c.al = c.packed.fields()
         logits, attn = self.model(c.sent, c.cids, c.nt, c.ns, c.al, c.packed)
@@ -88,14 +88,11 @@ class GraphedStep:
 
     def _key(self, sent, cids, packed):
         trainable = tuple(i for i, p in enumerate(self.model.parameters()) if p.requires_grad)
-        if isinstance(packed, StoreBatch):
-            B, n, kind = packed.B, packed.n, ('store', id(packed.dstore))
-        else:
-            B, n, kind = cids.size(0), cids.size(1), 'blobs' if isinstance(packed, PackedGraphBatch) else 'edge lists'
-        return (B, n, sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad), hash(trainable), kind)
+        B, n = (packed.B, packed.n) if packed.own_fields else (cids.size(0), cids.size(1))
+        return (B, n, sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad), hash(trainable), packed.capture_kind())
 
     def _capture(self, key, args):
-        B, n, sent_dim, e_cap, _, sent_rg, _, kind = key
+        B, n, sent_dim, e_cap, _, sent_rg = key[:6]
         sent, cids, nt, ns, al, packed, labels, lw = args
         dev, K = self.dev, ops.kernels()
         from ._lib import ERR_WATCH
@@ -103,29 +100,15 @@ class GraphedStep:
         c.params = [p for p in self.model.parameters() if p.requires_grad]
         c.watched, c.sent_grad = [], None
         c.sent = torch.empty((B, sent_dim), dtype=torch.float32, device=dev, requires_grad=sent_rg)
-        store_kind = isinstance(kind, tuple)
-        c.cids = c.nt = c.ns = c.al = None  # (a store batch: outputs of the captured gather)
-        if not store_kind:
+        c.cids = c.nt = c.ns = c.al = None  # (a holder with fields of its own: outputs of the captured gather)
+        if not packed.own_fields:
             c.cids = torch.empty((B, n), dtype=torch.long, device=dev)
             c.nt = torch.empty((B, n), dtype=torch.long, device=dev)
             c.ns = torch.empty((B, n, 1), dtype=torch.float32, device=dev)
             c.al = torch.empty((B,), dtype=torch.long, device=dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev)
         c.lw = torch.ones((), dtype=torch.float32, device=dev)
-        c.blob = c.ei = c.et = c.ecount = c.ids = None
-        if store_kind:  # the static input is the id list; gather and graph assembly run inside the captured graph and read it
-            assert packed.device == dev, 'the device store must live on the model\'s device'
-            c.ids = torch.zeros((B,), dtype=torch.int32, device=dev)
-            c.packed = StoreBatch(packed.dstore, packed.sample_ids, packed.num_choice, c.ids, packed.E, e_cap)
-        elif kind == 'blobs':
-            c.blob = torch.zeros(packed.head + 2 * n * B + 3 * e_cap, dtype=torch.int32, device=dev)
-            c.packed = PackedGraphBatch(c.blob, B, packed.E, packed.store, packed.sample_ids, packed.num_choice)
-            c.packed.e_cap = e_cap
-        else:  # int64 edge lists in static buffers of the bucket's capacity + the count word the preparation kernels read
-            c.ei = torch.zeros((2, e_cap), dtype=torch.long, device=dev)
-            c.et = torch.zeros((e_cap,), dtype=torch.long, device=dev)
-            c.ecount = torch.zeros((1,), dtype=torch.int32, device=dev)
-            c.packed = EdgeListBatch(c.ei, c.et, packed.E, e_cap, count=c.ecount)
+        c.packed = packed.static_twin(B, n, e_cap, dev)  # the graph input in static buffers laid out for the bucket's capacity
         c.replays = 0
         self._load(c, args)
         # warm-up outside the capture (lazy initialisation: operand-packing plans, LDS attribute raises, allocator pools), on a side
@@ -178,29 +161,15 @@ class GraphedStep:
             c.sent.copy_(sent, non_blocking=True)
         c.labels.copy_(labels, non_blocking=True)
         c.lw.fill_(float(lw))
-        if c.ids is not None:  # a store batch: B int32 words; the node fields are gathered on the device, by the replayed graph
-            assert packed.E <= c.packed.e_cap
-            c.ids.copy_(packed.ids, non_blocking=True)
-            c.packed.adopt(packed)
-            return
-        c.cids.copy_(cids, non_blocking=True)
-        c.nt.copy_(nt, non_blocking=True)
-        c.ns.copy_(ns.reshape(c.ns.shape), non_blocking=True)
-        c.al.copy_(al, non_blocking=True)
-        if c.blob is None:
-            E = packed.E
-            assert E <= c.packed.e_cap
-            c.ei[:, :E].copy_(packed.edge_index[:, :E], non_blocking=True)  # entries [E, e_cap) keep an earlier batch: never read
-            c.et[:E].copy_(packed.edge_type[:E], non_blocking=True)
-            c.ecount.fill_(E)  # (a launch argument, like the loss weight: nothing waits for the device)
-            c.packed.E = E
-            return
-        nwords = packed.buf.numel()
-        assert nwords <= c.blob.numel() and packed.E <= c.packed.e_cap and packed.B == c.packed.B and packed.n == c.packed.n
-        c.blob[:nwords].copy_(packed.buf, non_blocking=True)
+        if not c.packed.own_fields:
+            c.cids.copy_(cids, non_blocking=True)
+            c.nt.copy_(nt, non_blocking=True)
+            c.ns.copy_(ns.reshape(c.ns.shape), non_blocking=True)
+            c.al.copy_(al, non_blocking=True)
+        c.packed.refill(packed)
 
     def __call__(self, sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight=1.0, accumulate=False):
-        if not isinstance(packed, (PackedGraphBatch, EdgeListBatch, StoreBatch)):
+        if not isinstance(packed, GRAPH_HOLDERS):
             assert isinstance(packed, (tuple, list)) and len(packed) == 2 and all(isinstance(t, torch.Tensor) for t in packed), \
                 'GraphedStep takes the graph as a PackedGraphBatch, an EdgeListBatch, a StoreBatch or an (edge_index [2, E], edge_type [E]) pair'
             packed = EdgeListBatch(packed[0], packed[1], count=False)  # (no count word of its own: the capture's static one is written)

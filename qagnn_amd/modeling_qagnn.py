@@ -643,14 +643,12 @@ class LM_QAGNN(nn.Module):
         flat = [x.reshape(bs * nc, *x.shape[2:]) for x in inputs[:-2]]
         *lm_inputs, concept_ids, node_type_ids, node_scores, adj_lengths = flat
         dev = node_type_ids.device
-        from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
-        if isinstance(edge_index_orig, (PackedGraphBatch, StoreBatch)):
-            # the batch generator shipped the graph as one buffer of load-time blobs (or as sample ids into the store of all of them on
-            # the device): batch_graph's offsets are applied in-kernel
+        from .data_utils import GRAPH_HOLDERS
+        if isinstance(edge_index_orig, GRAPH_HOLDERS):
+            # the batch generator shipped the graph as one buffer of load-time blobs, as sample ids into the store of all of them on the
+            # device (batch_graph's offsets are applied in-kernel), or already batched with its edge count (EdgeListBatch.from_lists =
+            # batch_graph; moved to the decoder's device where the graph is built)
             adj = edge_index_orig
-        elif isinstance(edge_index_orig, EdgeListBatch):
-            # already batched (EdgeListBatch.from_lists = batch_graph) and carrying its edge count; handed back as is under `detail`
-            adj = edge_index_orig if edge_index_orig.device == dev else edge_index_orig.to(dev)
         else:
             edge_index = [g for row in edge_index_orig for g in row]  # (:224) nested [bs][nc] -> flat [bs*nc]
             edge_type = [g for row in edge_type_orig for g in row]
@@ -662,7 +660,7 @@ class LM_QAGNN(nn.Module):
         logits = logits.view(bs, nc)
         if not detail:
             return logits, attn
-        if isinstance(edge_index_orig, (PackedGraphBatch, StoreBatch)):
+        if hasattr(edge_index_orig, 'nested_lists'):  # (an EdgeListBatch has none: handed back as is)
             edge_index_orig, edge_type_orig = edge_index_orig.nested_lists()  # what the reference returns here (:237-239)
         return logits, attn, concept_ids.view(bs, nc, -1), node_type_ids.view(bs, nc, -1), edge_index_orig, edge_type_orig
 

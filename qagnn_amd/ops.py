@@ -359,23 +359,13 @@ def build_graph(adj, node_type, n_etype, n_ntype, block_n):
     blobs, one device buffer), the reference's (edge_index [2, E], edge_type [E]) int64 pair, or a data_utils.EdgeListBatch (that pair
     with its edge count: with a capacity it takes the capacity form of the sorting path, where the provider has one), or a
     data_utils.StoreBatch (sample ids into a device-resident store: the blobs are read where they lie; a provider without
-    graph_from_store is handed the same batch packed on the host, StoreBatch.to_packed)."""
-    K = kernels()
-    from .data_utils import EdgeListBatch, PackedGraphBatch, StoreBatch
-    if isinstance(adj, StoreBatch):
-        assert adj.n == block_n and adj.n_etype == n_etype and adj.n_ntype == n_ntype, 'device store built for another model shape'
-        if hasattr(K, 'graph_from_store') and node_type.is_cuda:
-            return K.graph_from_store(adj, node_type)
-        adj = adj.to_packed()
-    if isinstance(adj, EdgeListBatch):
-        if adj.e_cap is not None and hasattr(K, 'graph_prep_cap') and node_type.is_cuda:
-            return K.graph_prep_cap(adj.to(node_type.device) if adj.device != node_type.device else adj, node_type, n_etype, n_ntype, block_n=block_n)
-        adj = adj.pair()
-    packed = adj if isinstance(adj, PackedGraphBatch) else (adj[0] if isinstance(adj[0], PackedGraphBatch) else None)
-    if packed is not None:
-        assert packed.n == block_n and packed.n_etype == n_etype and packed.n_ntype == n_ntype, 'blob store built for another model shape'
-        return K.graph_from_blobs(packed, node_type)
-    return K.graph_prep(adj[0], adj[1], node_type, n_etype, n_ntype, block_n=block_n)
+    graph_from_store is handed the same batch packed on the host, StoreBatch.to_packed).  A holder may also arrive as the generator yields
+    it, (holder, None).  The plain pair is taken as an EdgeListBatch without capacity: like one, it is copied to node_type's device where it
+    lives on another."""
+    from .data_utils import GRAPH_HOLDERS, EdgeListBatch
+    if not isinstance(adj, GRAPH_HOLDERS):  # (holder, None) as the batch generator yields it, or the plain pair: an EdgeListBatch without capacity
+        adj = adj[0] if adj[1] is None else EdgeListBatch(adj[0], adj[1], count=False)
+    return adj.build(kernels(), node_type, n_etype, n_ntype, block_n)
 
 
 def graph_prep_async(adj, node_type, n_etype, n_ntype, block_n):

@@ -211,6 +211,66 @@ def test_module_on_a_store_batch_equals_the_packed_batch_on_the_emulation_provid
         assert all(torch.equal(outs[0][2][k], o[2][k]) for k in o[2])
 
 
+TWIN_IDS = {'A': [5, 7, 2, 9], 'B': [4, 3, 0, 8], 'too large': [10, 11, 5, 7]}  # 251 edges, then 83, then 1050: against a capacity of 300
+GRAPH_ARRAYS = ('rowptr_s', 'rowptr_t', 'eid_s', 'tgt_s', 'src_s', 'cls_s', 'src_t', 'tgt_t', 'cls_t', 'pos_t', 'pos_c', 'src_c', 'tgt_c', 'cls_count',
+                'chunkptr', 'chunk_cls', 'chunk_beg', 'chunk_len')
+
+
+def _holder(kind, h, d, ids, e_cap=None):
+    """the batch `ids` of the store in one of the three forms graphed.GraphedStep accepts, laid out for `e_cap` edges"""
+    if kind == 'store':
+        sb = d.batch(ids, 2)
+        sb.e_cap = e_cap
+        return sb
+    packed = _packed(h, ids, 2)
+    packed.e_cap = e_cap
+    return packed if kind == 'blobs' else data_utils.EdgeListBatch.from_lists(*packed.nested_lists(), h.n, e_cap=e_cap)
+
+
+@pytest.mark.parametrize('kind', ['edge lists', 'blobs', 'store'])
+def test_static_twin_refilled_twice_describes_the_second_batch(kind):
+    """What graphed.GraphedStep does around a capture and before every replay, on the CPU: a twin at a capacity above both batches, refilled
+    from A and then from B (fewer edges), is B -- in its own fields and in the graph ops.build_graph makes of it."""
+    from emu_kernels import EmuKernels
+    h, cap = _train_store(), 300
+    d = h.device('cpu')
+    A, B = _holder(kind, h, d, TWIN_IDS['A']), _holder(kind, h, d, TWIN_IDS['B'])
+    assert (A.E, B.E) == (251, 83)
+    twin = A.static_twin(4, h.n, cap, torch.device('cpu'))
+    assert type(twin) is type(A) and twin.e_cap == cap and twin.capture_kind() == A.capture_kind() == B.capture_kind()
+    assert twin.own_fields == (kind == 'store')
+    twin.refill(A)
+    assert twin.E == A.E
+    twin.refill(B)
+    assert twin.E == B.E and twin.e_cap == cap
+    if kind == 'edge lists':
+        assert twin.edge_index.shape == (2, cap) and twin.edge_type.shape == (cap,)
+        assert all(torch.equal(x, y) for x, y in zip(twin.pair(), B.pair()))
+        assert twin.count.dtype == torch.int32 and twin.count.tolist() == [B.E]
+        assert torch.equal(twin.edge_index[:, B.E:A.E], A.edge_index[:, B.E:A.E]), 'the stale tail is left in place: nobody reads it'
+    elif kind == 'blobs':
+        assert twin.buf.numel() == twin.head + 2 * h.n * 4 + 3 * cap and twin.buf.dtype == torch.int32
+        assert torch.equal(twin.buf[:B.buf.numel()], B.buf)
+    else:
+        assert torch.equal(twin.ids, B.ids) and twin.sample_ids == B.sample_ids and twin.dstore is d
+        twin.reset()
+        got, want = twin.gathered(), B.gathered()
+        assert got[5] is None and want[5] is None and all(torch.equal(x, y) for x, y in zip(got[:5], want[:5]))
+    nt = h.nt[TWIN_IDS['B']].reshape(-1)
+    old = ops.set_kernels(EmuKernels())
+    try:
+        g = ops.build_graph(twin, nt, h.R, T, h.n)
+        ref = ops.build_graph(_holder(kind, h, d, TWIN_IDS['B'], cap), nt, h.R, T, h.n)
+    finally:
+        ops.set_kernels(old)
+    assert (g.N, g.E, g.n_groups, g.n_chunks, g.max_chunks) == (ref.N, ref.E, ref.n_groups, ref.n_chunks, ref.max_chunks) and g.E == B.E
+    for name in GRAPH_ARRAYS:
+        assert torch.equal(getattr(g, name), getattr(ref, name)), name
+    with pytest.raises(AssertionError):
+        twin.refill(_holder(kind, h, d, TWIN_IDS['too large']))
+    assert twin.E == B.E
+
+
 def test_host_refusals():
     h = _special()
     d = h.device('cpu')
