@@ -55,12 +55,6 @@ namespace qagnn {
 
 namespace nn2 {
 
-// QAGNN_NN2_ABL (tools/nn2_ablate.hip only; numerically wrong, timing only): bit 0 no loads in the steady loop, bit 1 no B split / store,
-// bit 2 no A split, bit 3 no barrier, bit 4 no fragment reads, bit 5 no MFMAs, bit 6 no stores of the result
-#ifndef QAGNN_NN2_ABL
-#define QAGNN_NN2_ABL 0
-#endif
-
 constexpr int BK = 32;
 constexpr uint32_t OOB = 0x80000000u;  // beyond any operand this kernel is launched on: the buffer load answers with zeros
 
@@ -367,18 +361,14 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                                                   \
         u32x4s(&bf)[NP] = (j & 1) ? bfb : bfa;                                                                           \
         u32x4s(&bn)[NP] = (j & 1) ? bfa : bfb;                                                                           \
-        if (j + 1 < NT && !(QAGNN_NN2_ABL & 16)) {                                                                       \
+        if (j + 1 < NT) {                                                                                                \
           _Pragma("unroll") for (int p = 0; p < NP; ++p)                                                                 \
               bn[p] = *reinterpret_cast<const u32x4s*>((CUR) + ((j + 1) * NP + p) * 1024 + rd_off);                      \
         }                                                                                                                \
-        if constexpr (!(QAGNN_NN2_ABL & 32)) {                                                                           \
-          _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                \
-            f32x4s c = acc[i][j];                                                                                        \
-            if constexpr (DIRECT) { QAGNN_NN2_SIX_T(c, af[i], bf) } else { QAGNN_NN2_SIX(c, af[i], bf) }                  \
-            acc[i][j] = c;                                                                                               \
-          }                                                                                                              \
-        } else {                                                                                                         \
-          _Pragma("unroll") for (int p = 0; p < NP; ++p) asm volatile("" ::"v"(bf[p]));                                  \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                  \
+          f32x4s c = acc[i][j];                                                                                          \
+          if constexpr (DIRECT) { QAGNN_NN2_SIX_T(c, af[i], bf) } else { QAGNN_NN2_SIX(c, af[i], bf) }                   \
+          acc[i][j] = c;                                                                                                 \
         }                                                                                                                \
         if ((STORE) && j >= NT - BR) QAGNN_NN2_STORE_B(j - (NT - BR), NXT)                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
@@ -416,12 +406,10 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         } else {                                                                                                         \
           QAGNN_NN2_FRAG_WAIT(bf, 0);                                                                                    \
         }                                                                                                                \
-        if constexpr (!(QAGNN_NN2_ABL & 32)) {                                                                           \
-          _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                \
-            f32x4s c = acc[i][j];                                                                                        \
-            if constexpr (DIRECT) { QAGNN_NN2_SIX_T(c, af[i], bf) } else { QAGNN_NN2_SIX(c, af[i], bf) }                  \
-            acc[i][j] = c;                                                                                               \
-          }                                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                  \
+          f32x4s c = acc[i][j];                                                                                          \
+          if constexpr (DIRECT) { QAGNN_NN2_SIX_T(c, af[i], bf) } else { QAGNN_NN2_SIX(c, af[i], bf) }                   \
+          acc[i][j] = c;                                                                                                 \
         }                                                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
       }                                                                                                                  \
@@ -494,16 +482,12 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       for (int it = 0; it < nkt; ++it) {
         const uint32_t cur = lds0 + (uint32_t)((it % 3) * IMG);
         // N: fragments of tile it, loads of tile it + 1 (A) / it + 1 + g (this wave's share of B)
-        if ((QAGNN_NN2_ABL & 4) == 0 || it == 0) QAGNN_NN2_SPLIT_A(it)
+        QAGNN_NN2_SPLIT_A(it)
         QAGNN_NN2_FRAG(bfr[0], cur, 0)
         if constexpr (NT > 1) QAGNN_NN2_FRAG(bfr[1], cur, 1)
-        if constexpr (!(QAGNN_NN2_ABL & 1)) {
-          if (it + 1 < nkt) QAGNN_NN2_GLOAD(it + 1)
-        }
-        if constexpr (!(QAGNN_NN2_ABL & 2)) {
-          const int tb = it + 1 + g;
-          if (tb < nkt) QAGNN_NN2_GLDS(tb, smem + (tb % 3) * IMG)
-        }
+        if (it + 1 < nkt) QAGNN_NN2_GLOAD(it + 1)
+        const int tb = it + 1 + g;
+        if (tb < nkt) QAGNN_NN2_GLDS(tb, smem + (tb % 3) * IMG)
         QAGNN_NN2_BAR
         // M
         QAGNN_NN2_MFMA_TILE3(cur)
@@ -525,11 +509,11 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     for (int it = 0; it + 1 < nkt; ++it) {
       unsigned char* const cur = smem + (it & 1) * IMG;
       unsigned char* const nxt = smem + ((it & 1) ^ 1) * IMG;
-      if constexpr (PACKED && !(QAGNN_NN2_ABL & 2)) QAGNN_NN2_GLDS(it + 1, nxt)
-      if constexpr (!(QAGNN_NN2_ABL & 1)) QAGNN_NN2_GLOAD(it + 1)
-      QAGNN_NN2_MFMA_TILE(cur, nxt, !PACKED && !(QAGNN_NN2_ABL & 2))   // + tile it + 1's B rows -> nxt
-      if constexpr (!(QAGNN_NN2_ABL & 4)) QAGNN_NN2_SPLIT_A(it + 1)  // tile it + 1's A fragments (the MFMAs above were the last readers of af)
-      if constexpr (!(QAGNN_NN2_ABL & 8)) __syncthreads();  // nxt is complete; everybody is done reading cur
+      if constexpr (PACKED) QAGNN_NN2_GLDS(it + 1, nxt)
+      QAGNN_NN2_GLOAD(it + 1)
+      QAGNN_NN2_MFMA_TILE(cur, nxt, !PACKED)  // + tile it + 1's B rows -> nxt
+      QAGNN_NN2_SPLIT_A(it + 1)               // tile it + 1's A fragments (the MFMAs above were the last readers of af)
+      __syncthreads();                        // nxt is complete; everybody is done reading cur
     }
     {
       unsigned char* const cur = smem + ((nkt - 1) & 1) * IMG;
@@ -596,11 +580,7 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         for (int j = 0; j < NT; ++j) {
           const int col = en0 + j * 16 + c4;
           const uint32_t off = crow[i] != OOB && col < No ? crow[i] + (uint32_t)col * 4u : OOB;
-          if constexpr (QAGNN_NN2_ABL & 64) {
-            if (acc[i][j][0] == 1.2345e-30f) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, acc[i][j]), rC, (int)off, 0, 0);
-          } else {
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, acc[i][j]), rC, (int)off, 0, 0);
-          }
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, acc[i][j]), rC, (int)off, 0, 0);
         }
       continue;
     }
@@ -669,11 +649,7 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (a.rowtab) v = add4(v, ld4(a.rowtab + (int64_t)a.rowidx[row] * a.ldt + col));
         float* dst = a.C + (int64_t)row * a.ldc + col;
         if (a.accumulate) v = add4(v, ld4(dst));
-        if constexpr (QAGNN_NN2_ABL & 64) {
-          if (v.x == 1.2345e-30f) st4(dst, v);
-        } else {
-          st4(dst, v);
-        }
+        st4(dst, v);
       }
     }
     if constexpr (STATS) {

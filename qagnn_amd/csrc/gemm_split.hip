@@ -55,14 +55,6 @@ __device__ __forceinline__ void store_split(uint16_t* __restrict__ img, int img_
   *reinterpret_cast<uint2*>(img + img_elems + off) = make_uint2(pack_hi(a2, b2), pack_hi(c2, d2));
   *reinterpret_cast<uint2*>(img + 2 * img_elems + off) = make_uint2(pack_hi(a3, b3), pack_hi(c3, d3));
 }
-// timing ablations only (QAGNN_ABL_NO?SPLIT): the three stores without the split arithmetic
-__device__ __forceinline__ void store_nosplit(uint16_t* __restrict__ img, int img_elems, int off, float4 v) {
-  const uint2 h = make_uint2(pack_hi(__builtin_bit_cast(uint32_t, v.x), __builtin_bit_cast(uint32_t, v.y)),
-                             pack_hi(__builtin_bit_cast(uint32_t, v.z), __builtin_bit_cast(uint32_t, v.w)));
-  *reinterpret_cast<uint2*>(img + off) = h;
-  *reinterpret_cast<uint2*>(img + img_elems + off) = h;
-  *reinterpret_cast<uint2*>(img + 2 * img_elems + off) = h;
-}
 // element offset of (row, k) in a swizzled [rows][32] bf16 image
 // The XOR pattern follows ds_read_b128's lane groups (MI355X_MICROARCH.md, LDS): a fragment read (lane -> row lane & 15, chunk lane >> 4)
 // is serviced in four NON-contiguous 16-lane groups, e.g. {0-3, 12-15, 20-27} = rows 0-3, 12-15 of chunk c with rows 4-11 of chunk
@@ -73,17 +65,6 @@ __device__ __forceinline__ int swz(int row, int k) {
   const int g = (0x78 >> (((row >> 2) & 3) << 1)) & 3;
   return row * SBK + ((((k >> 3) ^ g) & 3) << 3) + (k & 7);
 }
-
-// QAGNN_NN_TRACE (tools/nn_trace.hip only): cycle stamps of one block's waves at the phase boundaries of every k-tile
-#ifdef QAGNN_NN_TRACE
-__device__ unsigned long long g_nn_trace[4][40][7];
-#define NN_STAMP(kt, ph)                                                                                                   \
-  do {                                                                                                                     \
-    if (blockIdx.x == QAGNN_NN_TRACE && vb == (int)blockIdx.x && lane == 0 && (kt) < 40) g_nn_trace[w][kt][ph] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define NN_STAMP(kt, ph)
-#endif
 
 // FLAT: operands addressed with 64-bit pointers (row gather through a_rowidx, or an operand of 2 GB and more); otherwise every
 // load goes through a buffer descriptor: per-thread 32-bit row offsets fixed per output tile, the k position as the instruction's
@@ -190,41 +171,24 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
           const bool ok = kin && (!first || arow[p] >= 0) && (first || m0 + lr + p * 32 < a.M);
           v = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
         }  // (buffer loads: zeros already; under AFFINE an out-of-range k leaves relu(shift) here, multiplied by B's zeros)
-#ifdef QAGNN_ABL_NOASPLIT  // timing ablation (tools/): no split arithmetic for A -- the high halves go to all three images
-        store_nosplit(As, A_EL, swz(lr + p * 32, kl), v);
-#else
         store_split(As, A_EL, swz(lr + p * 32, kl), v);
-#endif
       }
 #pragma unroll
       for (int q = 0; q < B_IT; ++q) {
         const int col = lr + q * 32;
         if (col < BN) {
           const float4 v = (!FLAT || (kin && n0 + col < a.No)) ? rb[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef QAGNN_ABL_NOBSPLIT  // timing ablation (tools/): what a weight operand that arrives pre-split would save
-          store_nosplit(Bs, B_EL, swz(col, kl), v);
-#else
           store_split(Bs, B_EL, swz(col, kl), v);
-#endif
         }
       }
     };
 
     gload(0);
     for (int kt = 0; kt < nkt; ++kt) {
-      NN_STAMP(kt, 0);
       __syncthreads();  // the previous tile's fragment reads (or the previous output tile's slab reads) are done
-      NN_STAMP(kt, 1);
-#ifdef QAGNN_NN_TRACE
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the tile's global loads have landed (separates their latency from the split)
-      NN_STAMP(kt, 6);
-#endif
       lstore(kt);
-      NN_STAMP(kt, 2);
       __syncthreads();
-      NN_STAMP(kt, 3);
       gload(min(kt + 1, nkt - 1));  // in flight under the MFMAs; past the last tile: a redundant reload, never stored
-      NN_STAMP(kt, 4);
       // the wave in its MFMA phase goes first at the SIMD's issue port (over the co-resident block's wave, which is in its load / split
       // phase): 3-6 % on the products alone, 0.1-0.4 % on the step (profiles/r3_run36_setprio.txt)
       __builtin_amdgcn_s_setprio(1);
@@ -252,7 +216,6 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         }
       }
       __builtin_amdgcn_s_setprio(0);
-      NN_STAMP(kt, 5);
     }
 
     // epilogue: transpose 16 rows at a time through the wave's LDS slab, then whole-row 16-byte stores (as k_gemm_nn)
@@ -639,11 +602,6 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 //     kind: the matrix pipe sees an MFMA stream, the vector ALU the split arithmetic, at the same time.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int WTHR = 512;
-// QAGNN_TNW_ABL (tools/tn_ablate.hip only; numerically wrong, timing only): bit 0 the producers do not split / store, bit 1 the producers
-// do not load, bit 2 the compute waves issue no MFMAs, bit 3 no fragment reads either, bit 4 the producers wait for their loads and drop them
-#ifndef QAGNN_TNW_ABL
-#define QAGNN_TNW_ABL 0
-#endif
 
 // store_task with a per-lane floor (AFF: relu for the lanes of A, -inf = pass-through for the lanes of B)
 template <bool AFF, int NP>
@@ -784,10 +742,6 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       // two register sets per task slot: the loads of tile t + 2 are issued BEFORE the split work of tile t + 1 and have a whole
       // k-tile to land (even tiles in set a, odd tiles in set b)
       float4 r1a[8], r2a[8], r1b[8], r2b[8];
-      if constexpr ((QAGNN_TNW_ABL & 2) != 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r1a[i] = r2a[i] = r1b[i] = r2b[i] = make_float4(1.f + lane, 2.f, 3.f, 4.f);
-      }
       // the rows of tile T of task slot K -> the registers RR (a task-wave that straddles the end of A asks both operands and ORs)
 #define QAGNN_TNW_LOAD1(T, K, RR)                                                                          \
       {                                                                                                    \
@@ -806,17 +760,12 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       }
       // TP: the tile's position modulo 4 (t itself is a multiple of 4)
 #define QAGNN_TNW_LOAD(T, TP, R1, R2)                                                                      \
-      if constexpr (!(QAGNN_TNW_ABL & 2)) {                                                                \
+      {                                                                                                    \
         QAGNN_TNW_LOAD1(T, 0, R1)                                                                          \
         if constexpr (NTW > 4 && ((IDX - (TP)) & 3) == 0) QAGNN_TNW_LOAD1(T, 1, R2)                        \
       }
 #define QAGNN_TNW_STORE(T, TP, R1, R2)                                                                     \
-      if constexpr ((QAGNN_TNW_ABL & 16) != 0) { /* wait for the tile's loads, do nothing with them */     \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(R1[i].x), "v"(R1[i].w));       \
-        if constexpr (NTW > 4 && ((IDX - (TP)) & 3) == 0) {                                                \
-          _Pragma("unroll") for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(R2[i].x), "v"(R2[i].w));     \
-        }                                                                                                  \
-      } else if constexpr (!(QAGNN_TNW_ABL & 1)) {                                                         \
+      {                                                                                                    \
         uint16_t* const img_ = reinterpret_cast<uint16_t*>(smem_tw) + ((TP)&1) * IMG_EL;                   \
         if (off[0] >= 0) store_task_lo<AFFINE, NP>(img_, iel[0], off[0], R1, sc[0], sh[0], lo[0], ssc[0]); \
         if constexpr (NTW > 4 && ((IDX - (TP)) & 3) == 0) {                                                \
@@ -894,16 +843,11 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     else if constexpr (NP == 2) asm volatile("" : "+v"(F[0]), "+v"(F[1]));               \
     else asm volatile("" : "+v"(F[0]));                                                  \
   }
-#define QAGNN_TNW_SIX(C, AF, BF)                                          \
-  if constexpr ((QAGNN_TNW_ABL & 4) != 0) { asm volatile("" ::"v"(AF[0]), "v"(AF[NP > 1 ? 1 : 0]), "v"(BF[0]), "v"(BF[NP > 1 ? 1 : 0])); } else { C = mfma_pieces<NP>(AF, BF, C); }
+#define QAGNN_TNW_SIX(C, AF, BF) C = mfma_pieces<NP>(AF, BF, C);
 
   QAGNN_TNW_BAR  // image 0 is complete
   for (int t = 0; t < ntile4; ++t) {
     if (t >= ntile) {  // (the producers' group of four is not over)
-      QAGNN_TNW_BAR
-      continue;
-    }
-    if constexpr ((QAGNN_TNW_ABL & 8) != 0) {
       QAGNN_TNW_BAR
       continue;
     }

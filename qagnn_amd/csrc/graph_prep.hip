@@ -553,9 +553,6 @@ static int xcd_partition(qagnn_graph* g, hipStream_t stream) {
 }
 
 static hipError_t zero_range(void* p, size_t bytes, hipStream_t stream) {
-#ifdef QAGNN_PREP_MEMSET_NODE  // the faulty form, only to reproduce the fault (tools/build_micro.sh -> scripts/r5_memset_node_fault.sh)
-  return hipMemsetAsync(p, 0, bytes, stream);
-#endif
   // (the callers' layout guarantees both: carve() rounds every array to 4 words and the storage is checked for 16-byte alignment; a layout
   // change that broke either would leave a tail of stale counters behind, so it fails here instead)
   if (bytes % 16 != 0 || !aligned16(p)) return hipErrorInvalidValue;

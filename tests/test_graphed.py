@@ -142,8 +142,8 @@ def test_replays_enqueued_back_to_back_equal_the_eager_step(nq, prep_overlap, mo
 
     Regression test of round 5's memset-node fault (csrc/graph_prep.hip, k_zero16): ROCm 7.2 replays the captured
     hipMemsetAsync node of a fork-free hipGraph with a fill pattern read from a kernel-argument slot that eager launches recycle, and
-    the first call sequence that shows it is "synchronise, three calls".  With the library built -DQAGNN_PREP_MEMSET_NODE the
-    `prep_overlap = False` cases fail in the first group (scripts/r5_memset_node_fault.sh, profiles/r5_run31_memset_node_fault.txt)."""
+    the first call sequence that shows it is "synchronise, three calls".  The negative control was run once: with the zero fill rebuilt
+    as a hipMemsetAsync node the `prep_overlap = False` cases failed in the first group (record: profiles/r5_run31_memset_node_fault.txt)."""
     ops.set_kernels(None)
     from qagnn_amd import _lib
     monkeypatch.setattr(ops, 'PREP_OVERLAP', prep_overlap)

@@ -1,6 +1,5 @@
 // Timings of k_gemm_nn2 (csrc/gemm_nn2.hip) alone, HIP events, on the NN shapes of the 320-subgraph batch: the six-MFMA form as the
-// library launches it and the three-MFMA form (4-wave blocks).  With -DQAGNN_NN2_ABL=<bits> (see the kernel source)
-// the 4-wave kernels drop parts of their k-loop: numerically wrong, timing only.  Build: tools/build_micro.sh, run: tools/bin/nn2_ablate_<bits>.
+// library launches it, the three-MFMA form and the one-MFMA form (4-wave blocks).  Build: tools/build_micro.sh, run: tools/bin/nn2_ablate.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -49,7 +48,7 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  printf("QAGNN_NN2_ABL=%d M=%d\n", QAGNN_NN2_ABL, M);
+  printf("M=%d\n", M);
   for (auto& sh : shapes) {
     float* A1 = dev_rand((size_t)M * sh.K1, 1);
     float* A2 = sh.K2 ? dev_rand((size_t)M * sh.K2, 2) : nullptr;

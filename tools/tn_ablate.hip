@@ -1,5 +1,5 @@
-// Timing ablations of k_gemm_tn_ws / k_gemm_tn_split (csrc/gemm_split.hip compiled into this program with -DQAGNN_TNW_ABL=<bits>): the
-// weight-gradient products of the 320-subgraph batch, kernel alone (no chunk sum), HIP events.  Numerically wrong for ABL != 0.
+// Timings of k_gemm_tn_ws / k_gemm_tn_split (csrc/gemm_split.hip compiled into this program): the weight-gradient products of the
+// 320-subgraph batch, kernel alone (no chunk sum), HIP events.  Build: tools/build_micro.sh, run: tools/bin/tn_ablate.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -47,7 +47,7 @@ int main() {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  printf("QAGNN_TNW_ABL=%d R=%d\n", QAGNN_TNW_ABL, R);
+  printf("R=%d\n", R);
   for (auto& sh : shapes) {
     float* A1 = dev_rand((size_t)R * sh.Ka1, 1);
     float* A2 = sh.Ka2 ? dev_rand((size_t)R * sh.Ka2, 2) : nullptr;
