@@ -27,6 +27,8 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows',
            'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32', 'qagnn_graph_prep_cap',
            'qagnn_store_gather', 'qagnn_graph_from_store']
+# include/qagnn_hip_tn.h, the extension header of the live-tile weight gradient (qagnn_hip.h and its ABI number are unchanged by it)
+EXPORTS_TN = ['qagnn_gemm_tn_graph_f32', 'qagnn_gemm_tn_route_query', 'qagnn_tn_work_table', 'qagnn_tn_live_tiles']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
 ABI_VERSION = 25  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY; 25: qagnn_store, qagnn_store_gather, qagnn_graph_from_store -- the dataset's graphs resident on the device)
@@ -126,6 +128,11 @@ def load_library(path=LIB_PATH):
     lib.qagnn_gemm_tn2_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]
     lib.qagnn_gemm_tn_h2_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.qagnn_gemm_tn_h1_f32.argtypes = lib.qagnn_gemm_tn_h2_f32.argtypes
+    lib.qagnn_gemm_tn_graph_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32,
+                                            C.POINTER(qagnn_graph), _vp, _vp]
+    lib.qagnn_gemm_tn_route_query.argtypes = [_i32, _i32, _i32, _i32, _vp]
+    lib.qagnn_tn_work_table.argtypes = [C.POINTER(qagnn_graph), _i32, _i32, _vp, _vp]
+    lib.qagnn_tn_live_tiles.argtypes = [_i32]
     lib.qagnn_absmax_f32.argtypes = [_vp, _i64, _vp, _vp]
     lib.qagnn_zero_words.argtypes = [_vp, _i64, _vp]
     lib.qagnn_timing_enable.argtypes = [_i32]
@@ -168,7 +175,7 @@ def load_library(path=LIB_PATH):
     lib.qagnn_hop_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _vp]
     lib.qagnn_stack_fwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
     lib.qagnn_stack_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_TN:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -302,6 +309,14 @@ class HipGraph:
         off = (getattr(self.c, name) - self.storage.data_ptr()) // 4
         return self.storage[off:off + length]
 
+    def live_tiles(self):
+        """(live_tiles [T], live_list [T], n_live [1]) of the T = ceil(N / 32) k-tiles: int32 views of the words behind err
+        (include/qagnn_hip_tn.h)"""
+        T = (self.N + 31) // 32
+        T4 = (T + 3) // 4 * 4
+        w = self.array('err', 16 + 4 + 2 * T4)[16:]
+        return w[4:4 + T], w[4 + T4:4 + T4 + T], w[:1]
+
     @property
     def cls_count(self):
         return self.array('cls_count', self.C)
@@ -356,6 +371,7 @@ class HipKernels(metaclass=_GuardedMeta):
     """Tensor-level calls into libqagnn_hip.so, each on the current HIP stream of the device that holds its operands
     (see _on_operand_device)."""
     name = 'hip'
+    tn_live = True  # the native hop hands its graph to the dWx_t | dWs_t product (live k-tiles, gemm_tn_graph): ops.hop_bwd_composed follows
 
     def __init__(self):
         if not torch.cuda.is_available():
@@ -760,6 +776,38 @@ class HipKernels(metaclass=_GuardedMeta):
                                            _ptr(a_shift), amax_a1.data_ptr(), _ptr(amax_a2), amax_b.data_ptr(), ws.data_ptr(), self._stream())
         self._check(rc, 'qagnn_gemm_tn_h2_f32')
         return out
+
+    def gemm_tn_graph(self, A1, A2, B, graph=None, pieces=3, amax=None, out=None):
+        """[A1 | A2]^T B for a B = dK | dM | dQ over the node rows of `graph` (qagnn_gemm_tn_graph_f32): the K / Q columns skip the graph's dead
+        k-tiles where the dispatch runs the long two-operand kernel.  graph=None: the plain product.  pieces 3 | 2 | 1; amax = (a1, a2, b)
+        absmax() words for pieces < 3."""
+        _chkp(A1, 'A1'), _chkp(A2, 'A2'), _chkp(B, 'B')
+        Ka1, Ka2 = A1.size(1), A2.size(1)
+        R, No = B.shape
+        assert A1.size(0) == R and A2.size(0) == R and (pieces == 3 or amax is not None)
+        out, ws = self._tn_out_ws(R, Ka1 + Ka2, No, out, B.device)
+        am = [None, None, None] if amax is None else [t.data_ptr() for t in amax]
+        rc = self.lib.qagnn_gemm_tn_graph_f32(A1.data_ptr(), _ld(A1), Ka1, A2.data_ptr(), _ld(A2), Ka2, B.data_ptr(), _ld(B), out.data_ptr(), _ld(out),
+                                              R, No, am[0], am[1], am[2], pieces, C.byref(graph.c) if graph is not None else None, ws.data_ptr(),
+                                              self._stream())
+        self._check(rc, 'qagnn_gemm_tn_graph_f32')
+        return out
+
+    def tn_route_query(self, R, Ka1, Ka2, No):
+        """host-only: (family, chunk_rows, nchunks, live) of the weight gradient [A1 | A2]^T B (qagnn_gemm_tn_route_query); family 3 = k_gemm_tn_ws"""
+        out = (_i32 * 4)()
+        self._check(self.lib.qagnn_gemm_tn_route_query(R, Ka1, Ka2, No, C.cast(out, _vp)), 'qagnn_gemm_tn_route_query')
+        return tuple(out)
+
+    def tn_work_table(self, graph, S, chunk_tiles):
+        """int32 [4 + 5 S]: cK, cM, T, L, then (column block, list?, first, tiles, partial tile) per unit (qagnn_tn_work_table)"""
+        out = torch.empty(4 + 5 * S, dtype=torch.int32, device=graph.storage.device)
+        self._check(self.lib.qagnn_tn_work_table(C.byref(graph.c), S, chunk_tiles, out.data_ptr(), self._stream()), 'qagnn_tn_work_table')
+        return out
+
+    def tn_live_tiles(self, on):
+        """TESTS AND A/B RUNS ONLY: the process-wide switch of the live-tile weight gradient (-1 reads); returns the previous value"""
+        return int(self.lib.qagnn_tn_live_tiles(int(on)))
 
     def gemm_tn2(self, A1, A2, B, out=None):
         """[A1 | A2]^T B -> [Ka1 + Ka2, No]: two weight gradients that share their B operand, one launch (qagnn_gemm_tn2_f32)."""

@@ -18,7 +18,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 
 def source_hash():
     h = hashlib.sha256(' '.join(FLAGS).encode())
-    paths = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'qagnn_hip.h')]
+    paths = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'qagnn_hip.h'),
+                                                           os.path.join(HERE, '..', 'include', 'qagnn_hip_tn.h')]
     for p in paths:
         with open(p, 'rb') as f:
             h.update(os.path.basename(p).encode() + b'\0' + f.read() + b'\0')

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "../../include/qagnn_hip.h"
+#include "../../include/qagnn_hip_tn.h"
 
 namespace qagnn {
 
@@ -69,6 +70,7 @@ struct TnProduct {  // C [Ka1 (+ Ka2), No] (+)= [A1 | A2]^T B over R rows, throu
   float* bsum; const int64_t* b_rowidx; int groups;  // column sums of B per group, by-product of the same pass
   const uint32_t* amax[3]; int np;                   // {max|A1|, max|A2|, max|B|} device words + the scaled form they ask for (2 or 1)
   float* ws;
+  const qagnn_graph* g;                              // the graph whose rows are the R rows of a K|M|Q gradient B (live k-tiles), or nullptr
 };
 // (one operand: A2 == nullptr or Ka2 <= 0)
 inline TnProduct tn_product(const float* A1, int lda1, int Ka1, const float* A2, int lda2, int Ka2, const float* B, int ldb, float* C, int ldc, int R,
@@ -89,6 +91,7 @@ struct TnRoute {
   bool affine, gather, colsum;
   int chunk_rows, nchunks;
   bool sum_by4;               // the chunk sum in float4 steps
+  bool live;                  // WS: the blocks take their k-tiles from the graph's live-tile list (tn_work below)
   dim3 grid;
   int64_t ws_elems;           // floats of ws the route writes
 };
@@ -100,6 +103,65 @@ int launch_tn_split(const TnRoute& r, const TnProduct& p, hipStream_t stream);
 int launch_tn_ws(const TnRoute& r, const TnProduct& p, hipStream_t stream);
 // C (+)= the chunks' partials P [nchunks][rows][No], summed in order (by4: float4 steps -- ldc, No multiples of 4, C 16-byte aligned)
 int launch_sum_chunks(const float* P, float* C, int ldc, int rows, int No, int nchunks, int accumulate, bool by4, hipStream_t stream);
+
+// ---- the two-operand weight gradient balanced by LIVE k-tiles (k_gemm_tn_ws<.., LIVE>) ---------------------------------------------
+// B = dK | dM | dQ of a hop: a node row whose only edge is its self loop has dK = dQ = 0 exactly, so a 32-row k-tile of such rows
+// ("dead") adds nothing to the K and Q column blocks.  The launch keeps its grid -- 3 column blocks x row blocks x nchunks, S = 3 nchunks
+// chunk slots per row block -- and divides the slots by work: cK slots each for K and Q, which walk lists of live tiles, cM = S - 2 cK for
+// M, which walk ranges of all tiles, so that every block walks about T (1 + 2 L / T) / S tiles.  Everything below is integer arithmetic on
+// (S, T, L): a pure function of the graph, the same in every block, in the chunk sum and on the host.
+constexpr int TN_LIST_CAP = 1024;  // k-tiles of one slot (staged in LDS); tn_route keeps longer products off the route
+constexpr int TN_LIVE_BC = 208;    // the column block: K, M and Q are 208 columns each (DP = 208)
+struct TnLive { const int* list; const int* n_live; int T, S, chunk_tiles; };
+struct TnWork { int cK, cM, lenM, qK, rK; };  // qK < 0: no dead tile -- every column block walks today's chunks
+struct TnSlot { int cb, list, beg, cnt, pslot; };  // column block; list (1) or range (0) of cnt tiles from beg; partial tile in the workspace
+__host__ __device__ inline TnWork tn_work(int S, int T, int L, int chunk_tiles) {
+  TnWork w;
+  L = L < 0 ? 0 : (L > T ? T : L);
+  if (L >= T) {  // the partition of the launch without a table: S / 3 chunks of chunk_tiles for every column block
+    w.cK = S / 3; w.cM = S - 2 * w.cK; w.lenM = chunk_tiles; w.qK = -1; w.rK = 0;
+    return w;
+  }
+  const long long den = (long long)T + 2ll * L;
+  int c = (int)((2ll * S * L + den) / (2 * den));  // round(S L / (T + 2 L))
+  const int hi = (S - 1) / 2;
+  c = c < 1 ? 1 : (c > hi ? hi : c);
+  w.cK = c; w.cM = S - 2 * c; w.lenM = (T + w.cM - 1) / w.cM; w.qK = L / c; w.rK = L % c;
+  return w;
+}
+// Unit u in [0, S) of a row block, in block order: group j = K slot j, Q slot j, then the M slots [j cM / cK, (j + 1) cM / cK) -- the K and
+// Q blocks of one slot index are neighbours (they walk the same list), and the M ranges advance through the rows with the lists.
+__host__ __device__ inline TnSlot tn_slot(const TnWork& w, int S, int T, int u) {
+  auto start = [&](int j) { return 2 * j + (int)((long long)j * w.cM / w.cK); };
+  int j = (int)((long long)u * w.cK / S);
+  while (j > 0 && start(j) > u) --j;
+  while (j + 1 < w.cK && start(j + 1) <= u) ++j;
+  const int off = u - start(j);
+  TnSlot s;
+  auto range = [&](int i) { s.list = 0; s.beg = i * w.lenM < T ? i * w.lenM : T; s.cnt = T - s.beg < w.lenM ? T - s.beg : w.lenM; };
+  if (off < 2) {
+    s.cb = off == 0 ? 0 : 2;
+    s.pslot = off == 0 ? j : w.cK + j;
+    if (w.qK < 0) range(j);
+    else { s.list = 1; s.beg = j * w.qK + (j < w.rK ? j : w.rK); s.cnt = w.qK + (j < w.rK ? 1 : 0); }
+  } else {
+    const int m = (int)((long long)j * w.cM / w.cK) + off - 2;
+    s.cb = 1;
+    s.pslot = 2 * w.cK + m;
+    range(m);
+  }
+  return s;
+}
+// the chunk sum of that launch: P holds S tiles [rows][208], the K slots first, then Q's, then M's; summed in slot order
+int launch_sum_chunks_live(const float* P, float* C, int ldc, int rows, const TnLive& lv, int accumulate, hipStream_t stream);
+bool tn_live_enabled();
+// where graph preparation leaves a graph's live tiles: behind the 16 words of g->err (include/qagnn_hip_tn.h)
+struct LiveTiles { int n_tiles; int32_t *n_live, *live, *list; };
+inline LiveTiles live_tiles_of(const qagnn_graph* g) {
+  const int T = (int)(((int64_t)g->N + 31) / 32), T4 = (T + 3) & ~3;
+  int32_t* const p = g->err + 16;
+  return LiveTiles{T, p, p + 4, p + 4 + T4};
+}
 
 // producers that can leave max |output| behind for the three-MFMA GEMM form (elementwise.hip; amax = nullptr: plain launch)
 int launch_gelu_dropout(const float* X, const float* dY, float* out, int64_t n, float p, uint64_t seed, uint32_t* amax, float* amax_part,

@@ -564,6 +564,46 @@ __global__ __launch_bounds__(SC_G * 64) void k_sum_chunks4(const float* __restri
   }
 }
 
+// k_sum_chunks4 for the live-tile form of k_gemm_tn_ws (common.h: tn_work): P holds S tiles [Ka][208] -- the cK partials of the K
+// columns, the cK of the Q columns, the cM of the M columns -- and a float4 of C sums the tiles of its column block in slot order, with
+// the association of k_sum_chunks4 (wave g takes slots g, g + 16, ...; the waves' sums added in wave order).  The counts come from the
+// device's live-tile count through the function the producing kernel used.
+__global__ __launch_bounds__(SC_G * 64) void k_sum_chunks4_live(const float* __restrict__ P, float* __restrict__ C, int ldc, int Ka, TnLive lv,
+                                                                int accumulate) {
+  __shared__ float4 part[SC_G][64];
+  constexpr int BC = TN_LIVE_BC, No = 3 * BC;
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int64_t n4 = (int64_t)Ka * No / 4, i4 = (int64_t)blockIdx.x * 64 + lane;
+  const TnWork w = tn_work(lv.S, lv.T, lv.n_live[0], lv.chunk_tiles);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (i4 < n4) {
+    const int64_t e = i4 * 4;
+    const int row = (int)(e / No), col = (int)(e % No), cb = col / BC, lc = col - cb * BC;
+    const int first = cb == 0 ? 0 : cb == 2 ? w.cK : 2 * w.cK, n = cb == 1 ? w.cM : w.cK;  // first + n <= S: inside the workspace
+    const int64_t t4 = (int64_t)Ka * BC / 4;
+    const float4* src = reinterpret_cast<const float4*>(P) + (int64_t)first * t4 + ((int64_t)row * BC + lc) / 4;
+    for (int c0 = g; c0 < n; c0 += 4 * SC_G) {
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = src[(int64_t)min(c0 + u * SC_G, n - 1) * t4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (c0 + u * SC_G < n) s = add4(s, v[u]);
+    }
+  }
+  part[g][lane] = s;
+  __syncthreads();
+  if (g == 0 && i4 < n4) {
+    float4 t = part[0][lane];
+#pragma unroll
+    for (int k = 1; k < SC_G; ++k) t = add4(t, part[k][lane]);
+    const int64_t e = i4 * 4;
+    float* d = C + (e / No) * ldc + (e % No);
+    if (accumulate) t = add4(t, ld4(d));
+    st4(d, t);
+  }
+}
+
 // ---- launchers: one per kernel template, shaped by the product's route (gemm_dispatch.hip) ----------------------------------------
 // NN: 8-wave blocks walking the tiles persistently, QAGNN_NN_OCC (= 2) blocks per CU, XCD-aware tile order.  Measured at M = 64000
 // (profiles/r1_gemm_micro.txt, r1_run23_nn_xcd_ab.txt, r1_run32_gemm_ab.txt): 10-18 % faster than one 128-row tile per 4-wave block.
@@ -604,6 +644,13 @@ int launch_tn_strip(const TnRoute& r, const TnProduct& p, float* Pcs, hipStream_
   });
 }
 #undef QAGNN_TN_ARGS
+
+int launch_sum_chunks_live(const float* P, float* C, int ldc, int rows, const TnLive& lv, int accumulate, hipStream_t stream) {
+  const int64_t tot = (int64_t)rows * 3 * TN_LIVE_BC;
+  k_sum_chunks4_live<<<cdiv(tot / 4, 64), SC_G * 64, 0, stream>>>(P, C, ldc, rows, lv, accumulate);
+  QAGNN_LAUNCH_CHECK("k_sum_chunks4_live");
+  return QAGNN_OK;
+}
 
 int launch_sum_chunks(const float* P, float* C, int ldc, int rows, int No, int nchunks, int accumulate, bool by4, hipStream_t stream) {
   const int64_t tot = (int64_t)rows * No;

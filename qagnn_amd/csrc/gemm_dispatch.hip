@@ -194,6 +194,14 @@ static bool tn_split_ok(const TnProduct& p, int Ka, int lda) {
   return mode != 0 && Ka >= 64 && p.No >= 104 && p.R >= 1024 && big < (int64_t)0x7FFFFFFF;  // 32-bit buffer offsets
 }
 
+// the switch of qagnn_tn_live_tiles
+static std::atomic<int> g_tn_live{1};
+bool tn_live_enabled() { return g_tn_live.load(std::memory_order_relaxed) != 0; }
+// a graph whose node rows are the product's rows, and K | M | Q in the kernel's three 208-column blocks
+static bool tn_live_ok(const TnProduct& p) {
+  return p.g && tn_live_enabled() && p.two && p.No == 3 * TN_LIVE_BC && p.g->N == p.R && p.g->err && !p.a_scale;
+}
+
 TnRoute tn_route(const TnProduct& p) {
   TnRoute r = {};
   r.np = 3;
@@ -220,6 +228,12 @@ TnRoute tn_route(const TnProduct& p) {
       const int rows1 = tn_chunk_rows(p.R, bpc, 1, 32, lo);
       if (rows1 >= 2 * TN_WS_MIN_TILES * 32) r.chunk_rows = rows1;
       if (r.chunk_rows >= TN_WS_MIN_TILES * 32) r.family = TnFamily::WS;
+      // ... and with the graph of a K | M | Q gradient at hand, balanced by its live k-tiles (common.h: tn_work).  nchunks >= 3 chunk
+      // slots per column block; a slot's tiles fit the kernel's LDS list: lists hold <= 4.5 T / S tiles, ranges <= T / (S / 3 - 2)
+      if (r.family == TnFamily::WS && tn_live_ok(p)) {
+        const int T = cdiv(p.R, 32), nch = cdiv(p.R, r.chunk_rows);
+        r.live = nch >= 3 && 5 * (T / (3 * nch) + 1) <= TN_LIST_CAP && cdiv(T, nch - 2) <= TN_LIST_CAP;
+      }
     }
   } else if (p.two) {
     r.family = TnFamily::PAIR;
@@ -272,6 +286,10 @@ static int tn_run(const TnProduct& p, hipStream_t stream) {
                  : r.family == TnFamily::STRIP ? launch_tn_strip(r, p, Pcs, stream)
                                                : launch_tn(r, p, Pcs, stream);
   if (rc != QAGNN_OK) return rc;
+  if (r.live) {
+    const LiveTiles lt = live_tiles_of(p.g);
+    return launch_sum_chunks_live(p.ws, p.C, p.ldc, Ka, TnLive{lt.list, lt.n_live, lt.n_tiles, 3 * r.nchunks, r.chunk_rows / 32}, p.accumulate, stream);
+  }
   if (int rc2 = launch_sum_chunks(p.ws, p.C, p.ldc, Ka, p.No, r.nchunks, p.accumulate, r.sum_by4, stream)) return rc2;
   return r.colsum ? launch_sum_chunks(Pcs, p.bsum, p.No, p.groups, p.No, r.nchunks, 0, false, stream) : QAGNN_OK;
 }
@@ -346,6 +364,32 @@ extern "C" int qagnn_gemm_tn_h2_f32(const float* A1, int32_t lda1, int32_t Ka1, 
   return gemm_tn(tn_product(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, a_scale, a_shift, workspace, amax_a1, amax_a2, amax_b, 2),
                  (hipStream_t)stream);
 }
+
+extern "C" int qagnn_gemm_tn_graph_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
+                                       int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const uint32_t* amax_a1, const uint32_t* amax_a2,
+                                       const uint32_t* amax_b, int32_t pieces, const qagnn_graph* g, float* workspace, qagnn_stream_t stream) {
+  QAGNN_REQUIRE(pieces >= 1 && pieces <= 3, QAGNN_EINVAL, "gemm_tn_graph: pieces=%d (1..3)", pieces);
+  const bool h = pieces < 3;
+  TnProduct p = tn_product(A1, lda1, Ka1, A2, lda2, Ka2, B, ldb, C, ldc, R, No, nullptr, nullptr, workspace, h ? amax_a1 : nullptr,
+                           h ? amax_a2 : nullptr, h ? amax_b : nullptr, h ? pieces : 3);
+  p.g = g;
+  return gemm_tn(p, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_tn_route_query(int32_t R, int32_t Ka1, int32_t Ka2, int32_t No, int32_t* h_out) {
+  QAGNN_REQUIRE(h_out && R > 0 && Ka1 > 0 && Ka2 >= 0 && No > 0, QAGNN_EINVAL, "gemm_tn_route_query: bad arguments");
+  alignas(16) static float any[4];  // (the route looks at the presence and the alignment of pointers only)
+  qagnn_graph any_g = {};
+  TnProduct p = tn_product(any, Ka1, Ka1, Ka2 > 0 ? any : nullptr, Ka2, Ka2, any, No, any, No, R, No, nullptr, nullptr, any);
+  any_g.N = R;
+  any_g.err = reinterpret_cast<int32_t*>(any);
+  p.g = &any_g;
+  const TnRoute r = tn_route(p);
+  h_out[0] = (int)r.family; h_out[1] = r.chunk_rows; h_out[2] = r.nchunks; h_out[3] = r.live ? 1 : 0;
+  return QAGNN_OK;
+}
+
+extern "C" int qagnn_tn_live_tiles(int32_t on) { return on < 0 ? g_tn_live.load() : g_tn_live.exchange(on ? 1 : 0); }
 
 extern "C" int qagnn_gemm_tn_h1_f32(const float* A1, int32_t lda1, int32_t Ka1, const float* A2, int32_t lda2, int32_t Ka2, const float* B,
                                     int32_t ldb, float* C, int32_t ldc, int32_t R, int32_t No, const float* a_scale, const float* a_shift,

@@ -623,11 +623,15 @@ __device__ __forceinline__ void store_task_lo(uint16_t* __restrict__ img, int im
   }
 }
 
-template <int KT, int NT, bool AFFINE, int NP = 3>
+// LIVE (common.h: tn_work): the block's unit of work -- column block, and a LIST of live k-tiles (K, Q) or a RANGE of k-tiles (M) --
+// comes from the graph's live-tile list instead of (blockIdx, chunk_rows).  The tile numbers of the walk are staged in LDS behind the
+// two images, every one clamped to [0, T]; T itself stands for "no tile" (rows past R: the loads answer zeros).  The walk is by
+// POSITION: the producers' rotation and the two images alternate with the position in the list, whatever the tile numbers are.
+template <int KT, int NT, bool AFFINE, int NP = 3, bool LIVE = false>
 __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm_tn_ws(
     const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ P, int R, int Ka, int No,
     const float* __restrict__ a_scale, const float* __restrict__ a_shift, int chunk_rows, const float* __restrict__ A2, int lda2, int Ka2,
-    TnAmax amax) {
+    TnAmax amax, TnLive lv) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_tw[];
   constexpr int AC = KT * 16, BC = NT * 16, A_EL = AC * TCP, B_EL = BC * TCP;
   constexpr int IMG_EL = NP * (A_EL + B_EL), IMG_B = IMG_EL * 2;  // one k-tile's image: [A: piece][column][32 rows + pad] | [B: ...]
@@ -645,7 +649,16 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   // next to each other in time -- in launch order they are dealt out over all eight L2s and every operand row crosses the fabric once
   // per block that uses it (744 MB instead of 242 MB for the two-operand product: the kernel ran at the speed of those re-reads)
   int bx = blockIdx.x, by = blockIdx.y, chunk = blockIdx.z, row_shift = 0;
-  if (chunk_rows < 0) {
+  TnSlot slot = {};
+  if constexpr (LIVE) {
+    // the row blocks of a unit are neighbours in the XCD-contiguous order, then the units in tn_slot's order (K_j, Q_j, their M ranges)
+    const int lin = bx + (int)gridDim.x * (by + (int)gridDim.y * chunk);
+    const int v = xcd_remap(lin, (int)(gridDim.x * gridDim.y * gridDim.z));
+    by = v % (int)gridDim.y;
+    const int L = __builtin_amdgcn_readfirstlane(lv.n_live[0]);
+    slot = tn_slot(tn_work(lv.S, lv.T, L, lv.chunk_tiles), lv.S, lv.T, min(v / (int)gridDim.y, lv.S - 1));
+    bx = slot.cb;
+  } else if (chunk_rows < 0) {
     chunk_rows = -chunk_rows;
   } else {
     const int lin = bx + (int)gridDim.x * (by + (int)gridDim.y * chunk);
@@ -668,8 +681,20 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     sb = h2_field_to_scale(fb);
   }
   const int n0 = bx * BC, m0 = by * AC;
-  const int r_beg = chunk * chunk_rows, r_end = min(R, r_beg + chunk_rows);
-  const int ntile = (r_end - r_beg + TKR - 1) / TKR;  // chunk_rows is a multiple of TKR: only the last chunk has a ragged tile, past R
+  const int r_beg = LIVE ? 0 : chunk * chunk_rows, r_end = min(R, r_beg + chunk_rows);
+  // chunk_rows is a multiple of TKR: only the last chunk has a ragged tile, past R.  LIVE: the slot's tiles, at most what the list holds
+  const int ntile = LIVE ? min(max(slot.cnt, 0), TN_LIST_CAP) : (r_end - r_beg + TKR - 1) / TKR;
+  int* const tiles = reinterpret_cast<int*>(smem_tw + 2 * IMG_B + 64);  // LIVE: [ntile4 + 2] the tile at every position of the walk
+  if constexpr (LIVE) {
+    for (int i = tid; i < ((ntile + 3) & ~3) + 2; i += WTHR) {
+      int t = lv.T;
+      if (i < ntile) {
+        const int q = min(max(slot.beg, 0), lv.T - 1) + i;  // (a wrong table may give wrong numbers, never an address outside the operands)
+        t = slot.list ? min(max(lv.list[min(q, lv.T - 1)], 0), lv.T - 1) : min(q, lv.T - 1);
+      }
+      tiles[i] = t;
+    }
+  }
 
   // roles: the first wave to arrive on a SIMD computes, the second produces; should the hardware ever place the waves otherwise
   // (not 4 + 4), waves 0-3 compute and 4-7 produce -- correct either way, only the overlap is lost
@@ -745,7 +770,8 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       // the rows of tile T of task slot K -> the registers RR (a task-wave that straddles the end of A asks both operands and ORs)
 #define QAGNN_TNW_LOAD1(T, K, RR)                                                                          \
       {                                                                                                    \
-        const uint32_t a_ = voA[K] + (uint32_t)(T) * (TKR * ldA4), b_ = voB[K] + (uint32_t)(T) * (TKR * ldB4); \
+        const uint32_t t_ = LIVE ? (uint32_t)__builtin_amdgcn_readfirstlane(tiles[(T)]) : (uint32_t)(T);      \
+        const uint32_t a_ = voA[K] + t_ * (TKR * ldA4), b_ = voB[K] + t_ * (TKR * ldB4);                    \
         if constexpr (HAS_A[K] && HAS_B[K]) {                                                              \
           _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                  \
             const u32x4s x_ = __builtin_bit_cast(u32x4s, bload4(rsA, a_ + (uint32_t)i * ldA4)) |           \
@@ -904,14 +930,15 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #undef QAGNN_TNW_SIX
 #undef QAGNN_TNW_BAR
 
-  float* const Pc = P + (int64_t)chunk * ka_total * No;
+  // LIVE: the partial of this slot is one [ka_total][BC] tile of the workspace (S of them: the K slots, then Q's, then M's)
+  float* const Pc = LIVE ? P + (int64_t)min(max(slot.pslot, 0), lv.S - 1) * ka_total * BC : P + (int64_t)chunk * ka_total * No;
   const float inv = NP <= 2 ? h2_inv_scale(fa, fb) : 1.f;
   auto put = [&](int maj_strip, int min_tile, const f32x4s& c) {
     const int rstrip = MAJ_A ? maj_strip : min_tile, ctile = MAJ_A ? min_tile : maj_strip;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = m0 + rstrip * 16 + (lane >> 4) * 4 + r, col = n0 + ctile * 16 + (lane & 15);
-      if (row < Ka && col < No) Pc[(int64_t)(row + row_shift) * No + col] = NP <= 2 ? c[r] * inv : c[r];
+      const int row = m0 + rstrip * 16 + (lane >> 4) * 4 + r, lc = ctile * 16 + (lane & 15), col = n0 + lc;
+      if (row < Ka && col < No) Pc[LIVE ? (int64_t)(row + row_shift) * BC + lc : (int64_t)(row + row_shift) * No + col] = NP <= 2 ? c[r] * inv : c[r];
     }
   };
 #pragma unroll
@@ -928,14 +955,20 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 // ---- launchers (the route: gemm_dispatch.hip).  chunk_rows > 0: the blocks of one split-K chunk on one XCD (-2..5 % per kernel:
 // profiles/r4_run17_tn_ws.txt) -------------------------------------------------------------------------------------------------------
 #define QAGNN_TN_ARGS p.A1, p.lda1, p.B, p.ldb, p.ws, p.R, p.Ka1, p.No, p.a_scale, p.a_shift, r.chunk_rows
+static TnLive tn_live_args(const TnRoute& r, const TnProduct& p) {
+  if (!r.live) return TnLive{nullptr, nullptr, 0, 0, 0};
+  const LiveTiles lt = live_tiles_of(p.g);
+  return TnLive{lt.list, lt.n_live, lt.n_tiles, 3 * r.nchunks, r.chunk_rows / TKR};
+}
 static TnAmax tn_amax(const TnRoute& r, const TnProduct& p) {
   return r.np == 3 ? TnAmax{nullptr, nullptr, nullptr} : TnAmax{p.amax[0], p.two ? p.amax[1] : nullptr, p.amax[2]};
 }
-template <int KT, int NT, bool AFFINE, int NP = 3>
+template <int KT, int NT, bool AFFINE, int NP = 3, bool LIVE = false>
 static int launch_tn_ws_i(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
-  constexpr int lds = 2 * NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t) + 64;
-  if (int rc = raise_lds_limit<k_gemm_tn_ws<KT, NT, AFFINE, NP>>(lds, "k_gemm_tn_ws")) return rc;
-  k_gemm_tn_ws<KT, NT, AFFINE, NP><<<r.grid, WTHR, lds, stream>>>(QAGNN_TN_ARGS, p.A2, p.lda2, p.Ka2, tn_amax(r, p));
+  static_assert(!LIVE || NT * 16 == TN_LIVE_BC, "the live-tile form is built for 208-column blocks");
+  constexpr int lds = 2 * NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t) + 64 + (LIVE ? (TN_LIST_CAP + 8) * (int)sizeof(int) : 0);
+  if (int rc = raise_lds_limit<k_gemm_tn_ws<KT, NT, AFFINE, NP, LIVE>>(lds, "k_gemm_tn_ws")) return rc;
+  k_gemm_tn_ws<KT, NT, AFFINE, NP, LIVE><<<r.grid, WTHR, lds, stream>>>(QAGNN_TN_ARGS, p.A2, p.lda2, p.Ka2, tn_amax(r, p), tn_live_args(r, p));
   QAGNN_LAUNCH_CHECK("k_gemm_tn_ws");
   return QAGNN_OK;
 }
@@ -951,7 +984,9 @@ static int launch_tn_split_i(const TnRoute& r, const TnProduct& p, hipStream_t s
 
 // k_gemm_tn_ws is built for the two-operand product [X | S]^T dKMQ, (KT, NT) = (7, 13), in the three arithmetic forms
 int launch_tn_ws(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
-  return dispatch_int<3, 2, 1>(r.np, [&](auto np) { return launch_tn_ws_i<7, 13, false, np.value>(r, p, stream); });
+  return dispatch_int<3, 2, 1>(r.np, [&](auto np) {
+    return dispatch_bool(r.live, [&](auto live) { return launch_tn_ws_i<7, 13, false, np.value, live.value>(r, p, stream); });
+  });
 }
 // (KT, NT) = (7, 13) or (13, 7); the row gather exists for (13, 7) without prologue in the six-MFMA form
 int launch_tn_split(const TnRoute& r, const TnProduct& p, hipStream_t stream) {

@@ -532,6 +532,39 @@ __global__ void k_xcd_partition(const int* __restrict__ rowptr_s, int N, int cap
   }
 }
 
+// Live k-tiles (qagnn_graph.live_tiles / live_list / n_live).  Every node row has its self loop in both orders, so the rows of a tile
+// all have degree 1 exactly when the tile's edge count equals its row count: two rowptr differences per tile.  One block: flags, their
+// exclusive scan, then the stable partition live | dead.  No atomics: the arrays are a pure function of the two rowptr arrays.
+__global__ __launch_bounds__(1024) void k_live_tiles(const int* __restrict__ rowptr_s, const int* __restrict__ rowptr_t, int N, int T,
+                                                     int* __restrict__ live, int* __restrict__ rank, int* __restrict__ list,
+                                                     int* __restrict__ n_live) {
+  for (int t = threadIdx.x; t < T; t += 1024) {
+    const int r0 = t * 32, r1 = min(N, r0 + 32);
+    live[t] = (rowptr_s[r1] - rowptr_s[r0] != r1 - r0 || rowptr_t[r1] - rowptr_t[r0] != r1 - r0) ? 1 : 0;
+  }
+  __syncthreads();
+  block_exclusive_scan(live, rank, T);
+  __syncthreads();
+  const int L = rank[T];
+  for (int t = threadIdx.x; t < T; t += 1024) {
+    const int r = rank[t];
+    list[live[t] ? r : L + (t - r)] = t;
+  }
+  if (threadIdx.x == 0) *n_live = L;
+}
+
+// the work table of the live-tile weight gradient as its kernels see it (qagnn_tn_work_table: tests)
+__global__ void k_tn_work_table(const int* __restrict__ n_live, int T, int S, int chunk_tiles, int* __restrict__ out) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  const int L = min(max(n_live[0], 0), T);
+  const TnWork w = tn_work(S, T, L, chunk_tiles);
+  if (u == 0) { out[0] = w.cK; out[1] = w.cM; out[2] = T; out[3] = L; }
+  if (u >= S) return;
+  const TnSlot s = tn_slot(w, S, T, u);
+  int* o = out + 4 + 5 * u;
+  o[0] = s.cb; o[1] = s.list; o[2] = s.beg; o[3] = s.cnt; o[4] = s.pslot;
+}
+
 // Zero `bytes` (a multiple of 16, 16-byte aligned) with a kernel of this library, NOT hipMemsetAsync.  Measured (round 5, visits 27-28,
 // profiles/r5_run28_race_variants.txt, r5_run31_memset_node_fault.txt): ROCm 7.2 replays a captured hipMemsetAsync node of a LINEAR hipGraph (no forked stream:
 // DEBUG_CLR_GRAPH_PACKET_CAPTURE, on by default) with its 16-byte fill pattern read from a kernel-argument slot that later eager launches
@@ -552,6 +585,13 @@ static int xcd_partition(qagnn_graph* g, hipStream_t stream) {
   return QAGNN_OK;
 }
 
+static int live_tiles(qagnn_graph* g, int32_t* rank, hipStream_t stream) {
+  const LiveTiles lt = live_tiles_of(g);
+  k_live_tiles<<<1, 1024, 0, stream>>>(g->rowptr_s, g->rowptr_t, g->N, lt.n_tiles, lt.live, rank, lt.list, lt.n_live);
+  QAGNN_LAUNCH_CHECK("k_live_tiles");
+  return QAGNN_OK;
+}
+
 static hipError_t zero_range(void* p, size_t bytes, hipStream_t stream) {
   // (the callers' layout guarantees both: carve() rounds every array to 4 words and the storage is checked for 16-byte alignment; a layout
   // change that broke either would leave a tail of stale counters behind, so it fails here instead)
@@ -566,7 +606,7 @@ static hipError_t zero_range(void* p, size_t bytes, hipStream_t stream) {
 
 // carve `storage` into the arrays of *g plus scratch (layout shared by qagnn_graph_prep_blocked and qagnn_graph_from_blobs)
 struct carved {
-  int32_t *eid_t, *gc_cnt, *gcptr, *nch, *cnt_s, *cnt_t, *es, *et, *ec, *tmp_s, *tmp_t, *srcpos, *hist;
+  int32_t *eid_t, *gc_cnt, *gcptr, *nch, *cnt_s, *cnt_t, *es, *et, *ec, *tmp_s, *tmp_t, *srcpos, *hist, *live_rank;
   int nblk, gb, NG, pairs;
 };
 static carved carve(qagnn_graph* g, int32_t* storage, int N, int E, int R, int T, int block_n) {
@@ -590,11 +630,13 @@ static carved carve(qagnn_graph* g, int32_t* storage, int N, int E, int R, int T
   g->cls_count = take(C);
   g->chunk_cls = take(maxch); g->chunk_beg = take(maxch); g->chunk_len = take(maxch);
   g->n_chunks = take(4); g->err = take(16);  // err[4 .. 12]: the XCD partition of the node blocks (k_xcd_partition)
+  take(4 + 2 * up4(cdiv(N, 32)));           // the live k-tiles behind err: n_live | live_tiles | live_list (common.h: live_tiles_of)
   // ---- scratch; the zero-initialised region comes first (cls_count, which sits just before it, must be zero too) ----
   cv.cnt_s = take(N); cv.cnt_t = take(N);
   cv.es = take(Ep); cv.et = take(Ep); cv.ec = take(Ep);
   cv.tmp_s = take(Ep); cv.tmp_t = take(Ep); cv.srcpos = take(Ep);
   cv.hist = take((int64_t)cv.nblk * C);
+  cv.live_rank = take(cdiv(N, 32) + 1);  // the scan of the live-tile flags
   return cv;
 }
 
@@ -639,6 +681,8 @@ extern "C" int64_t qagnn_graph_storage_elems(int32_t N, int32_t E, int32_t R, in
   tot += 2 * up4(N);          // cnt_s, cnt_t
   tot += 6 * up4(Ep);         // es et ec tmp_s tmp_t srcpos
   tot += up4(nblk * C);       // per-block class histograms
+  const int64_t tiles = ((int64_t)N + 31) / 32;
+  tot += 2 * up4(tiles) + up4(4) + up4(tiles + 1);  // live_tiles, live_list, n_live, the scan of the flags
   return tot;
 }
 
@@ -683,6 +727,7 @@ static int prep_sorted(const char* who, qagnn_graph* g, int32_t* storage, const 
   QAGNN_LAUNCH_CHECK("k_payload");
   int rc = xcd_partition(g, stream);
   if (rc != QAGNN_OK) return rc;
+  if ((rc = live_tiles(g, cv.live_rank, stream)) != QAGNN_OK) return rc;
   return class_pass(g, hist, gc_cnt, gcptr, nch, nblk, gb, NG, pairs, stream);
 }
 
@@ -722,6 +767,7 @@ static int from_blobs(const char* who, qagnn_graph* g, int32_t* storage, const B
   QAGNN_LAUNCH_CHECK("k_blob_assemble");
   int rc = xcd_partition(g, stream);
   if (rc != QAGNN_OK) return rc;
+  if ((rc = live_tiles(g, cv.live_rank, stream)) != QAGNN_OK) return rc;
   return class_pass(g, cv.hist, cv.gc_cnt, cv.gcptr, cv.nch, cv.nblk, cv.gb, cv.NG, cv.pairs, stream);
 }
 
@@ -730,6 +776,15 @@ extern "C" int qagnn_graph_from_blobs(qagnn_graph* g, int32_t* storage, const in
                                       int32_t T, qagnn_stream_t stream_) {
   QAGNN_REQUIRE(g && storage && blobs && blob_off && edge_off && node_type, QAGNN_EINVAL, "graph_from_blobs: null pointer");
   return from_blobs("graph_from_blobs", g, storage, packed_blobs{blobs, blob_off}, edge_off, node_type, B, n, E, R, T, (hipStream_t)stream_);
+}
+
+extern "C" int qagnn_tn_work_table(const qagnn_graph* g, int32_t S, int32_t chunk_tiles, int32_t* out, qagnn_stream_t stream_) {
+  QAGNN_REQUIRE(g && out && g->err && g->N > 0, QAGNN_EINVAL, "tn_work_table: null pointer");
+  const LiveTiles lt = live_tiles_of(g);
+  QAGNN_REQUIRE(S >= 3 && S % 3 == 0 && chunk_tiles > 0, QAGNN_EINVAL, "tn_work_table: S=%d (a multiple of 3), chunk_tiles=%d", S, chunk_tiles);
+  k_tn_work_table<<<cdiv(S, 256), 256, 0, (hipStream_t)stream_>>>(lt.n_live, lt.n_tiles, S, chunk_tiles, out);
+  QAGNN_LAUNCH_CHECK("k_tn_work_table");
+  return QAGNN_OK;
 }
 
 static int check_store(const char* who, const qagnn_store* st) {

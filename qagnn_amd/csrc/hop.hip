@@ -108,10 +108,13 @@ static int hop_nn(const qagnn_hop_args* h, const qagnn_gemm_nn_args* a, const fl
 }
 // weight gradient C = [A1 | A2]^T B over the hop's N rows (A2 == nullptr: one operand); am_*: the operands' maxima -- the scaled form
 // the hop asks for where all of them are known (am_b is, in a backward that runs the form), the six-MFMA form otherwise
+// g: the hop's graph where B is dK | dM | dQ (the product skips the K / Q work of the graph's dead k-tiles), else nullptr
 static int hop_tn(const qagnn_hop_args* h, const float* A1, int Ka1, const float* A2, int Ka2, const float* B, int No, float* C, const float* sc,
-                  const float* sh, const uint32_t* am_a1, const uint32_t* am_a2, const uint32_t* am_b, float* tnws, qagnn_stream_t stream) {
-  return gemm_tn(tn_product(A1, Ka1, Ka1, A2, Ka2, Ka2, B, No, C, No, h->N, No, sc, sh, tnws, am_a1, am_a2, am_b, h->gemm_split == 3 ? 1 : 2),
-                 (hipStream_t)stream);
+                  const float* sh, const uint32_t* am_a1, const uint32_t* am_a2, const uint32_t* am_b, float* tnws, qagnn_stream_t stream,
+                  const qagnn_graph* g = nullptr) {
+  TnProduct p = tn_product(A1, Ka1, Ka1, A2, Ka2, Ka2, B, No, C, No, h->N, No, sc, sh, tnws, am_a1, am_a2, am_b, h->gemm_split == 3 ? 1 : 2);
+  p.g = g;
+  return gemm_tn(p, (hipStream_t)stream);
 }
 
 // x_ready / s_ready: the words of X / S already hold this call's maxima (an earlier hop of the stack produced them)
@@ -329,7 +332,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   // projection: weight gradients, node-type-table gradient, data gradients
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
   if (SP > 0 && h->dWs_t == h->dWx_t + (int64_t)DP * 3 * DP) {  // the two gradients are one [DP + SP, 3 DP] matrix: one product
-    HOP_TRY(hop_tn(h, h->X, DP, h->S, SP, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, am.s, w_dkmq, tnws, wstream));
+    HOP_TRY(hop_tn(h, h->X, DP, h->S, SP, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, am.s, w_dkmq, tnws, wstream, h->g));
   } else {
     HOP_TRY(hop_tn(h, h->X, DP, nullptr, 0, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, nullptr, w_dkmq, tnws, wstream));
     if (SP > 0) HOP_TRY(hop_tn(h, h->S, SP, nullptr, 0, dKMQ, 3 * DP, h->dWs_t, nullptr, nullptr, am.s, nullptr, w_dkmq, tnws, wstream));

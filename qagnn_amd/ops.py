@@ -875,7 +875,9 @@ def hop_bwd_composed(K, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p
                                                           ones_col, batch_stats)
     dKMQ, dEkEm = K.edge_attn_bwd(graph, KMQ, EkEm, HP, qscale, aa[0], aa[1], daggr)
     if S is not None:  # one launch for both (qagnn_gemm_tn2_f32), like qagnn_hop_bwd_f32 when its two outputs are adjacent
-        joint = K.gemm_tn2(X, S, dKMQ)
+        # (a provider whose native hop balances this product by the graph's live k-tiles says so -- tn_live -- and the composed path asks for
+        # the same form: the two stay bit-identical)
+        joint = K.gemm_tn_graph(X, S, dKMQ, graph=graph, pieces=3) if getattr(K, 'tn_live', False) else K.gemm_tn2(X, S, dKMQ)
         dWx_t, dWs_t = joint[:X.size(1)], joint[X.size(1):]
     else:
         dWx_t, dWs_t = K.gemm_tn(X, dKMQ), None
