@@ -16,11 +16,16 @@ SOURCES = ['graph_prep.hip', 'gemm.hip', 'elementwise.hip', 'edge_attn.hip', 'po
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 
 
+def hashed_files():
+    """Everything the library is compiled from: the sources, every header next to them, the public headers."""
+    headers = sorted(f for f in os.listdir(CSRC) if f.endswith('.h'))
+    return [os.path.join(CSRC, s) for s in SOURCES + headers] + [os.path.join(HERE, '..', 'include', 'qagnn_hip.h'),
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_tn.h')]
+
+
 def source_hash():
     h = hashlib.sha256(' '.join(FLAGS).encode())
-    paths = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'qagnn_hip.h'),
-                                                           os.path.join(HERE, '..', 'include', 'qagnn_hip_tn.h')]
-    for p in paths:
+    for p in hashed_files():
         with open(p, 'rb') as f:
             h.update(os.path.basename(p).encode() + b'\0' + f.read() + b'\0')
     return h.hexdigest()

@@ -7,9 +7,11 @@
 // MFMA 16x16x4 f32 operand layout (wave64), from the CDNA4 ISA:
 //   A: lane l holds A[i = l & 15][k = l >> 4]       B: lane l holds B[k = l >> 4][j = l & 15]
 //   D: lane l, reg r holds D[row = (l >> 4) * 4 + r][col = l & 15]
+//
+// The slab epilogue of k_gemm_nn is the one text of gemm_device.h that k_gemm_nn_split and k_gemm_nn2 expand too.
 #include <stdlib.h>
 
-#include "common.h"
+#include "gemm_device.h"
 
 namespace qagnn {
 
@@ -191,39 +193,17 @@ __global__ __launch_bounds__(WAVES * 64) QAGNN_NN_ATTR void k_gemm_nn(qagnn_gemm
       if (kt + 1 < nkt) ktile(ic<1>{}, kt + 1);
     }
 
-    // epilogue.  The MFMA layout gives a lane ONE column of 4 rows per accumulator; storing that directly is 104 dword
-    // stores per lane in 64-byte row fragments (store-issue bound).  Instead each wave transposes SLAB_ROWS rows at a
-    // time through its private LDS slab and writes whole rows with 16-byte lanes: 4x fewer store instructions, full
-    // 128-byte lines.
+    // epilogue: SLAB_ROWS rows at a time through the wave's private LDS slab, then whole-row 16-byte stores (gemm_device.h)
     float* const St = smem + w * SLAB_ROWS * PS;
-    constexpr int ROW_F4 = BN / 4, TILE_F4 = SLAB_ROWS * ROW_F4, ST_IT = (TILE_F4 + 63) / 64;
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
 #pragma unroll
       for (int h = 0; h < SUB; ++h) {
         __syncthreads();  // k-loop reads (first pass) / the previous pass's slab reads are done before the slab is overwritten
         const int lr0 = (lane >> 4) * 4 - h * SLAB_ROWS;  // this lane's first row inside the slab (in range for its half only)
-        if (lr0 >= 0 && lr0 < SLAB_ROWS) {
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) St[(lr0 + r) * PS + j * 16 + (lane & 15)] = acc[i][j][r];
-        }
+        if (lr0 >= 0 && lr0 < SLAB_ROWS) { QAGNN_NN_SLAB_FILL(acc[i], lr0) }
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < ST_IT; ++it) {
-          const int idx = lane + it * 64;
-          if (idx >= TILE_F4) break;
-          const int lr = idx / ROW_F4, c4 = idx % ROW_F4;
-          const int row = m0 + (w * RT + i) * 16 + h * SLAB_ROWS + lr, col = n0 + c4 * 4;
-          if (row >= a.M || col >= a.No) continue;
-          float4 v = ld4(St + lr * PS + c4 * 4);
-          if (a.bias) v = add4(v, ld4(a.bias + col));
-          if (a.rowtab) v = add4(v, ld4(a.rowtab + (int64_t)a.rowidx[row] * a.ldt + col));
-          float* dst = a.C + (int64_t)row * a.ldc + col;
-          if (a.accumulate) v = add4(v, ld4(dst));
-          st4(dst, v);
-        }
+        QAGNN_NN_SLAB_STORE(m0 + (w * RT + i) * 16 + h * SLAB_ROWS, a.M, a.No)
       }
     }
   }

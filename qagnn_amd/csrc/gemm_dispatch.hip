@@ -1,6 +1,6 @@
 // Host side of the dense products: what stands between the GEMM entry points of include/qagnn_hip.h and the kernels of gemm.hip (fp32
 // MFMA, weight gradients at run-time shapes, chunk sums), gemm_split.hip (3 x bf16 split, first generation; split weight gradients) and
-// gemm_nn2.hip (second-generation NN kernel, B images).  No kernel lives here.
+// gemm_nn2.hip (second-generation NN kernel, B images); the device code those three share is in gemm_device.h.  No kernel lives here.
 //
 // An entry point fills a product description (NnProduct / TnProduct, common.h) and calls gemm_nn() / gemm_tn(): validate, ask
 // nn_route() / tn_route() for the product's route, hand route and product to the one launcher of the kernel template it names.  The

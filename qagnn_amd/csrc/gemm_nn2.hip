@@ -44,33 +44,18 @@
 // has no known maximum takes the NP = 3 kernels.
 // Epilogues: PACKED without column statistics stores straight from the accumulators (the MFMAs are issued with their operands swapped,
 // so that a lane holds four consecutive columns of a row); the others go through 16-row LDS slabs as in k_gemm_nn_split (whole-row
-// 16-byte stores; bias / row table / accumulate / BatchNorm column statistics).
+// 16-byte stores; bias / row table / accumulate / BatchNorm column statistics) -- the same text, from gemm_device.h, where the buffer
+// load, OOB, split3 and pack_hi of this file are defined too.
 #include <stdlib.h>
 
 
-#include "common.h"
+#include "gemm_device.h"
 
 namespace qagnn {
-
 
 namespace nn2 {
 
 constexpr int BK = 32;
-constexpr uint32_t OOB = 0x80000000u;  // beyond any operand this kernel is launched on: the buffer load answers with zeros
-
-__device__ __forceinline__ u32x4s bload(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
-  return __builtin_bit_cast(u32x4s, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
-}
-
-// x = h1 + h2 + h3 exactly, each h a bf16 number carried in the high half of a dword (see gemm_split.hip)
-__device__ __forceinline__ void split3(uint32_t u, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
-  h1 = u & 0xFFFF0000u;
-  const float r1 = __builtin_bit_cast(float, u) - __builtin_bit_cast(float, h1);
-  h2 = __builtin_bit_cast(uint32_t, r1) & 0xFFFF0000u;
-  const float r2 = r1 - __builtin_bit_cast(float, h2);
-  h3 = __builtin_bit_cast(uint32_t, r2);
-}
-__device__ __forceinline__ uint32_t pack_hi(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 template <bool AFFINE, int NP = 2>
 __device__ __forceinline__ void split_frag2(const u32x4s (&r)[2], u32x4s (&f)[NP], const float* __restrict__ sc, const float* __restrict__ sh, float lo,
@@ -126,7 +111,7 @@ __device__ __forceinline__ void store_b4(unsigned char* __restrict__ dst, u32x4s
 #define QAGNN_NN2_SIX(C, AF, BF) C = mfma_pieces<NP>(AF, BF, C);
 
 // Per column tile 12 MFMAs (hipcc interleaves the two row tiles' accumulate chains by itself), then the split work of a B load round as
-// one clump (ORDER is a vestigial template argument, always 0: the pinned MFMA / 2 VALU interleave it selected measured no faster).
+// one clump (a pinned MFMA / 2 VALU interleave measured no faster and is gone).
 // PACKED: B arrives pre-split in the kernel's own LDS image order (k_pack_b below: [k-tile of the walk][column tile][piece][lane] x 16 B,
 // zero-filled past K and No), B1n = that buffer, ldn1 = column tiles per k-tile.  A k-tile of B is then NT * 3 contiguous KB that go
 // to LDS by DMA (global_load_lds, 1 KB per wave-instruction): no registers, no split arithmetic, no ds_write for B in the k-loop
@@ -283,26 +268,26 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if constexpr (!PACKED) {                                                                                         \
           const uint32_t bo_ = kb_ + kq * 4 < K1 ? bbase1 : OOB;                                                         \
           _Pragma("unroll") for (int q = 0; q < BR; ++q)                                                                 \
-              rb[q] = bload(rB1, q * 32 < nvalid ? bo_ : OOB, (uint32_t)kb_ * 4u + (uint32_t)q * bstep1);                \
+              rb[q] = bload<u32x4s>(rB1, q * 32 < nvalid ? bo_ : OOB, (uint32_t)kb_ * 4u + (uint32_t)q * bstep1);                \
         }                                                                                                                \
         const bool ain_ = kb_ + ac * 8 < K1;                                                                             \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                  \
           const uint32_t off_ = ain_ ? arow1[i] : OOB;                                                                   \
-          ra[i][0] = bload(rA1, off_, (uint32_t)kb_ * 4u);                                                               \
-          ra[i][1] = bload(rA1, off_, (uint32_t)kb_ * 4u + 16u);                                                         \
+          ra[i][0] = bload<u32x4s>(rA1, off_, (uint32_t)kb_ * 4u);                                                               \
+          ra[i][1] = bload<u32x4s>(rA1, off_, (uint32_t)kb_ * 4u + 16u);                                                         \
         }                                                                                                                \
       } else {                                                                                                           \
         const int kb_ = s2 + (u_ - n1) * 32;                                                                             \
         if constexpr (!PACKED) {                                                                                         \
           const uint32_t bo_ = kb_ + kq * 4 < K2 ? bbase2 : OOB;                                                         \
           _Pragma("unroll") for (int q = 0; q < BR; ++q)                                                                 \
-              rb[q] = bload(rB2, q * 32 < nvalid ? bo_ : OOB, (uint32_t)kb_ * 4u + (uint32_t)q * bstep2);                \
+              rb[q] = bload<u32x4s>(rB2, q * 32 < nvalid ? bo_ : OOB, (uint32_t)kb_ * 4u + (uint32_t)q * bstep2);                \
         }                                                                                                                \
         const bool ain_ = kb_ + ac * 8 < K2;                                                                             \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                  \
           const uint32_t off_ = ain_ ? arow2[i] : OOB;                                                                   \
-          ra[i][0] = bload(rA2, off_, (uint32_t)kb_ * 4u);                                                               \
-          ra[i][1] = bload(rA2, off_, (uint32_t)kb_ * 4u + 16u);                                                         \
+          ra[i][0] = bload<u32x4s>(rA2, off_, (uint32_t)kb_ * 4u);                                                               \
+          ra[i][1] = bload<u32x4s>(rA2, off_, (uint32_t)kb_ * 4u + 16u);                                                         \
         }                                                                                                                \
       }                                                                                                                  \
     }
@@ -568,7 +553,7 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
             const int col = en0 + j * 16 + c4;
-            t[j] = __builtin_bit_cast(f32x4s, bload(rC, rok && col < No ? crow[i] + (uint32_t)col * 4u : OOB, 0u));
+            t[j] = bload<f32x4s>(rC, rok && col < No ? crow[i] + (uint32_t)col * 4u : OOB);
           }
 #pragma unroll
           for (int j = 0; j < NT; ++j) acc[i][j] += t[j];
@@ -598,81 +583,26 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #undef QAGNN_NN2_SPLIT_A
 #undef QAGNN_NN2_MFMA_TILE
 
-    // ---- epilogue: transpose 16 rows at a time through the wave's LDS slab, then whole-row 16-byte stores
+    // ---- epilogue (gemm_device.h): transpose 16 rows at a time through the wave's LDS slab, then whole-row 16-byte stores
     float* const St = reinterpret_cast<float*>(smem) + w * SLAB_ROWS * PS;
     float (*const cstat)[2][BN] = reinterpret_cast<float (*)[2][BN]>(smem + SLAB_B);
-    constexpr int ROW_F4 = BN / 4, TILE_F4 = SLAB_ROWS * ROW_F4, ST_IT = (TILE_F4 + 63) / 64;
     constexpr int SC = (BN + 63) / 64;
-    float x0r[SC], s1[SC], s2v[SC];
+    float x0r[SC], cs1[SC], cs2[SC];
 #pragma unroll
-    for (int cc = 0; cc < SC; ++cc) x0r[cc] = s1[cc] = s2v[cc] = 0.f;
+    for (int cc = 0; cc < SC; ++cc) x0r[cc] = cs1[cc] = cs2[cc] = 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       __syncthreads();  // k-loop reads (first pass) / the previous pass's slab reads are done before the slab is overwritten
-      const int lr0 = (lane >> 4) * 4;
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) St[(lr0 + r) * PS + j * 16 + (lane & 15)] = acc[i][j][r];
+      QAGNN_NN_SLAB_FILL(acc[i], (lane >> 4) * 4)
       __syncthreads();
       if constexpr (STATS) {
-        // row 0 of the first slab of this wave's 128-row statistics tile (wave 0's, or wave 4's in a 256-row block) = the tile's first row
+        // the first slab of this wave's 128-row statistics tile: wave 0's, or wave 4's in a 256-row block
         const float* const S0 = reinterpret_cast<const float*>(smem) + (w & ~3) * SLAB_ROWS * PS;
-#pragma unroll
-        for (int cc = 0; cc < SC; ++cc) {
-          const int c = lane + cc * 64;
-          if (c < BN && n0 + c < No) {
-            const float bcv = a.bias ? a.bias[n0 + c] : 0.f;
-            if (i == 0) x0r[cc] = S0[c] + bcv;
-            const int rows = M - (m0 + (w * 2 + i) * 16);
-            float v[SLAB_ROWS];
-#pragma unroll
-            for (int r = 0; r < SLAB_ROWS; ++r) v[r] = St[r * PS + c];
-#pragma unroll
-            for (int r = 0; r < SLAB_ROWS; ++r) {
-              const float dlt = r < rows ? (v[r] + bcv) - x0r[cc] : 0.f;
-              s1[cc] += dlt;
-              s2v[cc] = fmaf(dlt, dlt, s2v[cc]);
-            }
-          }
-        }
+        QAGNN_NN_SLAB_STATS(S0, i == 0, M - (m0 + (w * 2 + i) * 16), No)
       }
-#pragma unroll
-      for (int itx = 0; itx < ST_IT; ++itx) {
-        const int idx = lane + itx * 64;
-        if (idx >= TILE_F4) break;
-        const int slr = idx / ROW_F4, c4 = idx % ROW_F4;
-        const int row = m0 + (w * 2 + i) * 16 + slr, col = n0 + c4 * 4;
-        if (row >= M || col >= No) continue;
-        float4 v = ld4(St + slr * PS + c4 * 4);
-        if (a.bias) v = add4(v, ld4(a.bias + col));
-        if (a.rowtab) v = add4(v, ld4(a.rowtab + (int64_t)a.rowidx[row] * a.ldt + col));
-        float* dst = a.C + (int64_t)row * a.ldc + col;
-        if (a.accumulate) v = add4(v, ld4(dst));
-        st4(dst, v);
-      }
+      QAGNN_NN_SLAB_STORE(m0 + (w * 2 + i) * 16, M, No)
     }
-    if constexpr (STATS) {
-#pragma unroll
-      for (int cc = 0; cc < SC; ++cc) {
-        const int c = lane + cc * 64;
-        if (c < BN) { cstat[w][0][c] = s1[cc]; cstat[w][1][c] = s2v[cc]; }
-      }
-      __syncthreads();
-      // one partial per 128 rows (the contract of colstat_part): thread (hw, lane) of half `hf` = column hw * 64 + lane of that half,
-      // its own x0r[hw] is that column's shift
-      const int hw = w & 3, hf = w >> 2, col = hw * 64 + lane;
-      if (col < BN && n0 + col < No && m0 + hf * 128 < M) {
-        float x0c = x0r[0];
-#pragma unroll
-        for (int cc = 1; cc < SC; ++cc) x0c = (hw == cc) ? x0r[cc] : x0c;
-        float* const pt = a.colstat_part + ((int64_t)(tile / ncb) * (WV / 4) + hf) * 3 * No + n0 + col;
-        const int w0 = hf * 4;
-        pt[0] = x0c;
-        pt[No] = (cstat[w0][0][col] + cstat[w0 + 1][0][col]) + (cstat[w0 + 2][0][col] + cstat[w0 + 3][0][col]);
-        pt[2 * No] = (cstat[w0][1][col] + cstat[w0 + 1][1][col]) + (cstat[w0 + 2][1][col] + cstat[w0 + 3][1][col]);
-      }
-    }
+    if constexpr (STATS) QAGNN_NN_STATS_PUT(true, WV / 4, M, No)
   }
 }
 #undef QAGNN_NN2_SIX

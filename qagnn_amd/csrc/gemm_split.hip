@@ -17,32 +17,19 @@
 // LDS: three bf16 images of the A tile [128][32] and of the B tile [NT*16][32], 16-byte chunks XOR-swizzled by (row >> 2) & 3 so
 // that the 16 lanes of a fragment read hit 16 different bank groups; single-buffered (the next tile's global loads are in flight,
 // in registers, under the MFMAs), two blocks per CU.
+//
+// What these kernels share with each other and with gemm.hip / gemm_nn2.hip is defined once, in gemm_device.h: the buffer load, OOB,
+// split3 / pack_hi, the slab epilogue of the NN kernels with its column statistics, prologue and final store of the two weight-gradient
+// kernels below.
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_device.h"
 
 namespace qagnn {
 
-
-// 16-byte load through a buffer descriptor: per-lane byte offset + wave-uniform byte offset; out of range reads return zeros
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff = 0) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
-}
-
 constexpr int SBK = 32, SBM = 128, SWAVES = 4, SRT = 2, STHR = SWAVES * 64;
-
-__device__ __forceinline__ void split3(float x, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, x);
-  h1 = u & 0xFFFF0000u;
-  const float r1 = x - __builtin_bit_cast(float, h1);  // exact
-  h2 = __builtin_bit_cast(uint32_t, r1) & 0xFFFF0000u;
-  const float r2 = r1 - __builtin_bit_cast(float, h2);  // exact, <= 8 significant bits
-  h3 = __builtin_bit_cast(uint32_t, r2);  // <= 8 significant bits: the low half is already zero
-}
-// two fp32 bit patterns whose low halves are zero -> one dword of two bf16 (element 0 = lo, in the low half)
-__device__ __forceinline__ uint32_t pack_hi(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 // float4 (4 consecutive k of one row) -> the three bf16 images, 8 bytes each, at element offset `off` (already swizzled)
 __device__ __forceinline__ void store_split(uint16_t* __restrict__ img, int img_elems, int off, float4 v) {
@@ -109,7 +96,6 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       arow[p] = row < a.M ? (a.a_rowidx ? a.a_rowidx[row] : (int64_t)row) : -1;
     }
     float4 ra[A_IT], rb[B_IT];
-    constexpr uint32_t OOB = 0x80000000u;
     auto gload_buf = [&](int kt) {
       const bool first = kt < nk1;
       const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(first ? a.A1 : a.A2), 0, a.M * (first ? a.lda1 : a.lda2) * 4, 0x00020000);
@@ -123,12 +109,12 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #pragma unroll
       for (int p = 0; p < A_IT; ++p) {
         const int row = m0 + lr + p * 32;
-        ra[p] = bload4(rA, (kin && row < a.M) ? (uint32_t)row * lda4 + (uint32_t)kq * 16u : OOB, soff);
+        ra[p] = bload<float4>(rA, (kin && row < a.M) ? (uint32_t)row * lda4 + (uint32_t)kq * 16u : OOB, soff);
       }
 #pragma unroll
       for (int q = 0; q < B_IT; ++q) {
         const int col = n0 + lr + q * 32;
-        rb[q] = bload4(rB, (kin && col < a.No) ? (uint32_t)col * ldn4 + (uint32_t)kq * 16u : OOB, soff);
+        rb[q] = bload<float4>(rB, (kin && col < a.No) ? (uint32_t)col * ldn4 + (uint32_t)kq * 16u : OOB, soff);
       }
     };
     // FLAT: unconditional loads from clamped addresses (branches around loads make hipcc fall back to vmcnt(0)); what lies past the
@@ -218,77 +204,24 @@ __global__ __launch_bounds__(STHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       __builtin_amdgcn_s_setprio(0);
     }
 
-    // epilogue: transpose 16 rows at a time through the wave's LDS slab, then whole-row 16-byte stores (as k_gemm_nn)
+    // epilogue (gemm_device.h): transpose 16 rows at a time through the wave's LDS slab, then whole-row 16-byte stores (as k_gemm_nn)
     float* const St = reinterpret_cast<float*>(smem_raw) + w * SLAB_ROWS * PS;
-    constexpr int ROW_F4 = BN / 4, TILE_F4 = SLAB_ROWS * ROW_F4, ST_IT = (TILE_F4 + 63) / 64;
     constexpr int SC = (BN + 63) / 64;  // STATS: columns lane, lane + 64, ... of the tile per lane
-    float x0r[SC], s1[SC], s2[SC];
+    float x0r[SC], cs1[SC], cs2[SC];
 #pragma unroll
-    for (int cc = 0; cc < SC; ++cc) x0r[cc] = s1[cc] = s2[cc] = 0.f;
+    for (int cc = 0; cc < SC; ++cc) x0r[cc] = cs1[cc] = cs2[cc] = 0.f;
 #pragma unroll
     for (int i = 0; i < SRT; ++i) {
       __syncthreads();  // k-loop reads (first pass) / the previous pass's slab reads are done before the slab is overwritten
-      const int lr0 = (lane >> 4) * 4;
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) St[(lr0 + r) * PS + j * 16 + (lane & 15)] = acc[i][j][r];
+      QAGNN_NN_SLAB_FILL(acc[i], (lane >> 4) * 4)
       __syncthreads();
       if constexpr (STATS) {
-        // every wave's slab is complete: row 0 of wave 0's first slab is the tile's first row (the shift of this tile's sums)
-        const float* const S0 = reinterpret_cast<const float*>(smem_raw);
-#pragma unroll
-        for (int cc = 0; cc < SC; ++cc) {
-          const int c = lane + cc * 64;
-          if (c < BN && n0 + c < a.No) {
-            const float bc = a.bias ? a.bias[n0 + c] : 0.f;
-            if (i == 0) x0r[cc] = S0[c] + bc;
-            const int rows = a.M - (m0 + (w * SRT + i) * 16);  // rows of this slab inside the matrix (<= 0 past M)
-            float v[SLAB_ROWS];
-#pragma unroll
-            for (int r = 0; r < SLAB_ROWS; ++r) v[r] = St[r * PS + c];  // 16 LDS reads in flight, then the arithmetic
-#pragma unroll
-            for (int r = 0; r < SLAB_ROWS; ++r) {
-              const float dlt = r < rows ? (v[r] + bc) - x0r[cc] : 0.f;  // the value the store loop below writes, minus the shift
-              s1[cc] += dlt;
-              s2[cc] = fmaf(dlt, dlt, s2[cc]);
-            }
-          }
-        }
+        const float* const S0 = reinterpret_cast<const float*>(smem_raw);  // wave 0's first slab
+        QAGNN_NN_SLAB_STATS(S0, i == 0, a.M - (m0 + (w * SRT + i) * 16), a.No)
       }
-#pragma unroll
-      for (int it = 0; it < ST_IT; ++it) {
-        const int idx = lane + it * 64;
-        if (idx >= TILE_F4) break;
-        const int slr = idx / ROW_F4, c4 = idx % ROW_F4;
-        const int row = m0 + (w * SRT + i) * 16 + slr, col = n0 + c4 * 4;
-        if (row >= a.M || col >= a.No) continue;
-        float4 v = ld4(St + slr * PS + c4 * 4);
-        if (a.bias) v = add4(v, ld4(a.bias + col));
-        if (a.rowtab) v = add4(v, ld4(a.rowtab + (int64_t)a.rowidx[row] * a.ldt + col));
-        float* dst = a.C + (int64_t)row * a.ldc + col;
-        if (a.accumulate) v = add4(v, ld4(dst));
-        st4(dst, v);
-      }
+      QAGNN_NN_SLAB_STORE(m0 + (w * SRT + i) * 16, a.M, a.No)
     }
-    if constexpr (STATS) {
-#pragma unroll
-      for (int cc = 0; cc < SC; ++cc) {
-        const int c = lane + cc * 64;
-        if (c < BN) { cstat[w][0][c] = s1[cc]; cstat[w][1][c] = s2[cc]; }
-      }
-      __syncthreads();
-      if (tid < BN && n0 + tid < a.No) {  // thread (w, lane) = column w * 64 + lane: its own x0r[w] is that column's shift
-        float x0c = x0r[0];
-#pragma unroll
-        for (int cc = 1; cc < SC; ++cc) x0c = (w == cc) ? x0r[cc] : x0c;
-        float* const pt = a.colstat_part + (int64_t)(tile / ncb) * 3 * a.No + n0 + tid;
-        pt[0] = x0c;
-        pt[a.No] = (cstat[0][0][tid] + cstat[1][0][tid]) + (cstat[2][0][tid] + cstat[3][0][tid]);
-        pt[2 * a.No] = (cstat[0][1][tid] + cstat[1][1][tid]) + (cstat[2][1][tid] + cstat[3][1][tid]);
-      }
-      // (cstat is rewritten only after the next tile's k-loop and slab barriers)
-    }
+    if constexpr (STATS) QAGNN_NN_STATS_PUT(false, 1, a.M, a.No)
   }
 }
 
@@ -362,9 +295,10 @@ __device__ __forceinline__ void store_col8(uint16_t* __restrict__ dst, int img_e
   *reinterpret_cast<uint4*>(dst + 2 * img_elems) = make_uint4(pack_hi(h3[0], h3[1]), pack_hi(h3[2], h3[3]), pack_hi(h3[4], h3[5]), pack_hi(h3[6], h3[7]));
 }
 
-// a task's 8 x 4 numbers -> LDS (4 columns); AFF: relu(x * sc + sh) per column first
+// a task's 8 x 4 numbers -> LDS (4 columns), s = the operand's scale (NP <= 2); AFF: relu(x * sc + sh) per column first
 template <bool AFF, int NP>
-__device__ __forceinline__ void store_task(uint16_t* __restrict__ img, int img_elems, int off, const float4 (&r)[8], float4 sc, float4 sh, float s) {
+__device__ __forceinline__ void store_task(uint16_t* __restrict__ img, int img_elems, int off, const float4 (&r)[8], float s,
+                                           float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), float4 sh = make_float4(0.f, 0.f, 0.f, 0.f)) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float x[8];
@@ -372,8 +306,8 @@ __device__ __forceinline__ void store_task(uint16_t* __restrict__ img, int img_e
     for (int i = 0; i < 8; ++i) {
       float v = j == 0 ? r[i].x : j == 1 ? r[i].y : j == 2 ? r[i].z : r[i].w;
       if (AFF) {
-        const float s = j == 0 ? sc.x : j == 1 ? sc.y : j == 2 ? sc.z : sc.w, h = j == 0 ? sh.x : j == 1 ? sh.y : j == 2 ? sh.z : sh.w;
-        v = floor_nan(fmaf(v, s, h), 0.f);
+        const float s_ = j == 0 ? sc.x : j == 1 ? sc.y : j == 2 ? sc.z : sc.w, h = j == 0 ? sh.x : j == 1 ? sh.y : j == 2 ? sh.z : sh.w;
+        v = floor_nan(fmaf(v, s_, h), 0.f);
       }
       x[i] = v;
     }
@@ -383,8 +317,7 @@ __device__ __forceinline__ void store_task(uint16_t* __restrict__ img, int img_e
 
 // GATHER: row r of A is A[a_rowidx[r]] (negative = zero row): the frozen entity table under cpt_transform's weight gradient.  The
 // table can exceed 2 GB, so these rows come through 64-bit flat loads; their indices are fetched one tile ahead, behind the stores.
-// NP == 2: the three-MFMA form; amax[0..2] = the words holding max |A|, max |A2|, max |B| (bit patterns)
-struct TnAmax { const uint32_t* a; const uint32_t* a2; const uint32_t* b; };
+// NP == 2: the three-MFMA form; amax = the words holding max |A|, max |A2|, max |B| (TnAmax: gemm_device.h)
 template <int KT, int NT, bool AFFINE, bool GATHER, int NP = 3>
 __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm_tn_split(
     const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ P, int R, int Ka, int No,
@@ -404,35 +337,8 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   uint16_t* const Maj = A_MAJOR ? As : Bs;
   uint16_t* const Min = A_MAJOR ? Bs : As;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Two A operands (A2 != nullptr): the product [A | A2]^T B, rows [0, Ka) of the output from A, rows [Ka, Ka + Ka2) from A2 -- the
-  // row tiles of A2 follow those of A in blockIdx.y, and such a block simply works on the other operand (one launch and one chunk sum
-  // for the two weight gradients that share dK|dM|dQ: X^T dKMQ and S^T dKMQ)
-  const int ka_total = Ka + (A2 ? Ka2 : 0);
-  // XCD-aware block order (chunk_rows < 0: off; see k_gemm_tn_ws): the blocks of one chunk on one XCD
-  int bx = blockIdx.x, by = blockIdx.y, chunk = blockIdx.z, row_shift = 0;
-  if (chunk_rows < 0) {
-    chunk_rows = -chunk_rows;
-  } else {
-    const int lin = bx + (int)gridDim.x * (by + (int)gridDim.y * chunk);
-    const int v = xcd_remap(lin, (int)(gridDim.x * gridDim.y * gridDim.z));
-    bx = v % (int)gridDim.x;
-    by = (v / (int)gridDim.x) % (int)gridDim.y;
-    chunk = v / (int)(gridDim.x * gridDim.y);
-  }
-  bool second = false;
-  if (A2 != nullptr) {
-    const int n1 = (Ka + AC - 1) / AC;
-    if (by >= n1) { by -= n1; row_shift = Ka; A = A2; lda = lda2; Ka = Ka2; second = true; }
-  }
-  uint32_t fa = 127u, fb = 127u;
-  float sa = 1.f, sb = 1.f;
-  if constexpr (NP <= 2) {
-    fa = __builtin_amdgcn_readfirstlane(h2_scale_field(second ? amax.a2[0] : amax.a[0]));
-    fb = __builtin_amdgcn_readfirstlane(h2_scale_field(amax.b[0]));
-    sa = h2_field_to_scale(fa);
-    sb = h2_field_to_scale(fb);
-  }
-  const int n0 = bx * BC, m0 = by * AC;
+  // the block's tile (m0, n0) and chunk in the XCD-aware order, its A operand of the two, the scales (gemm_device.h)
+  QAGNN_TN_BLOCK(false, TnLive{})
   const int r_beg = chunk * chunk_rows, r_end = min(R, r_beg + chunk_rows);
   const int ntile = (r_end - r_beg + TKR - 1) / TKR;  // chunk_rows is a multiple of TKR: only the last chunk has a ragged tile, past R
 
@@ -442,7 +348,6 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   const __amdgpu_buffer_rsrc_t rsMaj = A_MAJOR ? rsA : rsB, rsMin = A_MAJOR ? rsB : rsA;
   const int maj0 = A_MAJOR ? m0 : n0, min0 = A_MAJOR ? n0 : m0, majDim = A_MAJOR ? Ka : No, minDim = A_MAJOR ? No : Ka;
   const uint32_t ldMaj4 = (uint32_t)(A_MAJOR ? lda : ldb) * 4u, ldMin4 = (uint32_t)(A_MAJOR ? ldb : lda) * 4u;
-  constexpr uint32_t OOB = 0x80000000u;  // beyond any operand this kernel is launched on: the load returns zeros
 
   const int g = lane & 3;                                   // row group (8 rows) of this thread's tasks
   const int c4j = w * 16 + (lane >> 2);                     // float4 column of the major task
@@ -487,7 +392,7 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) rj[i] = bload4(rsMaj, maj_voff + (uint32_t)i * ldMaj4);
+      for (int i = 0; i < 8; ++i) rj[i] = bload<float4>(rsMaj, maj_voff + (uint32_t)i * ldMaj4);
       maj_voff += maj_in ? (uint32_t)TKR * ldMaj4 : 0u;
     }
     const int mk = (w - t) & 3;  // this tile's minor task-wave of this wave (wave-uniform)
@@ -496,11 +401,11 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       const bool in = c4 * 4 < MIN_C && min0 + c4 * 4 < minDim;
       const uint32_t voff = in ? ((uint32_t)(r_beg + t * TKR + g * 8) * ldMin4 + (uint32_t)(min0 + c4 * 4) * 4u) : OOB;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) rn[i] = bload4(rsMin, voff + (uint32_t)i * ldMin4);
+      for (int i = 0; i < 8; ++i) rn[i] = bload<float4>(rsMin, voff + (uint32_t)i * ldMin4);
     }
   };
   auto lstore = [&](int t) {
-    if (maj_act) store_task<AFFINE && A_MAJOR, NP>(Maj, MAJ_EL, maj_off, rj, scj, shj, A_MAJOR ? sa : sb);
+    if (maj_act) store_task<AFFINE && A_MAJOR, NP>(Maj, MAJ_EL, maj_off, rj, A_MAJOR ? sa : sb, scj, shj);
     const int mk = (w - t) & 3;
     if (mk < MIN_TW) {
       const int c4 = mk * 16 + (lane >> 2);
@@ -512,7 +417,7 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
           sc = ld4(a_scale + cc);
           sh = ld4(a_shift + cc);
         }
-        store_task<AFFINE && !A_MAJOR, NP>(Min, MIN_EL, off, rn, sc, sh, A_MAJOR ? sb : sa);
+        store_task<AFFINE && !A_MAJOR, NP>(Min, MIN_EL, off, rn, A_MAJOR ? sb : sa, sc, sh);
       }
     }
   };
@@ -567,14 +472,8 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #undef QAGNN_SIX
 
   float* const Pc = P + (int64_t)chunk * ka_total * No;
-  const float inv = NP <= 2 ? h2_inv_scale(fa, fb) : 1.f;  // (NP == 2: the operand scales come out again, exactly)
-  auto put = [&](int strip, int j, const f32x4s& c) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + strip * 16 + (lane >> 4) * 4 + r, col = n0 + j * 16 + (lane & 15);
-      if (row < Ka && col < No) Pc[(int64_t)(row + row_shift) * No + col] = NP <= 2 ? c[r] * inv : c[r];
-    }
-  };
+  const float inv = NP <= 2 ? h2_inv_scale(fa, fb) : 1.f;
+  auto put = [&](int strip, int j, const f32x4s& c) { QAGNN_TN_PUT(false, strip, j, c) };
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -603,35 +502,15 @@ __global__ __launch_bounds__(TTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 // ------------------------------------------------------------------------------------------------------------
 constexpr int WTHR = 512;
 
-// store_task with a per-lane floor (AFF: relu for the lanes of A, -inf = pass-through for the lanes of B)
-template <bool AFF, int NP>
-__device__ __forceinline__ void store_task_lo(uint16_t* __restrict__ img, int img_elems, int off, const float4 (&r)[8], float4 sc, float4 sh, float lo,
-                                              float s) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = j == 0 ? r[i].x : j == 1 ? r[i].y : j == 2 ? r[i].z : r[i].w;
-      if (AFF) {
-        const float s_ = j == 0 ? sc.x : j == 1 ? sc.y : j == 2 ? sc.z : sc.w, h = j == 0 ? sh.x : j == 1 ? sh.y : j == 2 ? sh.z : sh.w;
-        v = floor_nan(fmaf(v, s_, h), lo);
-      }
-      x[i] = v;
-    }
-    store_col8<NP>(img + off + j * TCP, img_elems, x, s);
-  }
-}
-
+// The kernel takes two-operand products only, and those carry no scale / shift prologue (tn_route, tn_validate: gemm_dispatch.hip).
 // LIVE (common.h: tn_work): the block's unit of work -- column block, and a LIST of live k-tiles (K, Q) or a RANGE of k-tiles (M) --
 // comes from the graph's live-tile list instead of (blockIdx, chunk_rows).  The tile numbers of the walk are staged in LDS behind the
 // two images, every one clamped to [0, T]; T itself stands for "no tile" (rows past R: the loads answer zeros).  The walk is by
 // POSITION: the producers' rotation and the two images alternate with the position in the list, whatever the tile numbers are.
-template <int KT, int NT, bool AFFINE, int NP = 3, bool LIVE = false>
+template <int KT, int NT, int NP = 3, bool LIVE = false>
 __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm_tn_ws(
-    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ P, int R, int Ka, int No,
-    const float* __restrict__ a_scale, const float* __restrict__ a_shift, int chunk_rows, const float* __restrict__ A2, int lda2, int Ka2,
-    TnAmax amax, TnLive lv) {
+    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ P, int R, int Ka, int No, int chunk_rows,
+    const float* __restrict__ A2, int lda2, int Ka2, TnAmax amax, TnLive lv) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_tw[];
   constexpr int AC = KT * 16, BC = NT * 16, A_EL = AC * TCP, B_EL = BC * TCP;
   constexpr int IMG_EL = NP * (A_EL + B_EL), IMG_B = IMG_EL * 2;  // one k-tile's image: [A: piece][column][32 rows + pad] | [B: ...]
@@ -644,43 +523,8 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   static_assert(MT >= 1 && NTW >= 4 && NTW <= 8, "shapes: (13, 7) and (7, 13)");
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  const int ka_total = Ka + (A2 ? Ka2 : 0);
-  // XCD-aware block order (chunk_rows < 0: off): the blocks of one chunk read the same rows of A and B, so they belong on ONE XCD,
-  // next to each other in time -- in launch order they are dealt out over all eight L2s and every operand row crosses the fabric once
-  // per block that uses it (744 MB instead of 242 MB for the two-operand product: the kernel ran at the speed of those re-reads)
-  int bx = blockIdx.x, by = blockIdx.y, chunk = blockIdx.z, row_shift = 0;
-  TnSlot slot = {};
-  if constexpr (LIVE) {
-    // the row blocks of a unit are neighbours in the XCD-contiguous order, then the units in tn_slot's order (K_j, Q_j, their M ranges)
-    const int lin = bx + (int)gridDim.x * (by + (int)gridDim.y * chunk);
-    const int v = xcd_remap(lin, (int)(gridDim.x * gridDim.y * gridDim.z));
-    by = v % (int)gridDim.y;
-    const int L = __builtin_amdgcn_readfirstlane(lv.n_live[0]);
-    slot = tn_slot(tn_work(lv.S, lv.T, L, lv.chunk_tiles), lv.S, lv.T, min(v / (int)gridDim.y, lv.S - 1));
-    bx = slot.cb;
-  } else if (chunk_rows < 0) {
-    chunk_rows = -chunk_rows;
-  } else {
-    const int lin = bx + (int)gridDim.x * (by + (int)gridDim.y * chunk);
-    const int v = xcd_remap(lin, (int)(gridDim.x * gridDim.y * gridDim.z));
-    bx = v % (int)gridDim.x;
-    by = (v / (int)gridDim.x) % (int)gridDim.y;
-    chunk = v / (int)(gridDim.x * gridDim.y);
-  }
-  bool second = false;
-  if (A2 != nullptr) {
-    const int n1 = (Ka + AC - 1) / AC;
-    if (by >= n1) { by -= n1; row_shift = Ka; A = A2; lda = lda2; Ka = Ka2; second = true; }
-  }
-  uint32_t fa = 127u, fb = 127u;
-  float sa = 1.f, sb = 1.f;
-  if constexpr (NP <= 2) {
-    fa = __builtin_amdgcn_readfirstlane(h2_scale_field(second ? amax.a2[0] : amax.a[0]));
-    fb = __builtin_amdgcn_readfirstlane(h2_scale_field(amax.b[0]));
-    sa = h2_field_to_scale(fa);
-    sb = h2_field_to_scale(fb);
-  }
-  const int n0 = bx * BC, m0 = by * AC;
+  // the block's tile (m0, n0) and chunk (LIVE: its unit of work) in the XCD-aware order, its A operand of the two, the scales (gemm_device.h)
+  QAGNN_TN_BLOCK(LIVE, lv)
   const int r_beg = LIVE ? 0 : chunk * chunk_rows, r_end = min(R, r_beg + chunk_rows);
   // chunk_rows is a multiple of TKR: only the last chunk has a ragged tile, past R.  LIVE: the slot's tiles, at most what the list holds
   const int ntile = LIVE ? min(max(slot.cnt, 0), TN_LIST_CAP) : (r_end - r_beg + TKR - 1) / TKR;
@@ -734,15 +578,13 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
       const int g = lane & 3;
       const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, R * lda * 4, 0x00020000);
       const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B), 0, R * ldb * 4, 0x00020000);
-      constexpr uint32_t OOB = 0x80000000u;  // (+ any offset of this kernel stays out of range: the load answers with zeros)
       const uint32_t ldA4 = (uint32_t)lda * 4u, ldB4 = (uint32_t)ldb * 4u;
       constexpr int TW[2] = {IDX, 4};
       constexpr bool HAS_A[2] = {TW[0] * 16 < AC / 4, TW[1] * 16 < AC / 4};
       constexpr bool HAS_B[2] = {TW[0] * 16 + 15 >= AC / 4, TW[1] * 16 + 15 >= AC / 4};
       uint32_t voA[2], voB[2];
       int off[2], iel[2];
-      float4 sc[2], sh[2];
-      float lo[2], ssc[2];
+      float ssc[2];
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int c4u = TW[k] * 16 + (lane >> 2);
@@ -754,15 +596,6 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         iel[k] = isA ? A_EL : B_EL;
         off[k] = act ? (isA ? 0 : NP * A_EL) + c4 * 4 * TCP + ((g ^ ((c4 ^ (c4 >> 1)) & 1)) << 3) : -1;
         ssc[k] = isA ? sa : sb;
-        sc[k] = make_float4(1.f, 1.f, 1.f, 1.f);
-        sh[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        lo[k] = -INFINITY;
-        if (AFFINE && isA && act) {
-          const int cc = min(m0 + c4 * 4, Ka - 4);
-          sc[k] = ld4(a_scale + cc);
-          sh[k] = ld4(a_shift + cc);
-          lo[k] = 0.f;
-        }
       }
       // two register sets per task slot: the loads of tile t + 2 are issued BEFORE the split work of tile t + 1 and have a whole
       // k-tile to land (even tiles in set a, odd tiles in set b)
@@ -774,14 +607,13 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
         const uint32_t a_ = voA[K] + t_ * (TKR * ldA4), b_ = voB[K] + t_ * (TKR * ldB4);                    \
         if constexpr (HAS_A[K] && HAS_B[K]) {                                                              \
           _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                  \
-            const u32x4s x_ = __builtin_bit_cast(u32x4s, bload4(rsA, a_ + (uint32_t)i * ldA4)) |           \
-                              __builtin_bit_cast(u32x4s, bload4(rsB, b_ + (uint32_t)i * ldB4));            \
+            const u32x4s x_ = bload<u32x4s>(rsA, a_ + (uint32_t)i * ldA4) | bload<u32x4s>(rsB, b_ + (uint32_t)i * ldB4); \
             RR[i] = __builtin_bit_cast(float4, x_);                                                        \
           }                                                                                                \
         } else if constexpr (HAS_A[K]) {                                                                   \
-          _Pragma("unroll") for (int i = 0; i < 8; ++i) RR[i] = bload4(rsA, a_ + (uint32_t)i * ldA4);      \
+          _Pragma("unroll") for (int i = 0; i < 8; ++i) RR[i] = bload<float4>(rsA, a_ + (uint32_t)i * ldA4); \
         } else {                                                                                           \
-          _Pragma("unroll") for (int i = 0; i < 8; ++i) RR[i] = bload4(rsB, b_ + (uint32_t)i * ldB4);      \
+          _Pragma("unroll") for (int i = 0; i < 8; ++i) RR[i] = bload<float4>(rsB, b_ + (uint32_t)i * ldB4); \
         }                                                                                                  \
       }
       // TP: the tile's position modulo 4 (t itself is a multiple of 4)
@@ -793,9 +625,9 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 #define QAGNN_TNW_STORE(T, TP, R1, R2)                                                                     \
       {                                                                                                    \
         uint16_t* const img_ = reinterpret_cast<uint16_t*>(smem_tw) + ((TP)&1) * IMG_EL;                   \
-        if (off[0] >= 0) store_task_lo<AFFINE, NP>(img_, iel[0], off[0], R1, sc[0], sh[0], lo[0], ssc[0]); \
+        if (off[0] >= 0) store_task<false, NP>(img_, iel[0], off[0], R1, ssc[0]);                          \
         if constexpr (NTW > 4 && ((IDX - (TP)) & 3) == 0) {                                                \
-          if (off[1] >= 0) store_task_lo<AFFINE, NP>(img_, iel[1], off[1], R2, sc[1], sh[1], lo[1], ssc[1]); \
+          if (off[1] >= 0) store_task<false, NP>(img_, iel[1], off[1], R2, ssc[1]);                        \
         }                                                                                                  \
       }
       QAGNN_TNW_LOAD(0, 0, r1a, r2a)
@@ -933,14 +765,7 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
   // LIVE: the partial of this slot is one [ka_total][BC] tile of the workspace (S of them: the K slots, then Q's, then M's)
   float* const Pc = LIVE ? P + (int64_t)min(max(slot.pslot, 0), lv.S - 1) * ka_total * BC : P + (int64_t)chunk * ka_total * No;
   const float inv = NP <= 2 ? h2_inv_scale(fa, fb) : 1.f;
-  auto put = [&](int maj_strip, int min_tile, const f32x4s& c) {
-    const int rstrip = MAJ_A ? maj_strip : min_tile, ctile = MAJ_A ? min_tile : maj_strip;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + rstrip * 16 + (lane >> 4) * 4 + r, lc = ctile * 16 + (lane & 15), col = n0 + lc;
-      if (row < Ka && col < No) Pc[LIVE ? (int64_t)(row + row_shift) * BC + lc : (int64_t)(row + row_shift) * No + col] = NP <= 2 ? c[r] * inv : c[r];
-    }
-  };
+  auto put = [&](int maj_strip, int min_tile, const f32x4s& c) { QAGNN_TN_PUT(LIVE, MAJ_A ? maj_strip : min_tile, MAJ_A ? min_tile : maj_strip, c) };
 #pragma unroll
   for (int s_ = 0; s_ < MT; ++s_)
 #pragma unroll
@@ -954,7 +779,7 @@ __global__ __launch_bounds__(WTHR) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
 
 // ---- launchers (the route: gemm_dispatch.hip).  chunk_rows > 0: the blocks of one split-K chunk on one XCD (-2..5 % per kernel:
 // profiles/r4_run17_tn_ws.txt) -------------------------------------------------------------------------------------------------------
-#define QAGNN_TN_ARGS p.A1, p.lda1, p.B, p.ldb, p.ws, p.R, p.Ka1, p.No, p.a_scale, p.a_shift, r.chunk_rows
+#define QAGNN_TN_ARGS p.A1, p.lda1, p.B, p.ldb, p.ws, p.R, p.Ka1, p.No
 static TnLive tn_live_args(const TnRoute& r, const TnProduct& p) {
   if (!r.live) return TnLive{nullptr, nullptr, 0, 0, 0};
   const LiveTiles lt = live_tiles_of(p.g);
@@ -963,12 +788,12 @@ static TnLive tn_live_args(const TnRoute& r, const TnProduct& p) {
 static TnAmax tn_amax(const TnRoute& r, const TnProduct& p) {
   return r.np == 3 ? TnAmax{nullptr, nullptr, nullptr} : TnAmax{p.amax[0], p.two ? p.amax[1] : nullptr, p.amax[2]};
 }
-template <int KT, int NT, bool AFFINE, int NP = 3, bool LIVE = false>
+template <int KT, int NT, int NP = 3, bool LIVE = false>
 static int launch_tn_ws_i(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
   static_assert(!LIVE || NT * 16 == TN_LIVE_BC, "the live-tile form is built for 208-column blocks");
   constexpr int lds = 2 * NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t) + 64 + (LIVE ? (TN_LIST_CAP + 8) * (int)sizeof(int) : 0);
-  if (int rc = raise_lds_limit<k_gemm_tn_ws<KT, NT, AFFINE, NP, LIVE>>(lds, "k_gemm_tn_ws")) return rc;
-  k_gemm_tn_ws<KT, NT, AFFINE, NP, LIVE><<<r.grid, WTHR, lds, stream>>>(QAGNN_TN_ARGS, p.A2, p.lda2, p.Ka2, tn_amax(r, p), tn_live_args(r, p));
+  if (int rc = raise_lds_limit<k_gemm_tn_ws<KT, NT, NP, LIVE>>(lds, "k_gemm_tn_ws")) return rc;
+  k_gemm_tn_ws<KT, NT, NP, LIVE><<<r.grid, WTHR, lds, stream>>>(QAGNN_TN_ARGS, r.chunk_rows, p.A2, p.lda2, p.Ka2, tn_amax(r, p), tn_live_args(r, p));
   QAGNN_LAUNCH_CHECK("k_gemm_tn_ws");
   return QAGNN_OK;
 }
@@ -976,7 +801,7 @@ template <int KT, int NT, bool AFFINE, bool GATHER = false, int NP = 3>
 static int launch_tn_split_i(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
   constexpr int lds = NP * (KT * 16 + NT * 16) * TCP * (int)sizeof(uint16_t);
   if (int rc = raise_lds_limit<k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP>>(lds, "k_gemm_tn_split")) return rc;
-  k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP><<<r.grid, TTHR, lds, stream>>>(QAGNN_TN_ARGS, p.a_rowidx, p.A2, p.lda2, p.Ka2, tn_amax(r, p));
+  k_gemm_tn_split<KT, NT, AFFINE, GATHER, NP><<<r.grid, TTHR, lds, stream>>>(QAGNN_TN_ARGS, p.a_scale, p.a_shift, r.chunk_rows, p.a_rowidx, p.A2, p.lda2, p.Ka2, tn_amax(r, p));
   QAGNN_LAUNCH_CHECK("k_gemm_tn_split");
   return QAGNN_OK;
 }
@@ -985,7 +810,7 @@ static int launch_tn_split_i(const TnRoute& r, const TnProduct& p, hipStream_t s
 // k_gemm_tn_ws is built for the two-operand product [X | S]^T dKMQ, (KT, NT) = (7, 13), in the three arithmetic forms
 int launch_tn_ws(const TnRoute& r, const TnProduct& p, hipStream_t stream) {
   return dispatch_int<3, 2, 1>(r.np, [&](auto np) {
-    return dispatch_bool(r.live, [&](auto live) { return launch_tn_ws_i<7, 13, false, np.value, live.value>(r, p, stream); });
+    return dispatch_bool(r.live, [&](auto live) { return launch_tn_ws_i<7, 13, np.value, live.value>(r, p, stream); });
   });
 }
 // (KT, NT) = (7, 13) or (13, 7); the row gather exists for (13, 7) without prologue in the six-MFMA form

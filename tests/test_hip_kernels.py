@@ -36,6 +36,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.qagnn_abi_version() == _lib.ABI_VERSION
 
 
+def test_source_hash_covers_every_included_file():
+    """`-m "not gpu"`: every file a csrc source pulls in with #include "...", directly or through a header, is in the file set of
+    build.source_hash() -- a header outside it could change under a stale library that is then reused."""
+    import re
+    from qagnn_amd import build as B
+    hashed = {os.path.realpath(p) for p in B.hashed_files()}
+    todo, seen = [os.path.join(B.CSRC, s) for s in B.SOURCES], set()
+    while todo:
+        p = os.path.realpath(todo.pop())
+        if p in seen:
+            continue
+        seen.add(p)
+        assert p in hashed, f'{os.path.relpath(p, helpers.ROOT)} is compiled into the library but not hashed'
+        with open(p) as f:
+            todo += [os.path.join(os.path.dirname(p), inc) for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', f.read(), re.M)]
+    headers = {os.path.basename(p) for p in seen} - set(B.SOURCES)
+    assert {'common.h', 'qagnn_hip.h', 'qagnn_hip_tn.h'} <= headers, headers  # the walk did follow the includes
+
+
 def hip():
     from qagnn_amd import ops
     ops.set_kernels(None)

@@ -62,8 +62,8 @@ int main() {
     r.grid = dim3((sh.No + r.nt * 16 - 1) / (r.nt * 16), (sh.Ka1 + r.kt * 16 - 1) / (r.kt * 16) + (sh.Ka2 ? (sh.Ka2 + 111) / 112 : 0), nchunk);
     for (int ws = 0; ws < 2; ++ws) {
       auto run = [&] {
-        if (wide_b) ws ? qagnn::launch_tn_ws_i<7, 13, false>(r, p, st) : qagnn::launch_tn_split_i<7, 13, false>(r, p, st);
-        else ws ? qagnn::launch_tn_ws_i<13, 7, false>(r, p, st) : qagnn::launch_tn_split_i<13, 7, false>(r, p, st);
+        if (wide_b) ws ? qagnn::launch_tn_ws_i<7, 13>(r, p, st) : qagnn::launch_tn_split_i<7, 13, false>(r, p, st);
+        else ws ? qagnn::launch_tn_ws_i<13, 7>(r, p, st) : qagnn::launch_tn_split_i<13, 7, false>(r, p, st);
       };
       for (int i = 0; i < 3; ++i) run();
       CK(hipStreamSynchronize(st));
