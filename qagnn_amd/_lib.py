@@ -29,6 +29,9 @@ EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems',
            'qagnn_store_gather', 'qagnn_graph_from_store']
 # include/qagnn_hip_tn.h, the extension header of the live-tile weight gradient (qagnn_hip.h and its ABI number are unchanged by it)
 EXPORTS_TN = ['qagnn_gemm_tn_graph_f32', 'qagnn_gemm_tn_route_query', 'qagnn_tn_work_table', 'qagnn_tn_live_tiles']
+# include/qagnn_hip_infer.h, the extension header of the forward-only (evaluation) path (likewise)
+EXPORTS_INFER = ['qagnn_infer_version', 'qagnn_bn_relu_absmax_scratch_elems', 'qagnn_bn_relu_absmax_f32', 'qagnn_stack_infer_f32',
+                 'qagnn_choice_eval_f32']
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
 ABI_VERSION = 25  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY; 25: qagnn_store, qagnn_store_gather, qagnn_graph_from_store -- the dataset's graphs resident on the device)
@@ -175,7 +178,13 @@ def load_library(path=LIB_PATH):
     lib.qagnn_hop_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _vp]
     lib.qagnn_stack_fwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
     lib.qagnn_stack_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
-    for name in EXPORTS + EXPORTS_TN:
+    lib.qagnn_infer_version.argtypes = []
+    lib.qagnn_bn_relu_absmax_scratch_elems.restype = _i64
+    lib.qagnn_bn_relu_absmax_scratch_elems.argtypes = [_i32, _i32]
+    lib.qagnn_bn_relu_absmax_f32.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+    lib.qagnn_stack_infer_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
+    lib.qagnn_choice_eval_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp]
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -1237,6 +1246,66 @@ class HipKernels(metaclass=_GuardedMeta):
         h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
         self._check(self.lib.qagnn_hop_bwd_f32(C.byref(h), self._stream()), 'qagnn_hop_bwd_f32')
         return (dX, dS, *grads)
+
+    # -- the forward-only path (include/qagnn_hip_infer.h) ----------------------------------------------------------------------------------
+    def bn_relu_absmax(self, H, scale, shift, out=None):
+        """max relu(scale * H + shift) merged into out[0] (int32 [>= 1]; None: a zeroed int32 [4] is allocated); H [R, Cc], rows may be pitched"""
+        _chkp(H, 'H')
+        R, Cc = H.shape
+        assert scale.is_contiguous() and shift.is_contiguous() and scale.numel() == shift.numel() == Cc and scale.dtype == shift.dtype == torch.float32
+        if out is None:
+            out = torch.empty(4, dtype=torch.int32, device=H.device)
+            self._check(self.lib.qagnn_zero_words(out.data_ptr(), 4, self._stream()), 'qagnn_zero_words')
+        assert out.dtype == torch.int32 and out.is_cuda
+        scratch = torch.empty(max(int(self.lib.qagnn_bn_relu_absmax_scratch_elems(R, Cc)), 1), dtype=torch.float32, device=H.device)
+        self._check(self.lib.qagnn_bn_relu_absmax_f32(H.data_ptr(), _ld(H), R, Cc, scale.data_ptr(), shift.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                                                      self._stream()), 'qagnn_bn_relu_absmax_f32')
+        return out
+
+    def choice_eval(self, logits, labels, counts, pred=None):
+        """logits [Q, nc] fp32 (rows may be pitched), labels int64 [Q] or None, counts int64 [2] = (correct, seen), added to in place;
+        pred: int64 [Q] to receive the argmax, or None.  No synchronisation (qagnn_choice_eval_f32)."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        Q, nc = logits.shape
+        assert counts.dtype == torch.long and counts.numel() == 2 and counts.is_contiguous() and counts.is_cuda
+        assert labels is None or (labels.dtype == torch.long and labels.numel() == Q and labels.is_contiguous() and labels.is_cuda)
+        assert pred is None or (pred.dtype == torch.long and pred.numel() == Q and pred.is_contiguous() and pred.is_cuda)
+        self._check(self.lib.qagnn_choice_eval_f32(logits.data_ptr(), _ld(logits), _ptr(labels), Q, nc, _ptr(pred), counts.data_ptr(), self._stream()),
+                    'qagnn_choice_eval_f32')
+        return counts
+
+    def stack_infer(self, graph, HP, qscale, X, S, ntype, prms, eps, cols=-1, x_amax=None, s_amax=None, keep=False):
+        """The k-hop forward with running statistics and no dropout that keeps nothing (qagnn_stack_infer_f32): ONE set of hop buffers shared
+        by all hops plus two alternating y.  -> (y [N, DP], amax [k, HOP_AMAX_WORDS]).  keep=True (tests): a set of buffers per hop, returned
+        as a third value (KMQ, aa, rows, stats) laid out as stack_fwd's saved tensors."""
+        k = len(prms)
+        N, DP, Ep, dev = graph.N, 4 * HP, graph.Ep, X.device
+        kk = k if keep else 1
+        KMQ = torch.empty((kk, N, 3 * DP), dtype=torch.float32, device=dev)
+        aa = torch.empty((kk, 2, Ep, 4), dtype=torch.float32, device=dev)
+        rows = torch.empty((kk, 4, N, DP), dtype=torch.float32, device=dev) if keep else torch.empty((5, N, DP), dtype=torch.float32, device=dev)
+        stats = torch.empty((kk, 5, DP), dtype=torch.float32, device=dev)
+        amax = torch.empty((k, HOP_AMAX_WORDS), dtype=torch.int32, device=dev)
+        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP), dtype=torch.float32, device=dev)
+        hops = (qagnn_hop_args * k)()
+        x = X
+        p_kmq, p_aa, p_rows, p_stats, p_amax, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), N * DP * 4
+        for l in range(k):
+            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], False, eps, 0.0, 0, True, cols, running=None)
+            j = l if keep else 0
+            self._set_saved(h, p_kmq + j * 3 * row_b, p_aa + 2 * j * Ep * 16, p_rows + 4 * j * row_b, p_stats + j * 5 * DP * 4,
+                            p_amax + l * HOP_AMAX_WORDS * 4, Ep, row_b)
+            y = rows[l, 3] if keep else rows[3 + (l & 1)]  # (shared set: aggr | h1 | out | y even | y odd)
+            h.y = y.data_ptr()
+            if l == 0 and x_amax is not None:
+                h.x_amax = x_amax.data_ptr()
+            if s_amax is not None:
+                h.s_amax = s_amax.data_ptr()
+            h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
+            hops[l] = h
+            x = y
+        self._check(self.lib.qagnn_stack_infer_f32(hops, k, self._stream()), 'qagnn_stack_infer_f32')
+        return (x, amax, (KMQ, aa, rows, stats)) if keep else (x, amax)
 
     # -- the whole k-hop stack per call (csrc/hop.hip: qagnn_stack_{fwd,bwd}_f32) -------------------------------------------------------
     def stack_fwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, cols=-1, x_amax=None, s_amax=None):

@@ -8,6 +8,7 @@
 
 #include "../../include/qagnn_hip.h"
 #include "../../include/qagnn_hip_tn.h"
+#include "../../include/qagnn_hip_infer.h"
 
 namespace qagnn {
 
@@ -180,6 +181,8 @@ int launch_edge_attn_bwd(const qagnn_graph* g, const float* KMQ, int32_t ldk, co
                          const float* a, const float* alpha, const float* G, int32_t ldg, float* dKMQ, float* dEkEm, float* ga, float* rs,
                          float* cls_part, float* amax_part /* [3 N] or nullptr */, uint32_t* amax_slot, hipStream_t stream);
 int launch_amax_reduce(const float* part, int64_t n, uint32_t* slot, hipStream_t stream);  // max of n non-negative floats -> *slot (elementwise.hip)
+// max relu(scale * H + shift) over R x Cc -> *slot, through per-block partials in `part` (infer.hip: qagnn_bn_relu_absmax_f32 after its checks)
+int launch_bn_relu_absmax(const float* H, int ldh, int R, int Cc, const float* scale, const float* shift, uint32_t* slot, float* part, hipStream_t stream);
 
 // launch timing (timing.hip): a scope at the top of an entry point brackets everything it launches on `s` while qagnn_timing_enable(1)
 struct TimedScope {

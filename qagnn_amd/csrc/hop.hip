@@ -57,13 +57,18 @@ struct HopAmax {
   uint32_t* s;      // max |S|
   uint32_t* y;      // where this hop's GELU / dropout leaves max |y|
   uint32_t* own;    // the hop's own block
+  bool h1_pass;     // AM_H1 from a pass over h1 (the forward-only stack: running statistics give no bound)
 };
 // The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays where products take packed B images
-static bool hop_h2(const qagnn_hop_args* h) { return h->gemm_split >= 2 && h->amax != nullptr && h->batch_stats && nn_rows_packed(h->N); }
+static bool hop_h2(const qagnn_hop_args* h, bool infer = false) {
+  // infer (qagnn_stack_infer_f32): running statistics -- max relu(bn(h1)) is then measured, not bounded (HopAmax.h1_pass)
+  return h->gemm_split >= 2 && h->amax != nullptr && (infer ? !h->batch_stats : h->batch_stats != 0) && nn_rows_packed(h->N);
+}
 // gemm_split == 3: the reduced-precision form (one fp16 MFMA per product) wherever 2 would take three
 static int hop_pieces(const qagnn_hop_args* h) { return h->gemm_split == 3 ? 1 : 0; }
-static HopAmax hop_amax_single(const qagnn_hop_args* h) {
-  HopAmax m{hop_h2(h), nullptr, nullptr, nullptr, h->amax};
+static HopAmax hop_amax_single(const qagnn_hop_args* h, bool infer = false) {
+  HopAmax m{hop_h2(h, infer), nullptr, nullptr, nullptr, h->amax, false};
+  m.h1_pass = m.on && infer && h->DP > 192 && h->DP <= 208;  // (the widths at which the training forward takes the bound: hop_fwd_one)
   if (m.on) {  // (x_amax / s_amax: words the caller's producers filled; read-only here)
     m.x = h->x_amax ? const_cast<uint32_t*>(h->x_amax) : h->amax + AM_X;
     m.s = h->s_amax ? const_cast<uint32_t*>(h->s_amax) : h->amax + AM_S;
@@ -72,11 +77,11 @@ static HopAmax hop_amax_single(const qagnn_hop_args* h) {
   return m;
 }
 // hop l of a stack: X / S words shared along the chain where the tensors are
-static HopAmax hop_amax_stack(const qagnn_hop_args* hops, int k, int l) {
-  HopAmax m = hop_amax_single(&hops[l]);
+static HopAmax hop_amax_stack(const qagnn_hop_args* hops, int k, int l, bool infer = false) {
+  HopAmax m = hop_amax_single(&hops[l], infer);
   if (!m.on) return m;
-  if (l > 0 && hop_h2(&hops[l - 1]) && hops[l].X == hops[l - 1].y && hops[l - 1].apply_act && !hops[l].x_amax) m.x = hops[l - 1].amax + AM_Y;
-  if (l > 0 && hop_h2(&hops[0]) && hops[l].S == hops[0].S && hops[l].SP == hops[0].SP && !hops[l].s_amax)
+  if (l > 0 && hop_h2(&hops[l - 1], infer) && hops[l].X == hops[l - 1].y && hops[l - 1].apply_act && !hops[l].x_amax) m.x = hops[l - 1].amax + AM_Y;
+  if (l > 0 && hop_h2(&hops[0], infer) && hops[l].S == hops[0].S && hops[l].SP == hops[0].SP && !hops[l].s_amax)
     m.s = hops[0].s_amax ? const_cast<uint32_t*>(hops[0].s_amax) : hops[0].amax + AM_S;
   return m;
 }
@@ -177,10 +182,15 @@ static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready,
     HOP_TRY(qagnn_bn_finalize_f32(mean_u, var_u, h->gamma, h->beta, h->eps, invstd, scale, shift, DP, h->run_mean, h->run_var,
                                   h->num_batches_tracked, h->dense_pos, h->d, h->momentum, unbias, h->ones_col, stream));
   }
+  // the true maximum of relu(bn(h1)): one read of h1 (infer.hip); its partials lie where the edge kernel's were folded from (they fit:
+  // qagnn_stack_infer_f32 checks it on the host)
+  if (am.h1_pass) {
+    HOP_TRY(launch_bn_relu_absmax(h->h1, DP, N, DP, scale, shift, am.own + AM_H1, ampart, (hipStream_t)stream));
+  }
   qagnn_gemm_nn_args g2 = {};
   g2.A1 = h->h1; g2.lda1 = DP; g2.K1 = DP; g2.B1 = h->W2t; g2.ldb1 = DP; g2.C = h->out; g2.ldc = DP; g2.M = N; g2.No = DP; g2.bias = h->b2;
   g2.a_scale = scale; g2.a_shift = shift;
-  if (h1_bound) { g2.a_amax1 = am.own + AM_H1; g2.pieces = hop_pieces(h); }
+  if (h1_bound || am.h1_pass) { g2.a_amax1 = am.own + AM_H1; g2.pieces = hop_pieces(h); }
   HOP_TRY(hop_nn(h, &g2, h->W2, DP, nullptr, 0, pkws, pk_elems, stream));
   if (h->apply_act) {  // X' = dropout(GELU(out))  (:48-49)
     QAGNN_REQUIRE(h->p_drop >= 0.f && h->p_drop < 1.f, QAGNN_EINVAL, "hop_fwd: p=%f", h->p_drop);
@@ -408,22 +418,55 @@ extern "C" int qagnn_hop_bwd_f32(const qagnn_hop_args* h, qagnn_stream_t stream)
 // hops[l] is a complete qagnn_hop_args; the caller chains them (hops[l+1].X = hops[l].y, hops[l].dy = hops[l+1].dX, shared dS
 // with accumulate_dS = 1 on all but the hop whose backward runs first).  Pure sequencing: the same launches, in the same order,
 // as k calls of qagnn_hop_fwd_f32 / qagnn_hop_bwd_f32 -- one FFI crossing and one autograd node instead of k for host-bound batches.
-extern "C" int qagnn_stack_fwd_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {
-  QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_fwd: no hops");
-  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], "stack_fwd"));  // (every hop, before the first enqueue)
+static int stack_fwd_impl(const qagnn_hop_args* hops, int32_t k, bool infer, qagnn_stream_t stream) {
   // the hops' amax blocks start at zero: one launch when they are one array (the module mirror's are), one per hop otherwise
   bool any = false, one_array = true;
   for (int l = 0; l < k; ++l) {
-    any = any || hop_h2(&hops[l]);
+    any = any || hop_h2(&hops[l], infer);
     one_array = one_array && hops[l].amax != nullptr && hops[l].amax == hops[0].amax + (int64_t)l * QAGNN_HOP_AMAX_WORDS;
   }
   if (any && one_array) HOP_TRY(qagnn_zero_words(hops[0].amax, (int64_t)k * QAGNN_HOP_AMAX_WORDS, stream));
   for (int l = 0; l < k; ++l) {
-    const HopAmax am = hop_amax_stack(hops, k, l);
+    const HopAmax am = hop_amax_stack(hops, k, l, infer);
     if (am.on && !one_array) HOP_TRY(qagnn_zero_words(hops[l].amax, QAGNN_HOP_AMAX_WORDS, stream));
     HOP_TRY(hop_fwd_one(&hops[l], am, am.on && am.x != hops[l].amax + AM_X, am.on && am.s != hops[l].amax + AM_S, stream));
   }
   return QAGNN_OK;
+}
+
+extern "C" int qagnn_stack_fwd_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {
+  QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_fwd: no hops");
+  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], "stack_fwd"));  // (every hop, before the first enqueue)
+  return stack_fwd_impl(hops, k, false, stream);
+}
+
+// The forward-only stack (include/qagnn_hip_infer.h): running statistics, no dropout, nothing kept -- the hops may write one shared set
+// of result buffers, y alternating between two.  All on one stream, in order: hop l + 1 starts after hop l's last launch, so the only
+// aliasing that can go wrong is inside ONE hop, and that is refused here, on the host.
+extern "C" int qagnn_stack_infer_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {
+  QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_infer: no hops");
+  for (int l = 0; l < k; ++l) {  // (every hop, before the first enqueue)
+    const qagnn_hop_args* h = &hops[l];
+    HOP_TRY(check_hop(h, "stack_infer"));
+    QAGNN_REQUIRE(!h->batch_stats && h->run_mean_p && h->run_var_p, QAGNN_EINVAL, "stack_infer: hop %d asks for batch statistics", l);
+    QAGNN_REQUIRE(!h->run_mean && !h->run_var && !h->num_batches_tracked, QAGNN_EINVAL, "stack_infer: hop %d would update running statistics", l);
+    QAGNN_REQUIRE(h->p_drop == 0.f, QAGNN_EINVAL, "stack_infer: hop %d has dropout p=%f", l, h->p_drop);
+    // what the hop writes against what it reads, as byte ranges: a result buffer that overlaps X or S anywhere is refused, not only one
+    // that starts where they start
+    const int64_t row = (int64_t)h->N * h->DP * 4, edges = (int64_t)h->g->Ep * 16;
+    const struct { const void* p; int64_t bytes; } wr[] = {{h->KMQ, 3 * row}, {h->a, edges}, {h->alpha, edges}, {h->aggr, row}, {h->h1, row},
+                                                           {h->out, row}, {h->stats, (int64_t)5 * h->DP * 4}, {h->apply_act ? h->y : nullptr, row}};
+    const struct { const void* p; int64_t bytes; } rd[] = {{h->X, row}, {h->SP > 0 ? h->S : nullptr, (int64_t)h->N * h->SP * 4}};
+    for (const auto& w : wr)
+      for (const auto& r : rd) {
+        const char* const wp = (const char*)w.p, *const rp = (const char*)r.p;
+        QAGNN_REQUIRE(!wp || !rp || wp + w.bytes <= rp || rp + r.bytes <= wp, QAGNN_EINVAL,
+                      "stack_infer: hop %d writes into one of its own inputs (y over X, or X / S inside its result buffers)", l);
+      }
+    QAGNN_REQUIRE(qagnn_bn_relu_absmax_scratch_elems(h->N, h->DP) <= max64(h->N, gelu_amax_scratch_elems((int64_t)h->N * h->DP)), QAGNN_EINVAL,
+                  "stack_infer: the partial maxima of bn_relu_absmax do not fit the hop workspace");
+  }
+  return stack_fwd_impl(hops, k, true, stream);
 }
 
 extern "C" int qagnn_stack_bwd_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {

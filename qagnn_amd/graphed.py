@@ -43,6 +43,104 @@ def edge_capacity(E, floor=1024):
     return (E + step - 1) // step * step
 
 
+# ---- what a captured training step (GraphedStep) and a captured eval forward (inference.GraphedForward) share ----------------------
+def as_holder(packed, who):
+    """the graph input as one of data_utils.GRAPH_HOLDERS (the plain int64 pair becomes an EdgeListBatch without a count word of its own:
+    the capture's static one is written)"""
+    if isinstance(packed, GRAPH_HOLDERS):
+        return packed
+    assert isinstance(packed, (tuple, list)) and len(packed) == 2 and all(isinstance(t, torch.Tensor) for t in packed), \
+        f'{who} takes the graph as a PackedGraphBatch, an EdgeListBatch, a StoreBatch or an (edge_index [2, E], edge_type [E]) pair'
+    return EdgeListBatch(packed[0], packed[1], count=False)
+
+
+def capture_dims(cids, packed):
+    """(B, n) of a batch: the holder's own where it carries the node fields, else the caller's tensors'"""
+    return (packed.B, packed.n) if packed.own_fields else (cids.size(0), cids.size(1))
+
+
+def alloc_static_fields(c, packed, B, n, dev):
+    """c.cids / nt / ns / al: static buffers of the four node tensors -- None for a holder with fields of its own (outputs of the captured
+    gather)"""
+    c.cids = c.nt = c.ns = c.al = None
+    if not packed.own_fields:
+        c.cids = torch.empty((B, n), dtype=torch.long, device=dev)
+        c.nt = torch.empty((B, n), dtype=torch.long, device=dev)
+        c.ns = torch.empty((B, n, 1), dtype=torch.float32, device=dev)
+        c.al = torch.empty((B,), dtype=torch.long, device=dev)
+
+
+def load_static_inputs(c, sent, cids, nt, ns, al, packed):
+    """one non-blocking copy per tensor into the capture's static buffers, the graph through its holder's refill"""
+    with torch.no_grad():
+        c.sent.copy_(sent, non_blocking=True)
+    if not c.packed.own_fields:
+        c.cids.copy_(cids, non_blocking=True)
+        c.nt.copy_(nt, non_blocking=True)
+        c.ns.copy_(ns.reshape(c.ns.shape), non_blocking=True)
+        c.al.copy_(al, non_blocking=True)
+    c.packed.refill(packed)
+
+
+def fetch_own_fields(c):
+    """a holder with fields of its own: the gather is part of the captured work, it reads the static id buffer and the model consumes its
+    outputs in place"""
+    if c.packed.own_fields:
+        c.packed.reset()
+        c.cids, c.nt, c.ns, c.al = c.packed.fields()
+
+
+def warm_up(dev, times, fn):
+    """`times` runs of fn outside the capture (lazy initialisation: operand-packing plans, LDS attribute raises, allocator pools), on a side
+    stream as torch's capture recipe asks"""
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        for _ in range(times):
+            fn()
+    torch.cuda.current_stream(dev).wait_stream(s)
+    torch.cuda.synchronize(dev)
+
+
+def capture_graph(pool, watched, fn):
+    """-> (graph, fn's result) with fn's launches captured; the flag tensors of the captured preparation kernels land in `watched` (kept
+    alive, read behind every replay)"""
+    from ._lib import ERR_WATCH
+    graph = torch.cuda.CUDAGraph()
+    ERR_WATCH.sink = watched
+    try:
+        with torch.cuda.graph(graph, pool=pool):
+            out = fn()
+    finally:
+        ERR_WATCH.sink = None
+    return graph, out
+
+
+def capture_or_fall_back(owner, who, capture):
+    """capture(); a capture that rejects the forked side streams is taken again on one stream (owner.overlap off: same launches, no overlap
+    inside the graph)"""
+    try:
+        return capture()
+    except RuntimeError as e:
+        if not owner.overlap:
+            raise
+        import warnings
+        warnings.warn(f'{who}: capture with side streams failed ({str(e)[:300]}); capturing on one stream')
+        owner.overlap = False
+        torch.cuda.synchronize(owner.dev)
+        return capture()
+
+
+def replay(c, load):
+    """the previous replays' validation flags that have landed (a corrupt batch raises here, one call late), the refill, the launch"""
+    from ._lib import ERR_WATCH
+    ERR_WATCH.poll()
+    load()
+    c.graph.replay()
+    c.replays += 1
+    ERR_WATCH.after_replay(c.watched)
+
+
 class _Captured:
     # packed: the static twin of the graph input (data_utils: static_twin / refill), the holder the captured step reads
     __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'lw', 'packed', 'logits', 'attn', 'loss', 'grads', 'replays', 'params', 'watched', 'sent_grad')
@@ -78,9 +176,7 @@ class GraphedStep:
 
     # -- the eager step that gets captured -------------------------------------------------------------------------------------------
     def _step(self, c):
-        if c.packed.own_fields:
-            c.packed.reset()  # the gather is part of the step: it reads the static id buffer, the model consumes its outputs in place
-            c.cids, c.nt, c.ns, c.al = c.packed.fields()
+        fetch_own_fields(c)
         logits, attn = self.model(c.sent, c.cids, c.nt, c.ns, c.al, c.packed)
         loss = torch.nn.functional.cross_entropy(logits.view(-1, self.nc), c.labels) * c.lw
         loss.backward()
@@ -88,47 +184,43 @@ class GraphedStep:
 
     def _key(self, sent, cids, packed):
         trainable = tuple(i for i, p in enumerate(self.model.parameters()) if p.requires_grad)
-        B, n = (packed.B, packed.n) if packed.own_fields else (cids.size(0), cids.size(1))
+        B, n = capture_dims(cids, packed)
         return (B, n, sent.size(1), int(self.capacity(packed.E)), bool(self.model.training), bool(sent.requires_grad), hash(trainable), packed.capture_kind())
 
     def _capture(self, key, args):
         B, n, sent_dim, e_cap, _, sent_rg = key[:6]
         sent, cids, nt, ns, al, packed, labels, lw = args
         dev, K = self.dev, ops.kernels()
-        from ._lib import ERR_WATCH
         c = _Captured()
         c.params = [p for p in self.model.parameters() if p.requires_grad]
         c.watched, c.sent_grad = [], None
         c.sent = torch.empty((B, sent_dim), dtype=torch.float32, device=dev, requires_grad=sent_rg)
-        c.cids = c.nt = c.ns = c.al = None  # (a holder with fields of its own: outputs of the captured gather)
-        if not packed.own_fields:
-            c.cids = torch.empty((B, n), dtype=torch.long, device=dev)
-            c.nt = torch.empty((B, n), dtype=torch.long, device=dev)
-            c.ns = torch.empty((B, n, 1), dtype=torch.float32, device=dev)
-            c.al = torch.empty((B,), dtype=torch.long, device=dev)
+        alloc_static_fields(c, packed, B, n, dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev)
         c.lw = torch.ones((), dtype=torch.float32, device=dev)
         c.packed = packed.static_twin(B, n, e_cap, dev)  # the graph input in static buffers laid out for the bucket's capacity
         c.replays = 0
         self._load(c, args)
-        # warm-up outside the capture (lazy initialisation: operand-packing plans, LDS attribute raises, allocator pools), on a side
-        # stream as torch's capture recipe asks; module buffers (BatchNorm running statistics, batch counters) are put back afterwards
+        # warm-up outside the capture; module buffers (BatchNorm running statistics, batch counters) are put back afterwards
         saved = [(b, b.detach().clone()) for b in self.model.buffers()]
         held = [p.grad for p in c.params]  # a capture in the middle of an accumulation window must not lose the window's gradients
         old = ops.WGRAD_OVERLAP, ops.PREP_OVERLAP
         ops.WGRAD_OVERLAP = ops.WGRAD_OVERLAP and self.wgrad_overlap and self.overlap
         ops.PREP_OVERLAP = ops.PREP_OVERLAP and self.overlap
+
+        def fresh_step():
+            for p in c.params:
+                p.grad = None
+            c.sent.grad = None
+            return self._step(c)
+
+        def step_and_advance():
+            out = self._step(c)
+            K.seed_epoch_advance(1)  # the next replay draws different dropout masks
+            return out
+
         try:
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                for _ in range(self.warmup):
-                    for p in c.params:
-                        p.grad = None
-                    c.sent.grad = None
-                    self._step(c)
-            torch.cuda.current_stream(dev).wait_stream(s)
-            torch.cuda.synchronize(dev)
+            warm_up(dev, self.warmup, fresh_step)
             with torch.no_grad():
                 for b, v in saved:
                     b.copy_(v)
@@ -137,14 +229,7 @@ class GraphedStep:
             c.sent.grad = None
             if self._pool is None:
                 self._pool = torch.cuda.graph_pool_handle()
-            c.graph = torch.cuda.CUDAGraph()
-            ERR_WATCH.sink = c.watched  # the flag tensors of the captured preparation kernels (kept alive, read behind every replay)
-            try:
-                with torch.cuda.graph(c.graph, pool=self._pool):
-                    c.logits, c.attn, c.loss = self._step(c)
-                    K.seed_epoch_advance(1)  # the next replay draws different dropout masks
-            finally:
-                ERR_WATCH.sink = None
+            c.graph, (c.logits, c.attn, c.loss) = capture_graph(self._pool, c.watched, step_and_advance)
         finally:
             ops.WGRAD_OVERLAP, ops.PREP_OVERLAP = old
         c.grads = [p.grad for p in c.params]
@@ -157,44 +242,19 @@ class GraphedStep:
 
     def _load(self, c, args):
         sent, cids, nt, ns, al, packed, labels, lw = args
-        with torch.no_grad():
-            c.sent.copy_(sent, non_blocking=True)
         c.labels.copy_(labels, non_blocking=True)
         c.lw.fill_(float(lw))
-        if not c.packed.own_fields:
-            c.cids.copy_(cids, non_blocking=True)
-            c.nt.copy_(nt, non_blocking=True)
-            c.ns.copy_(ns.reshape(c.ns.shape), non_blocking=True)
-            c.al.copy_(al, non_blocking=True)
-        c.packed.refill(packed)
+        load_static_inputs(c, sent, cids, nt, ns, al, packed)
 
     def __call__(self, sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight=1.0, accumulate=False):
-        if not isinstance(packed, GRAPH_HOLDERS):
-            assert isinstance(packed, (tuple, list)) and len(packed) == 2 and all(isinstance(t, torch.Tensor) for t in packed), \
-                'GraphedStep takes the graph as a PackedGraphBatch, an EdgeListBatch, a StoreBatch or an (edge_index [2, E], edge_type [E]) pair'
-            packed = EdgeListBatch(packed[0], packed[1], count=False)  # (no count word of its own: the capture's static one is written)
+        packed = as_holder(packed, 'GraphedStep')
         args = (sent_vecs, concept_ids, node_type_ids, node_scores, adj_lengths, packed, labels, loss_weight)
         key = self._key(sent_vecs, concept_ids, packed)
         with torch.cuda.device(self.dev):
             c = self._captured.get(key)
             if c is None:
-                try:
-                    c = self._capture(key, args)
-                except RuntimeError as e:
-                    if not self.overlap:
-                        raise
-                    # a capture that rejects the forked side streams: same launches on one stream (no overlap inside the graph)
-                    import warnings
-                    warnings.warn(f'GraphedStep: capture with side streams failed ({str(e)[:300]}); capturing on one stream')
-                    self.overlap = False
-                    torch.cuda.synchronize(self.dev)
-                    c = self._capture(key, args)
-            from ._lib import ERR_WATCH
-            ERR_WATCH.poll()  # the previous replays' validation flags that have landed: a corrupt batch raises here, one step late
-            self._load(c, args)
-            c.graph.replay()
-            c.replays += 1
-            ERR_WATCH.after_replay(c.watched)
+                c = capture_or_fall_back(self, 'GraphedStep', lambda: self._capture(key, args))
+            replay(c, lambda: self._load(c, args))
             self.params, self.sent_grad = c.params, c.sent_grad
             if accumulate:
                 # the static gradients are overwritten by the next replay: the window's sum lives in tensors of its own

@@ -463,7 +463,10 @@ class QAGNN_Message_Passing(nn.Module):
         Kp = ops.kernels()
         stack_native = self.k > 0 and ops.use_fused_hop(bs * n) and hasattr(Kp, 'stack_fwd') and ops.FUSED_STACK
         bn0 = self.gnn_layers[0].mlp[1] if self.k > 0 else None
-        pieces = ({2: 2, 3: 1}[Kp.gemm_split] if (stack_native and getattr(Kp, 'gemm_split', 1) >= 2 and (self.training or not bn0.track_running_stats))
+        # (the forward-only stack, ops.inference_path: opt-in, eval mode without autograd and with running statistics; it runs the form too)
+        infer = (stack_native and ops.INFERENCE_PATH and not self.training and not torch.is_grad_enabled() and bn0.track_running_stats
+                 and hasattr(Kp, 'stack_infer'))
+        pieces = ({2: 2, 3: 1}[Kp.gemm_split] if (stack_native and getattr(Kp, 'gemm_split', 1) >= 2 and (self.training or not bn0.track_running_stats or infer))
                   else 3)  # (3 -> one image: the reduced-precision form, on request only)
         pairs = []
         for pk in per_layer:
@@ -494,9 +497,13 @@ class QAGNN_Message_Passing(nn.Module):
                     W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p = pk[8:]
                     prms.append((Wx_t, Wx, Ws_t, Ws, TT[l], ekem[l], W1t, W1p, b1, gam, bet, W2t, W2p, b2, rm_p, rv_p))
                     runnings.append(bn_running(bn, L, Hp.size(0), self.training))
-                Xp = ops.gat_stack(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms,
-                                   self.training or not bn0.track_running_stats, bn0.eps, self.dropout_rate if self.training else 0.0,
-                                   runnings, accX=accX, tab_col=(self._tab_col, L.ones_col))
+                if infer:
+                    Xp = ops.stack_infer(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms, bn0.eps,
+                                         tab_col=(self._tab_col, L.ones_col))
+                else:
+                    Xp = ops.gat_stack(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms,
+                                       self.training or not bn0.track_running_stats, bn0.eps, self.dropout_rate if self.training else 0.0,
+                                       runnings, accX=accX, tab_col=(self._tab_col, L.ones_col))
                 per_layer = []
             for l, (layer, pk) in enumerate(zip(self.gnn_layers, per_layer)):  # mp_helper (:45-50): GATConvE -> GELU -> dropout, fused
                 Xp, _ = layer.hop(Xp, None, graph, None, L, apply_act=True, p_drop=self.dropout_rate, typed=(temb, ntype, S),

@@ -235,6 +235,9 @@ _SIDE_STREAMS = {}
 #     reads it (_wgrad below is the one place that allocates, queues and keeps).
 WGRAD_OVERLAP = os.environ.get('QAGNN_WGRAD_OVERLAP', '1') == '1'
 _DEFER = [False]
+# The forward-only stack (include/qagnn_hip_infer.h) for eval-mode forwards under torch.no_grad(): opt-in, see stack_infer below and
+# QAGNN_Message_Passing.forward.  Off: every forward is the one it was before the path existed, launch for launch.
+INFERENCE_PATH = False
 
 
 class wgrad_scope:
@@ -988,6 +991,41 @@ class StackFn(torch.autograd.Function):
             #       Wx_t   Wx    Ws_t   Ws    TT   EkEm   W1t   W1   b1   gamma   beta   W2t   W2   b2  run_mean run_var
             out += [dWx_t, None, dWs_t, None, dTT, dEkEm, dW1t, None, db1, dgamma, dbeta, dW2t, None, db2, None, None]
         return (dX, dS, None, None, None, None, None, None, None, None, None, None, None, None, *out)
+
+
+class inference_path:
+    """`with ops.inference_path():` -- eval-mode forwards under torch.no_grad() inside the scope take the forward-only stack (where the
+    provider has one); qagnn_amd.inference wraps its forwards in it."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global INFERENCE_PATH
+        self.prev = INFERENCE_PATH
+        INFERENCE_PATH = self.on
+        return self
+
+    def __exit__(self, *exc):
+        global INFERENCE_PATH
+        INFERENCE_PATH = self.prev
+        return False
+
+
+def stack_infer(X, S, ntype, graph, HP, qscale, prms, eps, tab_col=-1):
+    """All k hops (GELU after each) with BatchNorm's running statistics and no dropout, keeping nothing: a plain function, no autograd
+    node, no seed drawn.  One set of hop buffers and two alternating outputs are allocated, whatever k (the training stack keeps
+    K|M|Q, the attention, aggr, h1, out and y of every hop for its backward).  The last hop's max |y| is noted like StackFn's, so the
+    output layer behind the stack takes the three-MFMA form too."""
+    K = kernels()
+    xw, sw = amax_lookup(X), amax_lookup(S)
+    kw = {}
+    if xw is not None or sw is not None:
+        kw = dict(x_amax=xw, s_amax=sw)
+    y, amax = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **kw)
+    if _wants_amax(K, X):  # (the library's own condition for the form: csrc/hop.hip, hop_h2 with infer)
+        amax_note(y, amax[len(prms) - 1, 4:5])
+    return y
 
 
 def gat_stack(X, S, ntype, graph, HP, qscale, prms, batch_stats, eps, p, runnings, accX=None, tab_col=-1):
