@@ -32,6 +32,10 @@ EXPORTS_TN = ['qagnn_gemm_tn_graph_f32', 'qagnn_gemm_tn_route_query', 'qagnn_tn_
 # include/qagnn_hip_infer.h, the extension header of the forward-only (evaluation) path (likewise)
 EXPORTS_INFER = ['qagnn_infer_version', 'qagnn_bn_relu_absmax_scratch_elems', 'qagnn_bn_relu_absmax_f32', 'qagnn_stack_infer_f32',
                  'qagnn_choice_eval_f32']
+# include/qagnn_hip_loss.h, the extension header of the training losses (likewise)
+EXPORTS_LOSS = ['qagnn_loss_version', 'qagnn_choice_loss_f32', 'qagnn_choice_loss_bwd_f32']
+LOSS_KINDS = {'cross_entropy': 0, 'margin_rank': 1}  # QAGNN_LOSS_CROSS_ENTROPY, QAGNN_LOSS_MARGIN_RANK
+LOSS_THREADS = 256  # QAGNN_LOSS_THREADS
 
 CLS_SLICES = 4  # QAGNN_CLS_SLICES
 ABI_VERSION = 25  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY; 25: qagnn_store, qagnn_store_gather, qagnn_graph_from_store -- the dataset's graphs resident on the device)
@@ -184,7 +188,10 @@ def load_library(path=LIB_PATH):
     lib.qagnn_bn_relu_absmax_f32.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
     lib.qagnn_stack_infer_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
     lib.qagnn_choice_eval_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp]
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER:
+    lib.qagnn_loss_version.argtypes = []
+    lib.qagnn_choice_loss_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]
+    lib.qagnn_choice_loss_bwd_f32.argtypes = [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -193,6 +200,18 @@ def load_library(path=LIB_PATH):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def choice_loss_bound(kind, nc, Q, max_abs=1.0, margin=0.0, weight=1.0, threads=LOSS_THREADS):
+    """(loss bound, gradient bound) of qagnn_choice_loss_f32 as include/qagnn_hip_loss.h states them: absolute errors against exact arithmetic
+    on the fp32 inputs.  max_abs: max |x| over the logits; weight: the weight word."""
+    import math
+    u, v = 2.0 ** -24, 2.0 ** -53
+    M, L, w = max(1.0, float(max_abs)), math.log(nc), abs(float(weight))
+    S = -(-Q // threads) + math.log2(threads) + nc
+    if LOSS_KINDS[kind] == 0:
+        return w * M * (u * (nc + 8 + 5 * L) + v * S * (2 + L)), w / Q * u * (nc + 8 + L)
+    return w * M * (3 * u + v * S) * (2 + abs(float(margin)) / M), w / Q * 2 * u
 
 
 def _running_fields(running):
@@ -396,6 +415,7 @@ class HipKernels(metaclass=_GuardedMeta):
         self.gemm_split = {'0': 0, '1': 1, '3': 3}.get(os.environ.get('QAGNN_GEMM_SPLIT', '2'), 2)
         self.PACK_MIN_M = int(self.lib.qagnn_packed_min_rows(-1))  # (the library's own threshold: nn2_packed_ok, hop_h2; packed_min_rows)
         self._side_streams = {}  # per device: the stream the natively sequenced hops put their weight-gradient products on
+        self._loss_flags = {}    # per device: the bad-label flag word of choice_loss
 
     # -- helpers -----------------------------------------------------------------------------------------------
     def _stream(self):
@@ -1273,6 +1293,57 @@ class HipKernels(metaclass=_GuardedMeta):
         self._check(self.lib.qagnn_choice_eval_f32(logits.data_ptr(), _ld(logits), _ptr(labels), Q, nc, _ptr(pred), counts.data_ptr(), self._stream()),
                     'qagnn_choice_eval_f32')
         return counts
+
+    # -- the training losses (include/qagnn_hip_loss.h) ---------------------------------------------------------------------------------------
+    def zero_words(self, t):
+        """zero a contiguous device tensor of 4-byte-multiple size with the library's own kernel (qagnn_zero_words): no memset node in a capture"""
+        nbytes = t.numel() * t.element_size()
+        assert t.is_cuda and t.is_contiguous() and nbytes % 4 == 0
+        self._check(self.lib.qagnn_zero_words(t.data_ptr(), nbytes // 4, self._stream()), 'qagnn_zero_words')
+        return t
+
+    def _loss_flag_word(self, device):
+        # ONE persistent flag word per device (no zeroing launch per call): ERR_WATCH clears it once it has reported it (`reset`)
+        flags = self._loss_flags.get(device)
+        if flags is None:
+            flags = self._loss_flags[device] = torch.zeros(4, dtype=torch.int32, device=device)
+        return flags
+
+    def choice_loss(self, logits, labels, kind='cross_entropy', margin=0.1, weight=None, stats=None, g=None):
+        """-> (loss fp32 [1], g [Q, nc] = d loss / d logits) in one launch (qagnn_choice_loss_f32).  logits [Q, nc] fp32, rows may be pitched;
+        labels int64 [Q]; weight: a one-element fp32 device tensor or None (= 1); stats: float64 [2] = (sum of losses, calls), added to in
+        place, or None; g: a [Q, nc] fp32 view to receive the gradient (rows may be pitched), else allocated.  A label outside [0, nc) is
+        reported through ERR_WATCH: it raises one call late, or at poll(block=True).  No synchronisation."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and (logits.stride(1) == 1 or logits.size(1) == 1)
+        Q, nc = logits.shape
+        dev = logits.device
+        assert labels.dtype == torch.long and labels.numel() == Q and labels.is_contiguous() and labels.device == dev
+        if weight is not None:
+            self._check_scale_word(weight, dev)
+        assert stats is None or (stats.dtype == torch.float64 and stats.numel() == 2 and stats.is_contiguous() and stats.device == dev)
+        if g is None:
+            g = torch.empty((Q, nc), dtype=torch.float32, device=dev)
+        assert g.dtype == torch.float32 and g.shape == (Q, nc) and g.device == dev and (g.stride(1) == 1 or nc == 1)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        flags = self._loss_flag_word(dev)
+        rc = self.lib.qagnn_choice_loss_f32(logits.data_ptr(), _ld(logits), labels.data_ptr(), Q, nc, LOSS_KINDS[kind], float(margin), _ptr(weight),
+                                            loss.data_ptr(), g.data_ptr(), _ld(g), _ptr(stats), flags.data_ptr(), self._stream())
+        self._check(rc, 'qagnn_choice_loss_f32')
+        ERR_WATCH.poll()
+        ERR_WATCH.watch(flags, f'labels (a label outside the {nc} choices)', reset=flags)
+        return loss, g
+
+    def choice_loss_bwd(self, g, grad_out, out=None):
+        """-> dlogits = g * grad_out[0] (qagnn_choice_loss_bwd_f32); grad_out: a one-element fp32 device tensor; out: g itself or a [Q, nc] view"""
+        assert g.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and (g.stride(1) == 1 or g.size(1) == 1)
+        self._check_scale_word(grad_out, g.device)
+        Q, nc = g.shape
+        if out is None:
+            out = torch.empty((Q, nc), dtype=torch.float32, device=g.device)
+        assert out.dtype == torch.float32 and out.shape == (Q, nc) and out.device == g.device and (out.stride(1) == 1 or nc == 1)
+        self._check(self.lib.qagnn_choice_loss_bwd_f32(g.data_ptr(), _ld(g), grad_out.data_ptr(), out.data_ptr(), _ld(out), Q, nc, self._stream()),
+                    'qagnn_choice_loss_bwd_f32')
+        return out
 
     def stack_infer(self, graph, HP, qscale, X, S, ntype, prms, eps, cols=-1, x_amax=None, s_amax=None, keep=False):
         """The k-hop forward with running statistics and no dropout that keeps nothing (qagnn_stack_infer_f32): ONE set of hop buffers shared

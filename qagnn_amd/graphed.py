@@ -154,17 +154,23 @@ class GraphedStep:
     then be None: the captured graph gathers them from the store itself), labels [B / num_choice].
 
     loss = cross_entropy(logits.view(-1, nc), labels) * loss_weight  (the reference's mini-batch loss, qagnn.py:257-261);
+    GraphedStep(..., loss='cross_entropy' | 'margin_rank', margin=0.1) computes it with ops.choice_loss instead -- one launch for the loss,
+    the weight and the gradient, either of the reference's --loss kinds -- and adds every replayed loss to `step.meter` (losses.LossMeter:
+    `step.meter.read()` -> (sum, count) with one synchronisation; the reference's total_loss without an .item() per mini-batch);
     after the call every trainable parameter's .grad holds this step's gradient (zero_grad implicit), or -- accumulate=True -- the
     running sum of the window's steps (the first step of a window is the one that finds .grad None, e.g. after
     optimizer.zero_grad(set_to_none=True)).  sent_vecs.requires_grad: `step.sent_grad` holds d loss / d sent_vecs afterwards.
     The set of trainable parameters is read at every call (freeze_net / unfreeze_net change it): one capture per set."""
 
-    def __init__(self, model, num_choice, capacity=edge_capacity, warmup=2):
+    def __init__(self, model, num_choice, capacity=edge_capacity, warmup=2, loss=None, margin=0.1):
+        from .losses import LossMeter, check_loss_name
+        self.loss, self.margin = (None if loss is None else check_loss_name(loss)), float(margin)
         self.model, self.nc, self.capacity, self.warmup = model, int(num_choice), capacity, int(warmup)
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.sent_grad = None
         self.dev = self.params[0].device
         assert self.dev.type == 'cuda', 'GraphedStep captures a HIP graph: the model must live on the GPU'
+        self.meter = LossMeter(self.dev) if self.loss is not None else None  # (sum, count) of the replayed losses, on the device
         self._captured = {}
         self._pool = None
         # Side streams inside the capture.  Graph preparation under the input GEMM pays (-2 % at 65 subgraphs, more below); the
@@ -178,7 +184,10 @@ class GraphedStep:
     def _step(self, c):
         fetch_own_fields(c)
         logits, attn = self.model(c.sent, c.cids, c.nt, c.ns, c.al, c.packed)
-        loss = torch.nn.functional.cross_entropy(logits.view(-1, self.nc), c.labels) * c.lw
+        if self.loss is None:
+            loss = torch.nn.functional.cross_entropy(logits.view(-1, self.nc), c.labels) * c.lw
+        else:  # one launch: the loss times the weight word, its gradient, the meter's two doubles
+            loss = ops.choice_loss(logits.view(-1, self.nc), c.labels, self.loss, self.margin, c.lw, self.meter.stats)
         loss.backward()
         return logits, attn, loss
 
@@ -204,6 +213,7 @@ class GraphedStep:
         # warm-up outside the capture; module buffers (BatchNorm running statistics, batch counters) are put back afterwards
         saved = [(b, b.detach().clone()) for b in self.model.buffers()]
         held = [p.grad for p in c.params]  # a capture in the middle of an accumulation window must not lose the window's gradients
+        metered = self.meter.stats.clone() if self.meter is not None else None  # (the warm-up steps add their losses: put back)
         old = ops.WGRAD_OVERLAP, ops.PREP_OVERLAP
         ops.WGRAD_OVERLAP = ops.WGRAD_OVERLAP and self.wgrad_overlap and self.overlap
         ops.PREP_OVERLAP = ops.PREP_OVERLAP and self.overlap
@@ -224,6 +234,8 @@ class GraphedStep:
             with torch.no_grad():
                 for b, v in saved:
                     b.copy_(v)
+                if metered is not None:
+                    self.meter.stats.copy_(metered)
             for p in c.params:
                 p.grad = None
             c.sent.grad = None

@@ -10,6 +10,7 @@ floats, DP = H*HP per row, pads are zero.  All matrices handed to the kernels ar
 """
 import math
 import os
+import struct
 import weakref
 
 import torch
@@ -1194,3 +1195,101 @@ def concept_input(emb_w, rowidx, Wc_t, bc, ctx_pre, n, p, training, Wc=None):
 
 
 QSCALE = lambda dh: 1.0 / math.sqrt(dh)  # noqa: E731  (query / sqrt(dim_per_head), modeling_qagnn.py:469)
+
+
+# ---- the training losses of the multiple-choice head (include/qagnn_hip_loss.h) -----------------------------------------------------------
+LOSS_KINDS = ('cross_entropy', 'margin_rank')
+
+
+class ChoiceLossFn(torch.autograd.Function):
+    """loss = w * cross-entropy / margin-rank of logits [Q, nc] against labels [Q]: the forward is ONE launch that also leaves
+    g = d loss / d logits, the backward ONE launch that multiplies g by the upstream gradient of the scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, K, kind, margin, weight, stats):
+        loss, g = K.choice_loss(logits, labels, kind, margin, weight, stats)
+        ctx.K = K
+        ctx.save_for_backward(g)
+        return loss.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        (g,) = ctx.saved_tensors
+        return ctx.K.choice_loss_bwd(g, dloss.reshape(1).contiguous()), None, None, None, None, None, None
+
+
+_WEIGHT_WORDS = {}
+
+
+def _weight_word(weight, device):
+    """a Python float as a one-element fp32 tensor on `device`, made once per (device, value)"""
+    key = (device, float(weight))
+    word = _WEIGHT_WORDS.get(key)
+    if word is None:
+        if len(_WEIGHT_WORDS) >= 256:  # (a training loop has a handful: (b - a) / bs of a full and of a last mini-batch)
+            _WEIGHT_WORDS.clear()
+        word = _WEIGHT_WORDS[key] = torch.full((1,), float(weight), dtype=torch.float32, device=device)
+    return word
+
+
+def _loss_provider(logits):
+    """the provider whose choice_loss takes these logits, or None (the plain-torch formulation)"""
+    K = _K
+    if K is None:
+        if not logits.is_cuda:
+            return None
+        K = kernels()
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not hasattr(K, 'choice_loss'):
+        return None
+    if not logits.is_cuda and getattr(K, 'name', 'hip') == 'hip':
+        return None
+    return K
+
+
+def choice_loss_torch(logits, labels, kind='cross_entropy', margin=0.1, weight=None, stats=None):
+    """The semantics of qagnn_choice_loss_f32 in stock torch ops, differentiable by autograd, without a host synchronisation (gather and
+    masks, no boolean-mask indexing).  A label outside [0, nc) contributes nothing and leaves the denominators alone; it is not reported."""
+    Q, nc = logits.shape
+    valid = (labels >= 0) & (labels < nc)
+    lab = labels.clamp(0, nc - 1).unsqueeze(1)
+    xl = logits.gather(1, lab)
+    if kind == 'cross_entropy':
+        rows = torch.logsumexp(logits, dim=1) - xl.squeeze(1)
+        total, denom = torch.where(valid, rows, torch.zeros_like(rows)).sum(), Q
+    else:
+        hinge = (-(xl - logits) + margin).clamp_min(0)
+        pairs = (torch.arange(nc, device=logits.device).unsqueeze(0) != lab) & valid.unsqueeze(1)
+        total, denom = torch.where(pairs, hinge, torch.zeros_like(hinge)).sum(), Q * (nc - 1)
+    loss = total / denom
+    if weight is not None:
+        loss = loss * weight.reshape(()).to(loss.dtype)
+    if stats is not None:
+        with torch.no_grad():
+            stats += torch.stack([loss.detach().float().double(), torch.ones((), dtype=torch.float64, device=loss.device)])
+    return loss
+
+
+def choice_loss(logits, labels, kind='cross_entropy', margin=0.1, weight=None, stats=None):
+    """-> the scalar loss of logits [Q, nc] against labels int64 [Q]:
+      'cross_entropy'  weight * mean_q (logsumexp(x_q) - x_q[label_q])                                  (F.cross_entropy)
+      'margin_rank'    weight * mean over q and c != label_q of max(0, margin - x_q[label_q] + x_q[c])  (nn.MarginRankingLoss on the
+                       (correct, wrong) pairs of every question; a pair on the kink is active: torch's clamp_min subgradient)
+    weight: a Python float or a one-element fp32 tensor on the logits' device (read on the device: a captured step reads each replay's
+    value from it), None = 1.  stats: float64 [2] on that device, (sum of the fp32 losses, number of calls) added to in place.
+    fp32 logits on the GPU (or any logits a test provider with a `choice_loss` takes): one launch forward (ChoiceLossFn), one backward,
+    a label outside [0, nc) is reported through _lib.ERR_WATCH.  Otherwise: choice_loss_torch."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f'unknown loss {kind!r}: one of {LOSS_KINDS}')
+    assert logits.dim() == 2 and labels.dim() == 1 and labels.size(0) == logits.size(0), 'logits [Q, nc], labels [Q]'
+    if kind == 'margin_rank' and logits.size(1) < 2:
+        raise ValueError('margin_rank needs at least two choices')
+    if weight is not None and not isinstance(weight, torch.Tensor):
+        weight = _weight_word(weight, logits.device)
+    margin = struct.unpack('f', struct.pack('f', float(margin)))[0]  # the fp32 value the kernel is handed, on every route
+    K = _loss_provider(logits)
+    if K is None:
+        return choice_loss_torch(logits, labels, kind, margin, weight, stats)
+    if logits.size(1) > 1 and logits.stride(1) != 1:  # (the kernel takes a row pitch, not a column stride)
+        logits = logits.contiguous()
+    return ChoiceLossFn.apply(logits, labels.contiguous(), K, kind, margin, weight, stats)
