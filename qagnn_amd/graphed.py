@@ -102,14 +102,15 @@ def warm_up(dev, times, fn):
     torch.cuda.synchronize(dev)
 
 
-def capture_graph(pool, watched, fn):
+def capture_graph(pool, watched, fn, tables):
     """-> (graph, fn's result) with fn's launches captured; the flag tensors of the captured preparation kernels land in `watched` (kept
-    alive, read behind every replay)"""
+    alive, read behind every replay), the (frozen table, maximum word) pairs whose word the graph reads (ops.table_amax) in `tables`
+    (brought up to date in front of every replay)"""
     from ._lib import ERR_WATCH
     graph = torch.cuda.CUDAGraph()
     ERR_WATCH.sink = watched
     try:
-        with torch.cuda.graph(graph, pool=pool):
+        with ops.table_words(tables), torch.cuda.graph(graph, pool=pool):
             out = fn()
     finally:
         ERR_WATCH.sink = None
@@ -132,10 +133,12 @@ def capture_or_fall_back(owner, who, capture):
 
 
 def replay(c, load):
-    """the previous replays' validation flags that have landed (a corrupt batch raises here, one call late), the refill, the launch"""
+    """the previous replays' validation flags that have landed (a corrupt batch raises here, one call late), the refill, the maxima of
+    frozen tables that were loaded anew since the last replay, the launch"""
     from ._lib import ERR_WATCH
     ERR_WATCH.poll()
     load()
+    ops.refresh_table_words(c.tables)
     c.graph.replay()
     c.replays += 1
     ERR_WATCH.after_replay(c.watched)
@@ -143,7 +146,7 @@ def replay(c, load):
 
 class _Captured:
     # packed: the static twin of the graph input (data_utils: static_twin / refill), the holder the captured step reads
-    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'lw', 'packed', 'logits', 'attn', 'loss', 'grads', 'replays', 'params', 'watched', 'sent_grad')
+    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'lw', 'packed', 'logits', 'attn', 'loss', 'grads', 'replays', 'params', 'watched', 'sent_grad', 'tables')
 
 
 class GraphedStep:
@@ -202,7 +205,7 @@ class GraphedStep:
         dev, K = self.dev, ops.kernels()
         c = _Captured()
         c.params = [p for p in self.model.parameters() if p.requires_grad]
-        c.watched, c.sent_grad = [], None
+        c.watched, c.tables, c.sent_grad = [], [], None
         c.sent = torch.empty((B, sent_dim), dtype=torch.float32, device=dev, requires_grad=sent_rg)
         alloc_static_fields(c, packed, B, n, dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev)
@@ -241,7 +244,7 @@ class GraphedStep:
             c.sent.grad = None
             if self._pool is None:
                 self._pool = torch.cuda.graph_pool_handle()
-            c.graph, (c.logits, c.attn, c.loss) = capture_graph(self._pool, c.watched, step_and_advance)
+            c.graph, (c.logits, c.attn, c.loss) = capture_graph(self._pool, c.watched, step_and_advance, c.tables)
         finally:
             ops.WGRAD_OVERLAP, ops.PREP_OVERLAP = old
         c.grads = [p.grad for p in c.params]

@@ -18,7 +18,7 @@ from .graphed import edge_capacity
 
 
 class _Captured:
-    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'packed', 'logits', 'attn', 'replays', 'watched')
+    __slots__ = ('graph', 'sent', 'cids', 'nt', 'ns', 'al', 'labels', 'packed', 'logits', 'attn', 'replays', 'watched', 'tables')
 
 
 class GraphedForward:
@@ -58,7 +58,7 @@ class GraphedForward:
         packed, labels = args[5], args[6]
         dev = self.dev
         c = _Captured()
-        c.watched = []
+        c.watched, c.tables = [], []
         c.sent = torch.empty((B, sent_dim), dtype=torch.float32, device=dev)
         graphed.alloc_static_fields(c, packed, B, n, dev)
         c.labels = torch.empty((B // self.nc,), dtype=torch.long, device=dev) if labels is not None else None
@@ -73,7 +73,7 @@ class GraphedForward:
             self._counts.copy_(held)
             if self._pool is None:
                 self._pool = torch.cuda.graph_pool_handle()
-            c.graph, (c.logits, c.attn) = graphed.capture_graph(self._pool, c.watched, lambda: self._forward(c))
+            c.graph, (c.logits, c.attn) = graphed.capture_graph(self._pool, c.watched, lambda: self._forward(c), c.tables)
         finally:
             ops.PREP_OVERLAP = old
         self._captured[key] = c

@@ -1134,7 +1134,11 @@ def table_amax(K, table):
     gathered rows): one reduction pass per table object and version, noted like every other operand maximum (amax_note) -- the first
     call must not fall inside a stream capture (GraphedStep's warm-up steps are eager).  An in-place update (copy_, load_state_dict)
     bumps the version and costs a new pass; an edit through `.data` bumps nothing and cannot be seen.  None where the form does not
-    apply (table not 16-byte / 4-element aligned, provider without the form)."""
+    apply (table not 16-byte / 4-element aligned, provider without the form).
+
+    A live table object keeps ONE word for its whole life: a new version is reduced into the word it already has.  A captured graph has
+    that word's address baked in; `table_words` hands a capture the (table, word) pairs it read, and refresh_table_words() brings them
+    up to date in front of a replay (a load_state_dict between two replays runs no eager forward that would)."""
     if not (getattr(K, 'gemm_split', 1) >= 2 and getattr(K, 'name', '') == 'hip') or table.requires_grad or table.numel() % 4 != 0 \
             or table.data_ptr() % 16 != 0 or not table.is_contiguous():
         return None
@@ -1142,9 +1146,43 @@ def table_amax(K, table):
     if w is None:
         if table.is_cuda and torch.cuda.is_current_stream_capturing():
             return None
+        e = _AMAX_NOTES.get(id(table))
         w = K.absmax(table.detach().view(-1))
+        if e is not None and e[0]() is table and e[2].shape == w.shape and e[2].device == w.device:
+            w = e[2].copy_(w)  # the same table at a new version: the word stays where it is
         amax_note(table, w)
+    if _table_words[0] is not None and not any(t is table for t, _ in _table_words[0]):
+        _table_words[0].append((table, w))
     return w
+
+
+_table_words = [None]  # the list of the capture in progress (table_words), or None
+
+
+class table_words:
+    """with table_words(sink): every (frozen table, maximum word) pair ops.table_amax hands out inside lands in the list `sink`"""
+
+    def __init__(self, sink):
+        self.sink = sink
+
+    def __enter__(self):
+        self.old, _table_words[0] = _table_words[0], self.sink
+        return self.sink
+
+    def __exit__(self, *exc):
+        _table_words[0] = self.old
+        return False
+
+
+def refresh_table_words(pairs):
+    """In front of a replay: a table that was updated in place since its word was written (load_state_dict, copy_: the version counter
+    moved) gets its maximum reduced again INTO that word -- one integer comparison per table otherwise."""
+    for table, word in pairs:
+        if amax_lookup(table) is word:
+            continue
+        w = table_amax(kernels(), table)
+        if w is not None and w is not word:
+            word.copy_(w)
 
 
 class ConceptInputFn(torch.autograd.Function):

@@ -785,11 +785,29 @@ def relu_sites(model_gnn, prefix):
     return sites
 
 
+def train_loss(logits, labels, kind, margin=0.1, weight=1.0):
+    """The reference's training loss (qagnn.py:208-224) from torch's own loss modules, in the dtype of `logits` [Q, nc], times `weight`:
+    nn.CrossEntropyLoss, or nn.MarginRankingLoss(margin) on the (correct, wrong) pairs of every question (a mean: the order of the
+    pairs does not matter); margin = the fp32 value the kernel gets."""
+    Q, nc = logits.shape
+    if kind == 'cross_entropy':
+        return torch.nn.functional.cross_entropy(logits, labels) * weight
+    assert kind == 'margin_rank', kind
+    crit = torch.nn.MarginRankingLoss(margin=float(np.float32(margin)), reduction='mean')
+    ones = torch.ones(nc - 1, dtype=logits.dtype)
+    terms = []
+    for q, l in enumerate(labels.tolist()):
+        others = torch.tensor([j for j in range(nc) if j != l])
+        terms.append(crit(logits[q, l].expand(nc - 1), logits[q, others], ones))
+    return torch.stack(terms).mean() * weight
+
+
 class F64Ref:
     """Float64 reference gradients of one (case, section) with overridable ReLU kinks; see the comment block above.
 
     section: 'grad' (QAGNN.forward, loss = sum(logits * linspace(0.5, 1.5))), 'mpgrad' (the message-passing stack on
-    mp_inputs, loss = sum(out * cos(0.37 i))), 'layergrad' (GATConvE layer 0, loss = sum(out * sin(0.11 i))).
+    mp_inputs, loss = sum(out * cos(0.37 i))), 'layergrad' (GATConvE layer 0, loss = sum(out * sin(0.11 i))), 'train' (QAGNN.forward under
+    the training loss: train_loss on the case's `labels`, `loss` kind, `margin` and `loss_weight`; tests/test_training_loop.py).
     `case`: a GOLDEN_CASES name, or a case dict with `inputs` = (sent_vecs, concept_ids, node_type_ids, node_scores,
     adj_lengths, edge_index, edge_type)."""
 
@@ -803,14 +821,14 @@ class F64Ref:
         self.inputs = inputs
         self.mp_in = mp_inputs(c)  # drawn under the fp32 default dtype: the same numbers for every run
         self.state = _KinkState()
-        model = build_oracle(c).double()  # weights are drawn in fp32, then widened
+        self.model = model = build_oracle(c).double()  # weights are drawn in fp32, then widened
         if prepare is not None:
             prepare(model)
         if section == 'layergrad':
             layer = model.gnn.gnn_layers[0]
             self.sites = [(layer.edge_encoder, 'edge_encoder.1.bias'), (layer.mlp, 'mlp.1.bias')]
         else:
-            self.sites = relu_sites(model.gnn, 'gnn.' if section == 'grad' else '')
+            self.sites = relu_sites(model.gnn, 'gnn.' if section in ('grad', 'train') else '')
         for idx, (seq, _) in enumerate(self.sites):
             assert isinstance(seq[2], torch.nn.ReLU)
             seq[2] = _KinkReLU(self.state, idx)
@@ -831,9 +849,12 @@ class F64Ref:
         B, n = c['nq'] * c['nc'], c['n']
         sv, cids, nt, ns, al, ei, et = self.inputs
         H, nsc, x, extra = self.mp_in
-        if section == 'grad':
+        if section in ('grad', 'train'):
             logits, attn = model(sv.to(dtype), cids, nt, ns.to(dtype), al, (ei, et))
-            loss = (logits * torch.linspace(0.5, 1.5, B).view(B, 1).to(dtype)).sum()
+            if section == 'train':
+                loss = train_loss(logits.view(-1, c['nc']), c['labels'], c['loss'], c.get('margin', 0.1), c['loss_weight'])
+            else:
+                loss = (logits * torch.linspace(0.5, 1.5, B).view(B, 1).to(dtype)).sum()
             params = {k: p for k, p in model.named_parameters() if p.requires_grad}
             return loss, params, {'::logits': logits.detach(), '::pool_attn': attn.detach()}
         if section == 'mpgrad':
