@@ -556,9 +556,8 @@ typedef struct qagnn_hop_args {
   uint32_t* amax;                  /* NULL, or QAGNN_HOP_AMAX_WORDS device words that belong to this hop and that the caller keeps, untouched, from
                                       the forward call to the backward call (the library zeroes them at the start of the forward).  With
                                       gemm_split == 2 and batch statistics, the hop's large products then run in the three-MFMA form
-                                      (csrc/gemm_nn2.hip): the words hold the bit patterns of max |X|, max |S|, max |aggr|, the bound of
-                                      relu(bn(h1)), max |y|, and (backward) max |d out|, max |d h1|, max |d K|M|Q|, each left behind by the
-                                      kernel that produces the tensor (X, S of the first hop: one reduction pass each).  In a stack call
+                                      (csrc/gemm_nn2.hip): word QAGNN_HOP_AM_<name> (below) holds the bit pattern of that tensor's maximum, left
+                                      behind by the kernel that produces the tensor (X, S of the first hop: one reduction pass each).  In a stack call
                                       whose hops are chained (hops[l + 1].X == hops[l].y, one shared S) the words of X and S are shared too */
   const uint32_t* x_amax;          /* NULL, or a word that already holds max |X| (bit pattern; e.g. left by qagnn_gelu_dropout_fwd_amax_f32 when it
                                       produced X): the hop then skips its own reduction pass over X.  Likewise s_amax for S.  Read-only, read
@@ -566,6 +565,15 @@ typedef struct qagnn_hop_args {
   const uint32_t* s_amax;
 } qagnn_hop_args;
 #define QAGNN_HOP_AMAX_WORDS 16
+/* the words of qagnn_hop_args.amax that are in use (the rest are spare) */
+#define QAGNN_HOP_AM_X 0     /* max |X| */
+#define QAGNN_HOP_AM_S 1     /* max |S| */
+#define QAGNN_HOP_AM_AGGR 2  /* max |aggr| */
+#define QAGNN_HOP_AM_H1 3    /* the bound (forward-only stack: the maximum) of relu(bn(h1)) */
+#define QAGNN_HOP_AM_Y 4     /* max |y| */
+#define QAGNN_HOP_AM_DOUT 5  /* backward: max |d out| */
+#define QAGNN_HOP_AM_DH1 6   /* backward: max |d h1| */
+#define QAGNN_HOP_AM_DKMQ 7  /* backward: max |d K|M|Q| */
 int64_t qagnn_hop_fwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP);
 int64_t qagnn_hop_bwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP, int32_t SP,
                                       int32_t cls_part_rows /* g->max_chunks + QAGNN_CLS_SLICES * g->C */);

@@ -92,6 +92,7 @@ class qagnn_hop_args(C.Structure):
 
 
 HOP_AMAX_WORDS = 16  # QAGNN_HOP_AMAX_WORDS
+HOP_AM_X, HOP_AM_S, HOP_AM_AGGR, HOP_AM_H1, HOP_AM_Y, HOP_AM_DOUT, HOP_AM_DH1, HOP_AM_DKMQ = range(8)  # QAGNN_HOP_AM_*: the words in use
 
 
 def load_library(path=LIB_PATH):
@@ -344,6 +345,11 @@ class HipGraph:
         T4 = (T + 3) // 4 * 4
         w = self.array('err', 16 + 4 + 2 * T4)[16:]
         return w[4:4 + T], w[4 + T4:4 + T4 + T], w[:1]
+
+    @property
+    def cls_part_rows(self):
+        """rows of the class-partial scratch of the edge backward (qagnn_edge_attn_bwd_f32's cls_part, qagnn_hop_bwd_workspace_elems)"""
+        return self.max_chunks + CLS_SLICES * self.C
 
     @property
     def cls_count(self):
@@ -1143,7 +1149,7 @@ class HipKernels(metaclass=_GuardedMeta):
         assert _ld(dKMQ) == _ld(KMQ) and _ld(dEkEm) == _ld(EkEm), 'edge_attn_bwd: dKMQ / dEkEm are written with the pitches of KMQ / EkEm'
         ga = torch.empty((graph.Ep, 4), dtype=torch.float32, device=dev)
         rs = torch.empty((graph.N, 4), dtype=torch.float32, device=dev)
-        cls_part = torch.empty((graph.max_chunks + CLS_SLICES * graph.C, 2 * DP), dtype=torch.float32, device=dev)
+        cls_part = torch.empty((graph.cls_part_rows, 2 * DP), dtype=torch.float32, device=dev)
         rc = self.lib.qagnn_edge_attn_bwd_f32(C.byref(graph.c), KMQ.data_ptr(), _ld(KMQ), EkEm.data_ptr(), _ld(EkEm), HP,
                                               float(qscale), a.data_ptr(), alpha.data_ptr(), G.data_ptr(), _ld(G),
                                               dKMQ.data_ptr(), dEkEm.data_ptr(), ga.data_ptr(), rs.data_ptr(),
@@ -1223,6 +1229,35 @@ class HipKernels(metaclass=_GuardedMeta):
         return (dWx_t.view(DP, 3 * DP), dWs_t.view(SP, 3 * DP) if SP else None, dTT.view(T, 3 * DP), dEkEm.view(n_cls, 2 * DP),
                 dW1t.view(DP, DP), db1, dbn[DP:], dbn[:DP], dW2t.view(DP, DP), db2)
 
+    def _fwd_ws(self, graph, DP, dev):
+        """a hop's forward workspace (the hops of a stack share one): exactly the library's query"""
+        return torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(graph.N, graph.Ep, DP), dtype=torch.float32, device=dev)
+
+    def _bwd_ws(self, graph, DP, SP, dev):
+        return torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(graph.N, graph.Ep, DP, SP, graph.cls_part_rows), dtype=torch.float32, device=dev)
+
+    def _hop_chain(self, graph, HP, qscale, X, S, ntype, prms, ys, saved, p_amax, x_amax, s_amax, ws, batch_stats, eps, p, seeds, cols, side=False,
+                   runnings=None, shared=False):
+        """The (qagnn_hop_args * k) of a chained stack: hop l reads X (l = 0) or ys[l - 1] and writes ys[l].  saved = (KMQ, aa, rows, stats) with
+        one slot per hop (shared: ONE slot that every hop writes); p_amax: the address of the [k, HOP_AMAX_WORDS] words, or None; x_amax / s_amax:
+        the words X's and S's producers left (ops.amax_lookup: no reduction pass then), or None / empty; ws: the workspace the hops share."""
+        k, N, DP, Ep = len(prms), graph.N, 4 * HP, graph.Ep
+        p_kmq, p_aa, p_rows, p_stats = (t.data_ptr() for t in saved)
+        row_b, p_ws, n_ws = N * DP * 4, ws.data_ptr(), ws.numel()
+        p_x, p_s = (t.data_ptr() if t is not None and t.numel() else None for t in (x_amax, s_amax))
+        hops = (qagnn_hop_args * k)()
+        for l in range(k):
+            h = self._hop_struct(graph, HP, qscale, X if l == 0 else ys[l - 1], S, ntype, prms[l], batch_stats, eps, p, seeds[l] if seeds else 0, True,
+                                 cols, side=side, running=runnings[l] if runnings else None)
+            j = 0 if shared else l
+            self._set_saved(h, p_kmq + j * 3 * row_b, p_aa + 2 * j * Ep * 16, p_rows + 4 * j * row_b, p_stats + j * 5 * DP * 4,
+                            p_amax + l * HOP_AMAX_WORDS * 4 if p_amax else None, Ep, row_b)
+            # (one slot per hop: y is where _set_saved put it; the chain hops[l + 1].X == hops[l].y is what shares the amax words)
+            h.y, h.x_amax, h.s_amax = ys[l].data_ptr(), (p_x if l == 0 else None), p_s
+            h.ws, h.ws_elems = p_ws, n_ws
+            hops[l] = h
+        return hops
+
     def hop_fwd(self, graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, running, cols=-1):
         """-> (y, saved) with saved = (KMQ, aa [2, Ep, 4] = a | alpha, aggr, h1, out, stats [5, DP]); y is `out` when not apply_act."""
         h = self._hop_struct(graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act, cols, running=running)
@@ -1232,7 +1267,7 @@ class HipKernels(metaclass=_GuardedMeta):
         rows = torch.empty((4 if apply_act else 3, N, DP), dtype=torch.float32, device=dev)  # aggr, h1, out (, y)
         stats = torch.empty((5, DP), dtype=torch.float32, device=dev)
         amax = torch.empty(HOP_AMAX_WORDS, dtype=torch.int32, device=dev)  # operand maxima of the three-MFMA form (zeroed by the library)
-        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, graph.Ep, DP), dtype=torch.float32, device=dev)
+        ws = self._fwd_ws(graph, DP, dev)
         self._set_saved(h, KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), graph.Ep, N * DP * 4)
         if not apply_act:
             h.y = None  # (rows has no fourth matrix)
@@ -1262,7 +1297,7 @@ class HipKernels(metaclass=_GuardedMeta):
             dS = dS_acc if dS_acc is not None else torch.empty((N, SP), dtype=torch.float32, device=dev)
             assert dS.shape == (N, SP) and dS.is_contiguous()
             h.dS, h.accumulate_dS = dS.data_ptr(), (1 if dS_acc is not None else 0)
-        ws = torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(N, graph.Ep, DP, SP, graph.max_chunks + CLS_SLICES * graph.C), dtype=torch.float32, device=dev)
+        ws = self._bwd_ws(graph, DP, SP, dev)
         h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
         self._check(self.lib.qagnn_hop_bwd_f32(C.byref(h), self._stream()), 'qagnn_hop_bwd_f32')
         return (dX, dS, *grads)
@@ -1357,26 +1392,12 @@ class HipKernels(metaclass=_GuardedMeta):
         rows = torch.empty((kk, 4, N, DP), dtype=torch.float32, device=dev) if keep else torch.empty((5, N, DP), dtype=torch.float32, device=dev)
         stats = torch.empty((kk, 5, DP), dtype=torch.float32, device=dev)
         amax = torch.empty((k, HOP_AMAX_WORDS), dtype=torch.int32, device=dev)
-        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP), dtype=torch.float32, device=dev)
-        hops = (qagnn_hop_args * k)()
-        x = X
-        p_kmq, p_aa, p_rows, p_stats, p_amax, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), N * DP * 4
-        for l in range(k):
-            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], False, eps, 0.0, 0, True, cols, running=None)
-            j = l if keep else 0
-            self._set_saved(h, p_kmq + j * 3 * row_b, p_aa + 2 * j * Ep * 16, p_rows + 4 * j * row_b, p_stats + j * 5 * DP * 4,
-                            p_amax + l * HOP_AMAX_WORDS * 4, Ep, row_b)
-            y = rows[l, 3] if keep else rows[3 + (l & 1)]  # (shared set: aggr | h1 | out | y even | y odd)
-            h.y = y.data_ptr()
-            if l == 0 and x_amax is not None:
-                h.x_amax = x_amax.data_ptr()
-            if s_amax is not None:
-                h.s_amax = s_amax.data_ptr()
-            h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
-            hops[l] = h
-            x = y
+        ws = self._fwd_ws(graph, DP, dev)
+        ys = [rows[l, 3] if keep else rows[3 + (l & 1)] for l in range(k)]  # (shared set: aggr | h1 | out | y even | y odd)
+        hops = self._hop_chain(graph, HP, qscale, X, S, ntype, prms, ys, (KMQ, aa, rows, stats), amax.data_ptr(), x_amax, s_amax, ws, False, eps, 0.0,
+                               None, cols, shared=not keep)
         self._check(self.lib.qagnn_stack_infer_f32(hops, k, self._stream()), 'qagnn_stack_infer_f32')
-        return (x, amax, (KMQ, aa, rows, stats)) if keep else (x, amax)
+        return (ys[-1], amax, (KMQ, aa, rows, stats)) if keep else (ys[-1], amax)
 
     # -- the whole k-hop stack per call (csrc/hop.hip: qagnn_stack_{fwd,bwd}_f32) -------------------------------------------------------
     def stack_fwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, cols=-1, x_amax=None, s_amax=None):
@@ -1388,24 +1409,13 @@ class HipKernels(metaclass=_GuardedMeta):
         rows = torch.empty((k, 4, N, DP), dtype=torch.float32, device=dev)  # per hop: aggr, h1, out, y
         stats = torch.empty((k, 5, DP), dtype=torch.float32, device=dev)
         amax = torch.empty((k, HOP_AMAX_WORDS), dtype=torch.int32, device=dev)  # one array: the library zeroes it with one launch
-        ws = torch.empty(self.lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP), dtype=torch.float32, device=dev)
-        hops = (qagnn_hop_args * k)()
-        x = X
-        p_kmq, p_aa, p_rows, p_stats, p_amax, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), amax.data_ptr(), N * DP * 4
-        for l in range(k):
-            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], batch_stats, eps, p, seeds[l], True, cols, running=runnings[l])
-            self._set_saved(h, p_kmq + l * 3 * row_b, p_aa + 2 * l * Ep * 16, p_rows + 4 * l * row_b, p_stats + l * 5 * DP * 4,
-                            p_amax + l * HOP_AMAX_WORDS * 4, Ep, row_b)
-            if l == 0 and x_amax is not None:  # max |X| from X's producer (ops.amax_lookup): no reduction pass over the stack input
-                h.x_amax = x_amax.data_ptr()
-            if s_amax is not None:
-                h.s_amax = s_amax.data_ptr()
-            h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
-            hops[l] = h
-            x = rows[l, 3]
+        ws = self._fwd_ws(graph, DP, dev)
+        ys = rows[:, 3].unbind(0)
+        hops = self._hop_chain(graph, HP, qscale, X, S, ntype, prms, ys, (KMQ, aa, rows, stats), amax.data_ptr(), x_amax, s_amax, ws, batch_stats, eps, p,
+                               seeds, cols, runnings=runnings)
         self._check(self.lib.qagnn_stack_fwd_f32(hops, k, self._stream()), 'qagnn_stack_fwd_f32')
         ext = torch.empty(0, dtype=torch.int32, device=dev)
-        return rows[k - 1, 3], (KMQ, aa, rows, stats, amax, x_amax if x_amax is not None else ext, s_amax if s_amax is not None else ext)
+        return ys[k - 1], (KMQ, aa, rows, stats, amax, x_amax if x_amax is not None else ext, s_amax if s_amax is not None else ext)
 
     def stack_bwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, saved, dy, need_dX, need_dS, dX_acc=None, tab_col=-1,
                   overlap=True):
@@ -1427,21 +1437,11 @@ class HipKernels(metaclass=_GuardedMeta):
         if need_dX:
             dX = dX_acc if dX_acc is not None else torch.empty((N, DP), dtype=torch.float32, device=dev)
             assert dX.shape == (N, DP) and dX.is_contiguous()
-        ws = torch.empty(self.lib.qagnn_hop_bwd_workspace_elems(N, Ep, DP, SP, graph.max_chunks + CLS_SLICES * graph.C), dtype=torch.float32, device=dev)
-        hops = (qagnn_hop_args * k)()
-        grads = []
-        p_kmq, p_aa, p_rows, p_stats, row_b = KMQ.data_ptr(), aa.data_ptr(), rows.data_ptr(), stats.data_ptr(), N * DP * 4
-        p_dxs = dxs.data_ptr()
-        for l in range(k):
-            x = X if l == 0 else rows[l - 1, 3]
-            h = self._hop_struct(graph, HP, qscale, x, S, ntype, prms[l], batch_stats, eps, p, seeds[l], True, tab_col, side=overlap)
-            # (h.y = what the forward wrote: the chain hops[l + 1].X == hops[l].y is what shares the amax words)
-            self._set_saved(h, p_kmq + l * 3 * row_b, p_aa + 2 * l * Ep * 16, p_rows + 4 * l * row_b, p_stats + l * 5 * DP * 4,
-                            p_amax + l * HOP_AMAX_WORDS * 4 if p_amax else None, Ep, row_b)
-            if l == 0 and x_amax is not None and x_amax.numel():
-                h.x_amax = x_amax.data_ptr()
-            if s_amax is not None and s_amax.numel():
-                h.s_amax = s_amax.data_ptr()
+        ws = self._bwd_ws(graph, DP, SP, dev)
+        hops = self._hop_chain(graph, HP, qscale, X, S, ntype, prms, rows[:, 3].unbind(0), (KMQ, aa, rows, stats), p_amax, x_amax, s_amax, ws,
+                               batch_stats, eps, p, seeds, tab_col, side=overlap)
+        grads, p_dxs, row_b = [], dxs.data_ptr(), N * DP * 4
+        for l, h in enumerate(hops):
             h.dy = dy.data_ptr() if l == k - 1 else p_dxs + l * row_b
             grads.append(self._carve_grads(h, flat[l * per:(l + 1) * per], sizes, offs, graph.C))
             if l > 0:
@@ -1450,7 +1450,5 @@ class HipKernels(metaclass=_GuardedMeta):
                 h.dX, h.accumulate_dX = dX.data_ptr(), (1 if dX_acc is not None else 0)
             if dS is not None:
                 h.dS, h.accumulate_dS = dS.data_ptr(), (0 if l == k - 1 else 1)  # hop k-1's backward runs first
-            h.ws, h.ws_elems = ws.data_ptr(), ws.numel()
-            hops[l] = h
         self._check(self.lib.qagnn_stack_bwd_f32(hops, k, self._stream()), 'qagnn_stack_bwd_f32')
         return dX, dS, grads

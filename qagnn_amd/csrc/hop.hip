@@ -18,18 +18,50 @@ namespace qagnn {
 static inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 static inline int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
 
-struct Carver {
-  float* p;
-  float* end;
-  float* take(int64_t n) {
-    float* r = p;
-    p += up4(n);
-    return r;
-  }
-  bool ok() const { return p <= end; }
+// rows per tile of the column statistics the first Linear's epilogue leaves (colstat_part: [tiles][3][DP]).  Twins: ST_TILE in elementwise.hip
+// (the launch that folds the tiles), SBM in gemm_split.hip (the block that writes one)
+static inline int hop_stat_tiles(int N) { return cdiv(N, 128); }
+// the widths at which that epilogue exists (twin: nn_validate's cdiv(No, 16) == 13 in gemm_dispatch.hip): there the batch statistics, and with
+// them the bound of relu(bn(h1)), ride on the first Linear, so only there does a training hop know every maximum its backward needs
+static inline bool hop_stat_width(int DP) { return DP > 192 && DP <= 208; }
+// scratch for the packed B image of a hop's NN products (qagnn_gemm_nn_split_ws_f32), in floats: sized for the projection
+// [DP | <= DP] -> 3 DP, the largest of them; one buffer, the products of a hop are in order on the main stream
+static int64_t hop_pack_elems(int DP) { return up4((qagnn_gemm_nn_pack_bytes(3 * DP, DP, DP) + 3) / 4); }
+// rows of the edge backward's class partials (qagnn_hip.h: qagnn_edge_attn_bwd_f32's cls_part; HipGraph.cls_part_rows is the binding's twin)
+static inline int hop_cls_part_rows(const qagnn_graph* g) { return QAGNN_CLS_SLICES * g->C + g->max_chunks; }
+
+// The workspace of each direction, stated once: the regions in order (members are initialised in the order they are declared), each padded to 4
+// floats.  base == nullptr: only the sizes and `total` mean anything (the size queries, check_hop); else the regions are carved from base.
+struct HopWs {
+  float* base;
+  int64_t total = 0;  // grows region by region
+  float* take(int64_t n) { const int64_t o = total; total += up4(n); return base ? base + o : nullptr; }
+};
+struct HopFwdWs : HopWs {
+  const int64_t N, Ep, DP, ampart_elems = max64(N, gelu_amax_scratch_elems(N * DP));
+  float* const score = take(Ep * 4);
+  float* const crws = take(max64(qagnn_colreduce_workspace_elems(N, DP, 1), hop_stat_tiles(N) * 3 * DP));  // column-reduction / statistics partials
+  float* const pkws = take(hop_pack_elems(DP));
+  float* const ampart = take(ampart_elems);  // per-node / per-block maxima (qagnn_hop_args.amax)
+  static HopFwdWs layout(int N, int Ep, int DP, int /*SP*/, int /*cls_part_rows*/, float* base) { return {{base}, N, Ep, DP}; }
+};
+struct HopBwdWs : HopWs {
+  const int64_t N, Ep, DP, SP, cls_part_rows;
+  struct { float *dout, *dh1, *dkmq; } set[2] = {{take(N * DP), take(N * DP), take(N * 3 * DP)},  // what the weight-gradient stream reads,
+                                                 {take(N * DP), take(N * DP), take(N * 3 * DP)}};  // twice: it may lag by a whole hop
+  float* const drelu = take(N * DP);  // d relu(bn(h1)), then d aggr (main stream only)
+  float* const gab = take(Ep * 4);
+  float* const rs = take(N * 4);
+  float* const cls_part = take(cls_part_rows * 2 * DP);
+  float* const tnws = take(max64(max64(qagnn_gemm_tn_workspace_elems(N, DP, DP), qagnn_gemm_tn_workspace_elems(N, DP, 3 * DP)),
+                                 SP > 0 ? qagnn_gemm_tn_workspace_elems(N, DP + SP, 3 * DP) : 0));  // split-K partials: weight-gradient stream only
+  float* const crws = take(qagnn_colreduce_workspace_elems(N, 3 * DP, 4));  // column-reduction partials: main stream only
+  float* const pkws = take(hop_pack_elems(DP));  // packed B images of the data-gradient products: main stream only
+  float* const ampart = take(max64(3 * N, gelu_amax_scratch_elems(N * DP)));
+  static HopBwdWs layout(int N, int Ep, int DP, int SP, int cls_part_rows, float* base) { return {{base}, N, Ep, DP, SP, cls_part_rows}; }
 };
 
-static int check_hop(const qagnn_hop_args* h, const char* who) {
+static int check_hop(const qagnn_hop_args* h, const char* who, bool bwd = false) {  // bwd: the entry point runs the backward
   QAGNN_REQUIRE(h && h->g, QAGNN_EINVAL, "%s: null argument block / graph", who);
   QAGNN_REQUIRE(h->N == h->g->N && h->N > 0, QAGNN_EINVAL, "%s: N=%d does not match the graph (N=%d)", who, h->N, h->g->N);
   QAGNN_REQUIRE(h->HP > 0 && h->HP % 4 == 0 && h->DP == 4 * h->HP, QAGNN_EINVAL, "%s: DP=%d must be 4*HP (HP=%d)", who, h->DP, h->HP);
@@ -45,34 +77,40 @@ static int check_hop(const qagnn_hop_args* h, const char* who) {
   QAGNN_REQUIRE(h->batch_stats || (h->run_mean_p && h->run_var_p), QAGNN_EINVAL, "%s: running statistics missing", who);
   QAGNN_REQUIRE(!h->apply_act || h->y, QAGNN_EINVAL, "%s: apply_act without an output buffer y", who);
   QAGNN_REQUIRE(h->ws, QAGNN_EINVAL, "%s: null workspace", who);
+  const int64_t need = bwd ? HopBwdWs::layout(h->N, h->g->Ep, h->DP, h->SP, hop_cls_part_rows(h->g), nullptr).total
+                           : HopFwdWs::layout(h->N, h->g->Ep, h->DP, h->SP, 0, nullptr).total;
+  QAGNN_REQUIRE(h->ws_elems >= need, QAGNN_EINVAL, "%s: workspace of %lld floats is too small", who, (long long)h->ws_elems);
   return QAGNN_OK;
 }
 
 // ---- the three-MFMA GEMM form inside a hop (qagnn_hop_args.amax, gemm_split == 2; arithmetic: gemm_nn2.hip's header) -------------
-// Word layout of a hop's amax block; X and S may live in another hop's block (a chained stack: the previous hop's y IS this hop's X)
-enum { AM_X = 0, AM_S = 1, AM_AGGR = 2, AM_H1 = 3, AM_Y = 4, AM_DOUT = 5, AM_DH1 = 6, AM_DKMQ = 7 };
+// Words of a hop's amax block: QAGNN_HOP_AM_*; X and S may live in another hop's block (a chained stack: the previous hop's y IS this hop's X)
 struct HopAmax {
   bool on;          // this hop runs the form
   uint32_t* x;      // max |X|   (written by the previous hop's GELU / dropout, or by a reduction pass at the start of the call)
   uint32_t* s;      // max |S|
   uint32_t* y;      // where this hop's GELU / dropout leaves max |y|
   uint32_t* own;    // the hop's own block
-  bool h1_pass;     // AM_H1 from a pass over h1 (the forward-only stack: running statistics give no bound)
+  bool h1_pass;     // QAGNN_HOP_AM_H1 from a pass over h1 (the forward-only stack: running statistics give no bound)
 };
 // The form needs batch statistics (the bound of relu(bn(h1)) comes from them) and pays where products take packed B images
 static bool hop_h2(const qagnn_hop_args* h, bool infer = false) {
   // infer (qagnn_stack_infer_f32): running statistics -- max relu(bn(h1)) is then measured, not bounded (HopAmax.h1_pass)
   return h->gemm_split >= 2 && h->amax != nullptr && (infer ? !h->batch_stats : h->batch_stats != 0) && nn_rows_packed(h->N);
 }
-// gemm_split == 3: the reduced-precision form (one fp16 MFMA per product) wherever 2 would take three
-static int hop_pieces(const qagnn_hop_args* h) { return h->gemm_split == 3 ? 1 : 0; }
+// the piece count of the scaled forms: two (three MFMAs per product), or with gemm_split == 3 one (the reduced-precision form, one fp16 MFMA)
+static int hop_pieces(const qagnn_hop_args* h) { return h->gemm_split == 3 ? 1 : 2; }
+// an NN product of the hop in a scaled form: the maxima of its A operands, and the piece count as qagnn_gemm_nn_args takes it (0: its default, two)
+static void nn_scaled(const qagnn_hop_args* h, qagnn_gemm_nn_args* a, const uint32_t* am1, const uint32_t* am2 = nullptr) {
+  a->a_amax1 = am1, a->a_amax2 = am2, a->pieces = hop_pieces(h) == 1 ? 1 : 0;
+}
 static HopAmax hop_amax_single(const qagnn_hop_args* h, bool infer = false) {
   HopAmax m{hop_h2(h, infer), nullptr, nullptr, nullptr, h->amax, false};
-  m.h1_pass = m.on && infer && h->DP > 192 && h->DP <= 208;  // (the widths at which the training forward takes the bound: hop_fwd_one)
+  m.h1_pass = m.on && infer && hop_stat_width(h->DP);  // (the widths at which the training forward takes the bound: hop_fwd_one)
   if (m.on) {  // (x_amax / s_amax: words the caller's producers filled; read-only here)
-    m.x = h->x_amax ? const_cast<uint32_t*>(h->x_amax) : h->amax + AM_X;
-    m.s = h->s_amax ? const_cast<uint32_t*>(h->s_amax) : h->amax + AM_S;
-    m.y = h->amax + AM_Y;
+    m.x = h->x_amax ? const_cast<uint32_t*>(h->x_amax) : h->amax + QAGNN_HOP_AM_X;
+    m.s = h->s_amax ? const_cast<uint32_t*>(h->s_amax) : h->amax + QAGNN_HOP_AM_S;
+    m.y = h->amax + QAGNN_HOP_AM_Y;
   }
   return m;
 }
@@ -80,9 +118,9 @@ static HopAmax hop_amax_single(const qagnn_hop_args* h, bool infer = false) {
 static HopAmax hop_amax_stack(const qagnn_hop_args* hops, int k, int l, bool infer = false) {
   HopAmax m = hop_amax_single(&hops[l], infer);
   if (!m.on) return m;
-  if (l > 0 && hop_h2(&hops[l - 1], infer) && hops[l].X == hops[l - 1].y && hops[l - 1].apply_act && !hops[l].x_amax) m.x = hops[l - 1].amax + AM_Y;
+  if (l > 0 && hop_h2(&hops[l - 1], infer) && hops[l].X == hops[l - 1].y && hops[l - 1].apply_act && !hops[l].x_amax) m.x = hops[l - 1].amax + QAGNN_HOP_AM_Y;
   if (l > 0 && hop_h2(&hops[0], infer) && hops[l].S == hops[0].S && hops[l].SP == hops[0].SP && !hops[l].s_amax)
-    m.s = hops[0].s_amax ? const_cast<uint32_t*>(hops[0].s_amax) : hops[0].amax + AM_S;
+    m.s = hops[0].s_amax ? const_cast<uint32_t*>(hops[0].s_amax) : hops[0].amax + QAGNN_HOP_AM_S;
   return m;
 }
 
@@ -96,20 +134,15 @@ using namespace qagnn;
     if (rc__ != QAGNN_OK) return rc__; \
   } while (0)
 
-// scratch for the packed B image of a hop's NN products (qagnn_gemm_nn_split_ws_f32), in floats: sized for the projection
-// [DP | <= DP] -> 3 DP, the largest of them; one buffer, the products of a hop are in order on the main stream
-static int64_t hop_pack_elems(int DP) { return up4((qagnn_gemm_nn_pack_bytes(3 * DP, DP, DP) + 3) / 4); }
-
-extern "C" int64_t qagnn_hop_fwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP) {
-  return up4((int64_t)Ep * 4) + up4(max64(qagnn_colreduce_workspace_elems(N, DP, 1), (int64_t)cdiv(N, 128) * 3 * DP)) + hop_pack_elems(DP) +
-         up4(max64(N, gelu_amax_scratch_elems((int64_t)N * DP)));  // (+ per-node / per-block maxima: qagnn_hop_args.amax)
+extern "C" int64_t qagnn_hop_fwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP) { return HopFwdWs::layout(N, Ep, DP, 0, 0, nullptr).total; }
+extern "C" int64_t qagnn_hop_bwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP, int32_t SP, int32_t cls_part_rows) {
+  return HopBwdWs::layout(N, Ep, DP, SP, cls_part_rows, nullptr).total;
 }
 
 // NN product through the kernel family the caller asked for (qagnn_hop_args.gemm_split): the bf16-split kernel takes B in its
 // [No][K] layout, which the hop holds for every weight (W and W^T both arrive packed)
-static int hop_nn(const qagnn_hop_args* h, const qagnn_gemm_nn_args* a, const float* B1n, int ldn1, const float* B2n, int ldn2,
-                  float* pkws, int64_t pk_elems, qagnn_stream_t stream) {
-  return gemm_nn(NnProduct{a, h->gemm_split != 0, B1n, ldn1, B2n, ldn2, pkws, pk_elems * 4}, (hipStream_t)stream);
+static int hop_nn(const qagnn_hop_args* h, const qagnn_gemm_nn_args* a, const float* B1n, int ldn1, const float* B2n, int ldn2, float* pkws, qagnn_stream_t stream) {
+  return gemm_nn(NnProduct{a, h->gemm_split != 0, B1n, ldn1, B2n, ldn2, pkws, hop_pack_elems(h->DP) * 4}, (hipStream_t)stream);
 }
 // weight gradient C = [A1 | A2]^T B over the hop's N rows (A2 == nullptr: one operand); am_*: the operands' maxima -- the scaled form
 // the hop asks for where all of them are known (am_b is, in a backward that runs the form), the six-MFMA form otherwise
@@ -117,22 +150,16 @@ static int hop_nn(const qagnn_hop_args* h, const qagnn_gemm_nn_args* a, const fl
 static int hop_tn(const qagnn_hop_args* h, const float* A1, int Ka1, const float* A2, int Ka2, const float* B, int No, float* C, const float* sc,
                   const float* sh, const uint32_t* am_a1, const uint32_t* am_a2, const uint32_t* am_b, float* tnws, qagnn_stream_t stream,
                   const qagnn_graph* g = nullptr) {
-  TnProduct p = tn_product(A1, Ka1, Ka1, A2, Ka2, Ka2, B, No, C, No, h->N, No, sc, sh, tnws, am_a1, am_a2, am_b, h->gemm_split == 3 ? 1 : 2);
+  TnProduct p = tn_product(A1, Ka1, Ka1, A2, Ka2, Ka2, B, No, C, No, h->N, No, sc, sh, tnws, am_a1, am_a2, am_b, hop_pieces(h));
   p.g = g;
   return gemm_tn(p, (hipStream_t)stream);
 }
 
 // x_ready / s_ready: the words of X / S already hold this call's maxima (an earlier hop of the stack produced them)
 static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready, bool s_ready, qagnn_stream_t stream) {
-  // (h has passed check_hop: both entry points validate every hop before the first enqueue)
   const int N = h->N, DP = h->DP, SP = h->SP, Ep = h->g->Ep;
-  Carver w{h->ws, h->ws + h->ws_elems};
-  float* score = w.take((int64_t)Ep * 4);
-  float* crws = w.take(max64(qagnn_colreduce_workspace_elems(N, DP, 1), (int64_t)cdiv(N, 128) * 3 * DP));
-  const int64_t pk_elems = hop_pack_elems(DP);
-  float* pkws = w.take(pk_elems);
-  float* ampart = w.take(max64(N, gelu_amax_scratch_elems((int64_t)N * DP)));
-  QAGNN_REQUIRE(w.ok(), QAGNN_EINVAL, "hop_fwd: workspace of %lld floats is too small", (long long)h->ws_elems);
+  // (h has passed check_hop, the workspace size included: both entry points validate every hop before the first enqueue)
+  const HopFwdWs w = HopFwdWs::layout(N, Ep, DP, SP, 0, h->ws);
   float* mean = h->stats, *var = h->stats + DP, *invstd = h->stats + 2 * DP, *scale = h->stats + 3 * DP, *shift = h->stats + 4 * DP;
 
   if (am.on) {  // operand maxima nobody left behind: one reduction pass each
@@ -145,35 +172,35 @@ static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready,
   if (SP > 0) { ga.A2 = h->S; ga.lda2 = SP; ga.K2 = SP; ga.B2 = h->Ws_t; ga.ldb2 = 3 * DP; }
   ga.C = h->KMQ; ga.ldc = 3 * DP; ga.M = N; ga.No = 3 * DP;
   ga.rowtab = h->TT; ga.ldt = 3 * DP; ga.rowidx = h->ntype;
-  if (am.on) { ga.a_amax1 = am.x; ga.a_amax2 = SP > 0 ? am.s : nullptr; ga.pieces = hop_pieces(h); }
-  HOP_TRY(hop_nn(h, &ga, h->Wx, DP, SP > 0 ? h->Ws : nullptr, SP, pkws, pk_elems, stream));
+  if (am.on) nn_scaled(h, &ga, am.x, SP > 0 ? am.s : nullptr);
+  HOP_TRY(hop_nn(h, &ga, h->Wx, DP, SP > 0 ? h->Ws : nullptr, SP, w.pkws, stream));
   // attention + aggregation (:442, 455-484)
-  HOP_TRY(launch_edge_attn_fwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, score, h->a, h->alpha, h->aggr, DP,
-                               am.on ? ampart : nullptr, (hipStream_t)stream));
-  if (am.on) HOP_TRY(launch_amax_reduce(ampart, N, am.own + AM_AGGR, (hipStream_t)stream));
+  HOP_TRY(launch_edge_attn_fwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, w.score, h->a, h->alpha, h->aggr, DP,
+                               am.on ? w.ampart : nullptr, (hipStream_t)stream));
+  if (am.on) HOP_TRY(launch_amax_reduce(w.ampart, N, am.own + QAGNN_HOP_AM_AGGR, (hipStream_t)stream));
   // mlp: Linear -> BatchNorm1d -> ReLU -> Linear (:443, 408); BN + ReLU are folded into the second GEMM's operand load
   qagnn_gemm_nn_args g1 = {};
   g1.A1 = h->aggr; g1.lda1 = DP; g1.K1 = DP; g1.B1 = h->W1t; g1.ldb1 = DP; g1.C = h->h1; g1.ldc = DP; g1.M = N; g1.No = DP; g1.bias = h->b1;
   // batch statistics as a by-product of this GEMM's epilogue where the split kernel can provide them (same rule as ops.GatMlpFn)
-  const bool fused_stats = h->batch_stats && h->gemm_split && DP > 192 && DP <= 208;
-  if (fused_stats) g1.colstat_part = crws;
-  if (am.on) { g1.a_amax1 = am.own + AM_AGGR; g1.pieces = hop_pieces(h); }
-  HOP_TRY(hop_nn(h, &g1, h->W1, DP, nullptr, 0, pkws, pk_elems, stream));
+  const bool fused_stats = h->batch_stats && h->gemm_split && hop_stat_width(DP);
+  if (fused_stats) g1.colstat_part = w.crws;
+  if (am.on) nn_scaled(h, &g1, am.own + QAGNN_HOP_AM_AGGR);
+  HOP_TRY(hop_nn(h, &g1, h->W1, DP, nullptr, 0, w.pkws, stream));
   const double Rd = (double)N;
   const float unbias = (float)(Rd / (Rd - 1.0 > 1.0 ? Rd - 1.0 : 1.0));
   const bool h1_bound = am.on && fused_stats;  // (the bound of relu(bn(h1)) rides on the statistics launch)
   if (fused_stats) {
     QAGNN_REQUIRE(!h->run_mean || (h->run_var && h->d > 0 && h->d % 4 == 0 && h->d <= DP), QAGNN_EINVAL, "hop_fwd: running-stat arguments");
-    HOP_TRY(launch_bn_stats_finalize(crws, cdiv(N, 128), N, DP, h->gamma, h->beta, h->eps, h->stats, h->run_mean, h->run_var, h->num_batches_tracked,
-                                     h->d, h->momentum, unbias, h->ones_col, h1_bound ? am.own + AM_H1 : nullptr, (hipStream_t)stream));
+    HOP_TRY(launch_bn_stats_finalize(w.crws, hop_stat_tiles(N), N, DP, h->gamma, h->beta, h->eps, h->stats, h->run_mean, h->run_var, h->num_batches_tracked,
+                                     h->d, h->momentum, unbias, h->ones_col, h1_bound ? am.own + QAGNN_HOP_AM_H1 : nullptr, (hipStream_t)stream));
   } else {
     const float* mean_u = mean;
     const float* var_u = var;
     if (h->batch_stats) {
       const float inv_rows = (float)(1.0 / (double)N);  // rounded like the composed path's Python double -> float
-      HOP_TRY(qagnn_colreduce_f32(0, h->h1, DP, nullptr, DP, N, DP, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, inv_rows, mean, crws,
+      HOP_TRY(qagnn_colreduce_f32(0, h->h1, DP, nullptr, DP, N, DP, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, inv_rows, mean, w.crws,
                                   stream));
-      HOP_TRY(qagnn_colreduce_f32(1, h->h1, DP, nullptr, DP, N, DP, nullptr, 1, mean, nullptr, nullptr, nullptr, nullptr, inv_rows, var, crws,
+      HOP_TRY(qagnn_colreduce_f32(1, h->h1, DP, nullptr, DP, N, DP, nullptr, 1, mean, nullptr, nullptr, nullptr, nullptr, inv_rows, var, w.crws,
                                   stream));
     } else {
       mean_u = h->run_mean_p;
@@ -185,16 +212,16 @@ static int hop_fwd_one(const qagnn_hop_args* h, const HopAmax& am, bool x_ready,
   // the true maximum of relu(bn(h1)): one read of h1 (infer.hip); its partials lie where the edge kernel's were folded from (they fit:
   // qagnn_stack_infer_f32 checks it on the host)
   if (am.h1_pass) {
-    HOP_TRY(launch_bn_relu_absmax(h->h1, DP, N, DP, scale, shift, am.own + AM_H1, ampart, (hipStream_t)stream));
+    HOP_TRY(launch_bn_relu_absmax(h->h1, DP, N, DP, scale, shift, am.own + QAGNN_HOP_AM_H1, w.ampart, (hipStream_t)stream));
   }
   qagnn_gemm_nn_args g2 = {};
   g2.A1 = h->h1; g2.lda1 = DP; g2.K1 = DP; g2.B1 = h->W2t; g2.ldb1 = DP; g2.C = h->out; g2.ldc = DP; g2.M = N; g2.No = DP; g2.bias = h->b2;
   g2.a_scale = scale; g2.a_shift = shift;
-  if (h1_bound || am.h1_pass) { g2.a_amax1 = am.own + AM_H1; g2.pieces = hop_pieces(h); }
-  HOP_TRY(hop_nn(h, &g2, h->W2, DP, nullptr, 0, pkws, pk_elems, stream));
+  if (h1_bound || am.h1_pass) nn_scaled(h, &g2, am.own + QAGNN_HOP_AM_H1);
+  HOP_TRY(hop_nn(h, &g2, h->W2, DP, nullptr, 0, w.pkws, stream));
   if (h->apply_act) {  // X' = dropout(GELU(out))  (:48-49)
     QAGNN_REQUIRE(h->p_drop >= 0.f && h->p_drop < 1.f, QAGNN_EINVAL, "hop_fwd: p=%f", h->p_drop);
-    HOP_TRY(launch_gelu_dropout(h->out, nullptr, h->y, (int64_t)N * DP, h->p_drop, h->seed, am.on ? am.y : nullptr, ampart, (hipStream_t)stream));
+    HOP_TRY(launch_gelu_dropout(h->out, nullptr, h->y, (int64_t)N * DP, h->p_drop, h->seed, am.on ? am.y : nullptr, w.ampart, (hipStream_t)stream));
   }
   return QAGNN_OK;
 }
@@ -205,15 +232,6 @@ extern "C" int qagnn_hop_fwd_f32(const qagnn_hop_args* h, qagnn_stream_t stream)
   const HopAmax am = hop_amax_single(h);
   if (am.on) HOP_TRY(qagnn_zero_words(h->amax, QAGNN_HOP_AMAX_WORDS, stream));
   return hop_fwd_one(h, am, h->x_amax != nullptr, h->s_amax != nullptr, stream);
-}
-
-extern "C" int64_t qagnn_hop_bwd_workspace_elems(int32_t N, int32_t Ep, int32_t DP, int32_t SP, int32_t cls_part_rows) {
-  int64_t tn = max64(qagnn_gemm_tn_workspace_elems(N, DP, DP), qagnn_gemm_tn_workspace_elems(N, DP, 3 * DP));
-  if (SP > 0) tn = max64(tn, qagnn_gemm_tn_workspace_elems(N, DP + SP, 3 * DP));
-  // two sets of the buffers the weight-gradient stream reads (d out, d h1, d K|M|Q) + what the main stream keeps to itself
-  return 2 * (2 * up4((int64_t)N * DP) + up4((int64_t)N * 3 * DP)) + up4((int64_t)N * DP) + up4((int64_t)Ep * 4) + up4((int64_t)N * 4) +
-         up4((int64_t)cls_part_rows * 2 * DP) + up4(tn) + up4(qagnn_colreduce_workspace_elems(N, 3 * DP, 4)) + hop_pack_elems(DP) +
-         up4(max64((int64_t)3 * N, gelu_amax_scratch_elems((int64_t)N * DP)));  // (+ per-node / per-block maxima)
 }
 
 namespace qagnn {
@@ -271,28 +289,8 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
                 "hop_bwd: null gradient pointer");
   QAGNN_REQUIRE(h->SP == 0 || h->dWs_t, QAGNN_EINVAL, "hop_bwd: dWs_t missing");
   const int N = h->N, DP = h->DP, SP = h->SP, Ep = h->g->Ep;
-  Carver w{h->ws, h->ws + h->ws_elems};
-  float *bufA2[2], *bufC2[2], *dKMQ2[2];
-  for (int i = 0; i < 2; ++i) {
-    bufA2[i] = w.take((int64_t)N * DP);
-    bufC2[i] = w.take((int64_t)N * DP);
-    dKMQ2[i] = w.take((int64_t)N * 3 * DP);
-  }
-  float* bufA = bufA2[set];  // d out
-  float* bufC = bufC2[set];  // d h1
-  float* dKMQ = dKMQ2[set];
-  float* bufB = w.take((int64_t)N * DP);  // d relu(bn(h1)), then d aggr (main stream only)
-  float* gab = w.take((int64_t)Ep * 4);
-  float* rs = w.take((int64_t)N * 4);
-  float* cls_part = w.take(((int64_t)h->g->max_chunks + (int64_t)QAGNN_CLS_SLICES * h->g->C) * 2 * DP);
-  int64_t tn = max64(qagnn_gemm_tn_workspace_elems(N, DP, DP), qagnn_gemm_tn_workspace_elems(N, DP, 3 * DP));
-  if (SP > 0) tn = max64(tn, qagnn_gemm_tn_workspace_elems(N, DP + SP, 3 * DP));
-  float* tnws = w.take(tn);  // split-K partials: used by the weight-gradient products only, which are in order on one stream
-  float* crws = w.take(qagnn_colreduce_workspace_elems(N, 3 * DP, 4));  // column-reduction partials: main stream only
-  const int64_t pk_elems = hop_pack_elems(DP);
-  float* pkws = w.take(pk_elems);  // packed B images of the data-gradient products: main stream only
-  float* ampart = w.take(max64((int64_t)3 * N, gelu_amax_scratch_elems((int64_t)N * DP)));
-  QAGNN_REQUIRE(w.ok(), QAGNN_EINVAL, "hop_bwd: workspace of %lld floats is too small", (long long)h->ws_elems);
+  const HopBwdWs w = HopBwdWs::layout(N, Ep, DP, SP, hop_cls_part_rows(h->g), h->ws);  // (it fits: check_hop)
+  float* const bufA = w.set[set].dout, *const bufC = w.set[set].dh1, *const dKMQ = w.set[set].dkmq, *const bufB = w.drelu;
   const float* mean = h->batch_stats ? h->stats : h->run_mean_p;
   const float* invstd = h->stats + 2 * DP, *scale = h->stats + 3 * DP, *shift = h->stats + 4 * DP;
   const qagnn_stream_t stream = (qagnn_stream_t)ss->main;
@@ -301,20 +299,20 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   // GELU + dropout backward
   const float* dout = h->dy;
   // (the three-MFMA form in the backward needs every maximum the forward left: the same condition, and h1's bound)
-  const bool h2 = am.on && DP > 192 && DP <= 208;
-  uint32_t* const w_dout = h2 ? am.own + AM_DOUT : nullptr, *const w_dh1 = h2 ? am.own + AM_DH1 : nullptr, *const w_dkmq = h2 ? am.own + AM_DKMQ : nullptr;
-  const uint32_t* const w_h1 = h2 ? am.own + AM_H1 : nullptr, *const w_aggr = h2 ? am.own + AM_AGGR : nullptr;
+  const bool h2 = am.on && hop_stat_width(DP);
+  uint32_t* const w_dout = h2 ? am.own + QAGNN_HOP_AM_DOUT : nullptr, *const w_dh1 = h2 ? am.own + QAGNN_HOP_AM_DH1 : nullptr, *const w_dkmq = h2 ? am.own + QAGNN_HOP_AM_DKMQ : nullptr;
+  const uint32_t* const w_h1 = h2 ? am.own + QAGNN_HOP_AM_H1 : nullptr, *const w_aggr = h2 ? am.own + QAGNN_HOP_AM_AGGR : nullptr;
   if (h->apply_act) {
-    HOP_TRY(launch_gelu_dropout(h->out, h->dy, bufA, (int64_t)N * DP, h->p_drop, h->seed, w_dout, ampart, (hipStream_t)stream));
+    HOP_TRY(launch_gelu_dropout(h->out, h->dy, bufA, (int64_t)N * DP, h->p_drop, h->seed, w_dout, w.ampart, (hipStream_t)stream));
     dout = bufA;
   } else if (h2) {
     HOP_TRY(qagnn_absmax_f32(dout, (int64_t)N * DP, w_dout, stream));
   }
   if (h->ones_col < 0)
-    HOP_TRY(qagnn_colreduce_f32(0, dout, DP, nullptr, DP, N, DP, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, h->db2, crws, stream));
+    HOP_TRY(qagnn_colreduce_f32(0, dout, DP, nullptr, DP, N, DP, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, h->db2, w.crws, stream));
   // second Linear: dW2^T = relu(bn(h1))^T dout, d r = dout W2
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
-  HOP_TRY(hop_tn(h, h->h1, DP, nullptr, 0, dout, DP, h->dW2t, scale, shift, w_h1, nullptr, w_dout, tnws, wstream));
+  HOP_TRY(hop_tn(h, h->h1, DP, nullptr, 0, dout, DP, h->dW2t, scale, shift, w_h1, nullptr, w_dout, w.tnws, wstream));
   // relu(bn(h1)) carries a column of ones there: that row of the weight gradient is the bias gradient (no copy when the caller's db2 IS
   // that row)
   if (h->ones_col >= 0 && h->db2 != h->dW2t + (int64_t)h->ones_col * DP) {
@@ -323,29 +321,29 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   }
   qagnn_gemm_nn_args gr = {};
   gr.A1 = dout; gr.lda1 = DP; gr.K1 = DP; gr.B1 = h->W2; gr.ldb1 = DP; gr.C = bufB; gr.ldc = DP; gr.M = N; gr.No = DP;
-  gr.a_amax1 = w_dout; gr.pieces = hop_pieces(h);
-  HOP_TRY(hop_nn(h, &gr, h->W2t, DP, nullptr, 0, pkws, pk_elems, stream));
+  nn_scaled(h, &gr, w_dout);
+  HOP_TRY(hop_nn(h, &gr, h->W2t, DP, nullptr, 0, w.pkws, stream));
   // BatchNorm + ReLU backward: dbn[0] = d beta, dbn[1] = d gamma, then d h1
-  HOP_TRY(qagnn_colreduce_f32(2, bufB, DP, h->h1, DP, N, DP, nullptr, 1, mean, invstd, scale, shift, nullptr, 1.0f, h->dbn, crws, stream));
+  HOP_TRY(qagnn_colreduce_f32(2, bufB, DP, h->h1, DP, N, DP, nullptr, 1, mean, invstd, scale, shift, nullptr, 1.0f, h->dbn, w.crws, stream));
   HOP_TRY(launch_bn_relu_bwd_colsum(bufB, h->h1, bufC, DP, N, DP, mean, invstd, scale, shift, h->gamma, h->dbn, h->dbn + DP,
-                                    h->batch_stats ? (float)(1.0 / (double)N) : 0.f, nullptr, h->db1, crws, w_dh1, (hipStream_t)stream));
+                                    h->batch_stats ? (float)(1.0 / (double)N) : 0.f, nullptr, h->db1, w.crws, w_dh1, (hipStream_t)stream));
   // first Linear (db1 = colsum(d h1) came out of the pass above)
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
-  HOP_TRY(hop_tn(h, h->aggr, DP, nullptr, 0, bufC, DP, h->dW1t, nullptr, nullptr, w_aggr, nullptr, w_dh1, tnws, wstream));
+  HOP_TRY(hop_tn(h, h->aggr, DP, nullptr, 0, bufC, DP, h->dW1t, nullptr, nullptr, w_aggr, nullptr, w_dh1, w.tnws, wstream));
   qagnn_gemm_nn_args gg = {};
   gg.A1 = bufC; gg.lda1 = DP; gg.K1 = DP; gg.B1 = h->W1; gg.ldb1 = DP; gg.C = bufB; gg.ldc = DP; gg.M = N; gg.No = DP;
-  gg.a_amax1 = w_dh1; gg.pieces = hop_pieces(h);
-  HOP_TRY(hop_nn(h, &gg, h->W1t, DP, nullptr, 0, pkws, pk_elems, stream));
+  nn_scaled(h, &gg, w_dh1);
+  HOP_TRY(hop_nn(h, &gg, h->W1t, DP, nullptr, 0, w.pkws, stream));
   // attention backward
-  HOP_TRY(launch_edge_attn_bwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, h->a, h->alpha, bufB, DP, dKMQ, h->dEkEm, gab, rs, cls_part,
-                               h2 ? ampart : nullptr, w_dkmq, (hipStream_t)stream));
+  HOP_TRY(launch_edge_attn_bwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, h->a, h->alpha, bufB, DP, dKMQ, h->dEkEm, w.gab, w.rs, w.cls_part,
+                               h2 ? w.ampart : nullptr, w_dkmq, (hipStream_t)stream));
   // projection: weight gradients, node-type-table gradient, data gradients
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
   if (SP > 0 && h->dWs_t == h->dWx_t + (int64_t)DP * 3 * DP) {  // the two gradients are one [DP + SP, 3 DP] matrix: one product
-    HOP_TRY(hop_tn(h, h->X, DP, h->S, SP, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, am.s, w_dkmq, tnws, wstream, h->g));
+    HOP_TRY(hop_tn(h, h->X, DP, h->S, SP, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, am.s, w_dkmq, w.tnws, wstream, h->g));
   } else {
-    HOP_TRY(hop_tn(h, h->X, DP, nullptr, 0, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, nullptr, w_dkmq, tnws, wstream));
-    if (SP > 0) HOP_TRY(hop_tn(h, h->S, SP, nullptr, 0, dKMQ, 3 * DP, h->dWs_t, nullptr, nullptr, am.s, nullptr, w_dkmq, tnws, wstream));
+    HOP_TRY(hop_tn(h, h->X, DP, nullptr, 0, dKMQ, 3 * DP, h->dWx_t, nullptr, nullptr, am.x, nullptr, w_dkmq, w.tnws, wstream));
+    if (SP > 0) HOP_TRY(hop_tn(h, h->S, SP, nullptr, 0, dKMQ, 3 * DP, h->dWs_t, nullptr, nullptr, am.s, nullptr, w_dkmq, w.tnws, wstream));
   }
   if (SP > 0 && h->tab_col >= 0) {
     // the type indicators ride in S's padding columns: their rows of dWs_t ARE the type-table gradient
@@ -357,7 +355,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
     }
   } else {
     HOP_TRY(qagnn_colreduce_f32(0, dKMQ, 3 * DP, nullptr, 3 * DP, N, 3 * DP, h->ntype, h->T, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, h->dTT,
-                                crws, stream));
+                                w.crws, stream));
   }
   if (ss->side) {  // the side stream is done with this buffer set (and with everything queued on it before) once this event fires
     *done = ss->take();
@@ -368,15 +366,15 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
     qagnn_gemm_nn_args gx = {};
     gx.A1 = dKMQ; gx.lda1 = 3 * DP; gx.K1 = 3 * DP; gx.B1 = h->Wx; gx.ldb1 = DP; gx.C = h->dX; gx.ldc = DP; gx.M = N; gx.No = DP;
     gx.accumulate = h->accumulate_dX;
-    gx.a_amax1 = w_dkmq; gx.pieces = hop_pieces(h);
-    HOP_TRY(hop_nn(h, &gx, h->Wx_t, 3 * DP, nullptr, 0, pkws, pk_elems, stream));
+    nn_scaled(h, &gx, w_dkmq);
+    HOP_TRY(hop_nn(h, &gx, h->Wx_t, 3 * DP, nullptr, 0, w.pkws, stream));
   }
   if (SP > 0 && h->dS) {
     qagnn_gemm_nn_args gs = {};
     gs.A1 = dKMQ; gs.lda1 = 3 * DP; gs.K1 = 3 * DP; gs.B1 = h->Ws; gs.ldb1 = SP; gs.C = h->dS; gs.ldc = SP; gs.M = N; gs.No = SP;
     gs.accumulate = h->accumulate_dS;
-    gs.a_amax1 = w_dkmq; gs.pieces = hop_pieces(h);
-    HOP_TRY(hop_nn(h, &gs, h->Ws_t, 3 * DP, nullptr, 0, pkws, pk_elems, stream));
+    nn_scaled(h, &gs, w_dkmq);
+    HOP_TRY(hop_nn(h, &gs, h->Ws_t, 3 * DP, nullptr, 0, w.pkws, stream));
   }
   return QAGNN_OK;
 }
@@ -384,7 +382,7 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
 // k hops, last first; the buffer sets alternate and the main stream joins the weight-gradient stream before it returns
 static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main) {
   // every hop, before an event is recorded or a kernel enqueued: a refused stack leaves every buffer as it was
-  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], k > 1 ? "stack_bwd" : "hop_bwd"));
+  for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], k > 1 ? "stack_bwd" : "hop_bwd", true));
   SideSync ss;
   HOP_TRY(side_sync_init(&ss, main, (hipStream_t)hops[k - 1].side_stream));
   hipEvent_t done[2] = {nullptr, nullptr};
@@ -429,7 +427,7 @@ static int stack_fwd_impl(const qagnn_hop_args* hops, int32_t k, bool infer, qag
   for (int l = 0; l < k; ++l) {
     const HopAmax am = hop_amax_stack(hops, k, l, infer);
     if (am.on && !one_array) HOP_TRY(qagnn_zero_words(hops[l].amax, QAGNN_HOP_AMAX_WORDS, stream));
-    HOP_TRY(hop_fwd_one(&hops[l], am, am.on && am.x != hops[l].amax + AM_X, am.on && am.s != hops[l].amax + AM_S, stream));
+    HOP_TRY(hop_fwd_one(&hops[l], am, am.on && am.x != hops[l].amax + QAGNN_HOP_AM_X, am.on && am.s != hops[l].amax + QAGNN_HOP_AM_S, stream));
   }
   return QAGNN_OK;
 }
@@ -463,7 +461,7 @@ extern "C" int qagnn_stack_infer_f32(const qagnn_hop_args* hops, int32_t k, qagn
         QAGNN_REQUIRE(!wp || !rp || wp + w.bytes <= rp || rp + r.bytes <= wp, QAGNN_EINVAL,
                       "stack_infer: hop %d writes into one of its own inputs (y over X, or X / S inside its result buffers)", l);
       }
-    QAGNN_REQUIRE(qagnn_bn_relu_absmax_scratch_elems(h->N, h->DP) <= max64(h->N, gelu_amax_scratch_elems((int64_t)h->N * h->DP)), QAGNN_EINVAL,
+    QAGNN_REQUIRE(qagnn_bn_relu_absmax_scratch_elems(h->N, h->DP) <= HopFwdWs::layout(h->N, h->g->Ep, h->DP, h->SP, 0, nullptr).ampart_elems, QAGNN_EINVAL,
                   "stack_infer: the partial maxima of bn_relu_absmax do not fit the hop workspace");
   }
   return stack_fwd_impl(hops, k, true, stream);

@@ -16,6 +16,8 @@ import weakref
 import torch
 from torch.amp import custom_bwd, custom_fwd
 
+from . import _lib  # (constants only; the library is loaded by kernels())
+
 # every operator computes in fp32: inside torch.autocast (the reference's --fp16 mode, qagnn.py:254-257) inputs are cast back
 _fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 _bwd = custom_bwd(device_type='cuda')
@@ -603,6 +605,24 @@ def _wants_amax(K, X):
     return getattr(K, 'gemm_split', 1) >= 2 and getattr(K, 'name', '') == 'hip' and X.dim() == 2 and X.size(0) >= pack_min_rows(K)
 
 
+def _hop_left_ymax(K, X, batch_stats, infer=False):
+    """The provider's natively sequenced hop over X ran the three-MFMA form, so its GELU / dropout pass left max |y| in the hop's HOP_AM_Y
+    word.  Twin of hop_h2 in csrc/hop.hip (which zeroes the words only where it holds): the form takes batch statistics in training and
+    running statistics in the forward-only stack (infer)."""
+    return _wants_amax(K, X) and (not batch_stats if infer else bool(batch_stats))
+
+
+def _note_ymax(y, words):
+    """words: the int32 amax words of the hop that produced y (qagnn_hop_args.amax)"""
+    return amax_note(y, words[_lib.HOP_AM_Y:_lib.HOP_AM_Y + 1])
+
+
+def _producer_words(X, S):
+    """keyword arguments for a stack call: the maxima X's / S's producers left, where there are any (no reduction pass inside the stack then)"""
+    xw, sw = amax_lookup(X), amax_lookup(S)
+    return dict(x_amax=xw, s_amax=sw) if xw is not None or sw is not None else {}
+
+
 class GeluDropoutFn(torch.autograd.Function):
     """Y = dropout(gelu_tanh(X), p)   (utils/layers.py:10-14 + F.dropout); the keep mask is regenerated in backward."""
 
@@ -904,8 +924,8 @@ class HopFn(torch.autograd.Function):
         fwd = getattr(K, 'hop_fwd', None)
         args = (graph, HP, qscale, X, S, ntype, prm, batch_stats, eps, p, seed, apply_act)
         y, saved = fwd(*args, running, tab_col) if fwd is not None else hop_fwd_composed(K, *args, running, tab_col)
-        if apply_act and len(saved) > 6 and _wants_amax(K, X) and batch_stats:  # (as StackFn: the library's condition for the form, hop_h2)
-            amax_note(y, saved[6][4:5])  # max |y| (AM_Y), left by the hop's GELU / dropout pass: the next hop or the output layer reads it
+        if apply_act and len(saved) > 6 and _hop_left_ymax(K, X, batch_stats):
+            _note_ymax(y, saved[6])  # the next hop or the output layer reads it
         ctx.save_for_backward(X, S, ntype, *prm, *saved)
         ctx.cfg = (graph, HP, qscale, batch_stats, eps, p, seed, apply_act, len(prm))
         ctx.tab_col = tab_col
@@ -960,13 +980,9 @@ class StackFn(torch.autograd.Function):
         K = kernels()
         npk = len(prm) // k
         prms = [prm[l * npk:(l + 1) * npk] for l in range(k)]
-        xw, sw = amax_lookup(X), amax_lookup(S)
-        kw = {}
-        if xw is not None or sw is not None:  # (the producers of X / S left their maxima: no reduction pass inside the stack)
-            kw = dict(x_amax=xw, s_amax=sw)
-        y, saved = K.stack_fwd(graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, tab_col, **kw)
-        if len(saved) > 4 and _wants_amax(K, X) and batch_stats:  # (the library's own condition for the form: csrc/hop.hip, hop_h2)
-            amax_note(y, saved[4][k - 1, 4:5])  # max |y| of the last hop (AM_Y), left by its GELU / dropout pass
+        y, saved = K.stack_fwd(graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, tab_col, **_producer_words(X, S))
+        if len(saved) > 4 and _hop_left_ymax(K, X, batch_stats):
+            _note_ymax(y, saved[4][k - 1])  # (the last hop's)
         ctx.save_for_backward(X, S, ntype, *prm, *saved)
         ctx.cfg = (graph, HP, qscale, batch_stats, eps, p, seeds, k, npk)
         ctx.accX, ctx.tab_col = accX, tab_col
@@ -1019,13 +1035,9 @@ def stack_infer(X, S, ntype, graph, HP, qscale, prms, eps, tab_col=-1):
     K|M|Q, the attention, aggr, h1, out and y of every hop for its backward).  The last hop's max |y| is noted like StackFn's, so the
     output layer behind the stack takes the three-MFMA form too."""
     K = kernels()
-    xw, sw = amax_lookup(X), amax_lookup(S)
-    kw = {}
-    if xw is not None or sw is not None:
-        kw = dict(x_amax=xw, s_amax=sw)
-    y, amax = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **kw)
-    if _wants_amax(K, X):  # (the library's own condition for the form: csrc/hop.hip, hop_h2 with infer)
-        amax_note(y, amax[len(prms) - 1, 4:5])
+    y, amax = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **_producer_words(X, S))
+    if _hop_left_ymax(K, X, False, infer=True):
+        _note_ymax(y, amax[len(prms) - 1])
     return y
 
 

@@ -6,8 +6,7 @@ value of the `-m gpu` tests and as the CPU provider of the host-logic tests (rou
 import torch
 
 from emu_kernels import EmuKernels
-
-HOP_AMAX_WORDS = 16
+from qagnn_amd._lib import HOP_AMAX_WORDS
 
 
 class EmuInferKernels(EmuKernels):

@@ -402,7 +402,6 @@ def _canary(*shape):
 def run_edge_kernels_into_canaries(case):
     """forward and two backwards through the C ABI into buffers that hold the canary -> (aggr, a, alpha, dKMQ, dEkEm), the second backward's
     (dKMQ, dEkEm)"""
-    from qagnn_amd import _lib
     (ei, et, nt, R, T), HP, DP = case.graph, case.HP, 4 * case.HP
     K = hip()
     g = K.graph_prep(ei.cuda(), et.cuda(), nt.cuda(), R, T)
@@ -413,7 +412,7 @@ def run_edge_kernels_into_canaries(case):
     assert rc == 0, K.lib.qagnn_last_error().decode()
     runs = []
     for _ in range(2):
-        outs = [_canary(g.N, 3 * DP), _canary(g.C, 2 * DP), _canary(g.Ep, 4), _canary(g.N, 4), _canary(g.max_chunks + _lib.CLS_SLICES * g.C, 2 * DP)]
+        outs = [_canary(g.N, 3 * DP), _canary(g.C, 2 * DP), _canary(g.Ep, 4), _canary(g.N, 4), _canary(g.cls_part_rows, 2 * DP)]
         rc = K.lib.qagnn_edge_attn_bwd_f32(C.byref(g.c), KMQ.data_ptr(), 3 * DP, EkEm.data_ptr(), 2 * DP, HP, case.qs, a.data_ptr(), alpha.data_ptr(),
                                            G.data_ptr(), DP, *[t.data_ptr() for t in outs], K._stream())
         assert rc == 0, K.lib.qagnn_last_error().decode()

@@ -216,9 +216,8 @@ def test_edge_attention_refuses_a_pitch_outside_the_range(HP):
     assert all(bool((t == CANARY).all()) for t in (score, a, alpha, aggr)), 'the refused forward wrote to an output'
     with pytest.raises(RuntimeError, match=r'\(code 2\)'):  # ... and through the binding
         K.edge_attn_fwd(g, KMQ, EkEm, HP, 0.25)
-    from qagnn_amd import _lib
     a_in, alpha_in = torch.rand(g.Ep, 4).cuda(), torch.rand(g.Ep, 4).cuda()
-    outs = [_canary(g.N, 3 * DP), _canary(g.C, 2 * DP), _canary(g.Ep, 4), _canary(g.N, 4), _canary(g.max_chunks + _lib.CLS_SLICES * g.C, 2 * DP)]
+    outs = [_canary(g.N, 3 * DP), _canary(g.C, 2 * DP), _canary(g.Ep, 4), _canary(g.N, 4), _canary(g.cls_part_rows, 2 * DP)]
     rc = K.lib.qagnn_edge_attn_bwd_f32(C.byref(g.c), KMQ.data_ptr(), 3 * DP, EkEm.data_ptr(), 2 * DP, HP, 0.25, a_in.data_ptr(), alpha_in.data_ptr(),
                                        G.data_ptr(), DP, *[t.data_ptr() for t in outs], K._stream())
     torch.cuda.synchronize()
@@ -246,7 +245,7 @@ def _canaried_hop(K, g, nt, HP, backward, T=4):
         flat, dX, dS = _canary(offs[-1]), _canary(g.N, DP), _canary(g.N, SP)
         K._carve_grads(h, flat, sizes, offs, g.C)
         h.dy, h.dX, h.dS = dy.data_ptr(), dX.data_ptr(), dS.data_ptr()
-        ws = _canary(int(K.lib.qagnn_hop_bwd_workspace_elems(g.N, g.Ep, DP, SP, g.max_chunks + _lib.CLS_SLICES * g.C)))
+        ws = _canary(int(K.lib.qagnn_hop_bwd_workspace_elems(g.N, g.Ep, DP, SP, g.cls_part_rows)))
         guarded += [flat, dX, dS]
     else:
         ws = _canary(int(K.lib.qagnn_hop_fwd_workspace_elems(g.N, g.Ep, DP)))

@@ -14,6 +14,8 @@ import torch
 
 import helpers
 from emu_kernels import EmuGraph, EmuKernels
+from qagnn_amd._lib import (HOP_AM_AGGR as AM_AGGR, HOP_AM_DH1 as AM_DH1, HOP_AM_DKMQ as AM_DKMQ, HOP_AM_DOUT as AM_DOUT, HOP_AM_H1 as AM_H1,
+                            HOP_AM_S as AM_S, HOP_AM_X as AM_X, HOP_AM_Y as AM_Y)
 
 EMU = EmuKernels()
 EPS = 1.2e-7
@@ -1619,9 +1621,6 @@ def test_gemm_with_fused_row_gather_in_the_three_mfma_form_at_small_m(M, V, Kd, 
     six = K.gemm_nn(table.cuda(), B.cuda(), **kw).cpu()
     if M * No >= 200:
         assert not torch.equal(got3, six), 'the three-MFMA form did not run'
-
-
-AM_X, AM_S, AM_AGGR, AM_H1, AM_Y, AM_DOUT, AM_DH1, AM_DKMQ = range(8)  # word layout of a hop's amax block (csrc/hop.hip)
 
 
 def _bits(t):

@@ -18,6 +18,7 @@ import torch
 
 import helpers
 from qagnn_amd import data_utils, ops, synthetic
+from qagnn_amd._lib import HOP_AM_AGGR as AM_AGGR, HOP_AM_DH1 as AM_DH1, HOP_AM_DKMQ as AM_DKMQ, HOP_AM_DOUT as AM_DOUT, HOP_AM_H1 as AM_H1, HOP_AM_Y as AM_Y
 from test_host_logic_emu import FWD, build, golden_inputs
 
 CASES = list(helpers.GOLDEN_CASES.keys())
@@ -686,9 +687,6 @@ def test_whole_stack_native_call_equals_per_hop_path_in_the_three_mfma_form(case
         assert all(torch.equal(b0[k], b1[k]) for k in b0)
     lc, gc, _ = res[3]
     assert not torch.equal(l0, lc) and any(not torch.equal(g0[k], gc[k]) for k in g0), 'the composed leg equals the native ones'
-
-
-AM_X, AM_S, AM_AGGR, AM_H1, AM_Y, AM_DOUT, AM_DH1, AM_DKMQ = range(8)  # word layout of a hop's amax block (csrc/hop.hip)
 
 
 def _bits(t):

@@ -20,7 +20,7 @@ from qagnn_amd import _lib, data_utils, graphed, inference, ops, synthetic
 from test_host_logic_emu import FWD, build, golden_inputs
 
 EVAL_CASES = [c for c in helpers.GOLDEN_CASES if not helpers.GOLDEN_CASES[c]['train']]
-AM_X, AM_S, AM_AGGR, AM_H1, AM_Y = range(5)  # word layout of a hop's amax block (csrc/hop.hip)
+AM_X, AM_S, AM_AGGR, AM_H1, AM_Y = _lib.HOP_AM_X, _lib.HOP_AM_S, _lib.HOP_AM_AGGR, _lib.HOP_AM_H1, _lib.HOP_AM_Y  # a hop's amax words
 LOG = os.environ.get('QAGNN_INFER_TEST_LOG')  # file that collects the measured figures of the GPU tests
 
 

@@ -46,9 +46,12 @@ def main():
                       lib.qagnn_gemm_nn_ws_bytes(C.byref(a), ptr, K1, ptr if K2 else None, K2))
         finally:
             lib.qagnn_packed_min_rows(old)
-    for (N, Ep), DP, SP in itertools.product([(2000, 14400), (12800, 92160), (64000, 460800)], (208, 112), (0, 112)):
-        print('hop_fwd_workspace_elems', N, Ep, DP, lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP))
-        for cls_rows in (0, 640):
+    # the hop workspaces: N at both sides of the packed-row and row-block thresholds, Ep = 7.2 N as in the benchmark's batches
+    for N, DP, SP in itertools.product([1, 2000, 8191, 8192, 12800, 32767, 32768, 64000], (16, 64, 112, 208, 256), (0, 16, 112, 128)):
+        Ep = N * 36 // 5
+        if SP == 0:
+            print('hop_fwd_workspace_elems', N, Ep, DP, lib.qagnn_hop_fwd_workspace_elems(N, Ep, DP))
+        for cls_rows in (0, 2, 640, 40960):
             print('hop_bwd_workspace_elems', N, Ep, DP, SP, cls_rows, lib.qagnn_hop_bwd_workspace_elems(N, Ep, DP, SP, cls_rows))
 
 
