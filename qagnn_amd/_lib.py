@@ -34,6 +34,9 @@ EXPORTS_INFER = ['qagnn_infer_version', 'qagnn_bn_relu_absmax_scratch_elems', 'q
                  'qagnn_choice_eval_f32']
 # include/qagnn_hip_loss.h, the extension header of the training losses (likewise)
 EXPORTS_LOSS = ['qagnn_loss_version', 'qagnn_choice_loss_f32', 'qagnn_choice_loss_bwd_f32']
+# include/qagnn_hip_explain.h, the extension header of the detailed evaluation: attention export and its trace from the context node (likewise)
+EXPORTS_EXPLAIN = ['qagnn_explain_version', 'qagnn_attn_export_f32', 'qagnn_attn_trace_f32']
+TRACE_MAX_N = 1024  # QAGNN_TRACE_MAX_N
 LOSS_KINDS = {'cross_entropy': 0, 'margin_rank': 1}  # QAGNN_LOSS_CROSS_ENTROPY, QAGNN_LOSS_MARGIN_RANK
 LOSS_THREADS = 256  # QAGNN_LOSS_THREADS
 
@@ -192,7 +195,10 @@ def load_library(path=LIB_PATH):
     lib.qagnn_loss_version.argtypes = []
     lib.qagnn_choice_loss_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]
     lib.qagnn_choice_loss_bwd_f32.argtypes = [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS:
+    lib.qagnn_explain_version.argtypes = []
+    lib.qagnn_attn_export_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _vp, _i64, _vp]
+    lib.qagnn_attn_trace_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -405,6 +411,7 @@ class HipKernels(metaclass=_GuardedMeta):
     """Tensor-level calls into libqagnn_hip.so, each on the current HIP stream of the device that holds its operands
     (see _on_operand_device)."""
     name = 'hip'
+    infer_attn = True  # stack_infer(attn=True): an `a` buffer per hop for ops.attention_capture
     tn_live = True  # the native hop hands its graph to the dWx_t | dWs_t product (live k-tiles, gemm_tn_graph): ops.hop_bwd_composed follows
 
     def __init__(self):
@@ -1380,10 +1387,13 @@ class HipKernels(metaclass=_GuardedMeta):
                     'qagnn_choice_loss_bwd_f32')
         return out
 
-    def stack_infer(self, graph, HP, qscale, X, S, ntype, prms, eps, cols=-1, x_amax=None, s_amax=None, keep=False):
+    def stack_infer(self, graph, HP, qscale, X, S, ntype, prms, eps, cols=-1, x_amax=None, s_amax=None, keep=False, attn=False):
         """The k-hop forward with running statistics and no dropout that keeps nothing (qagnn_stack_infer_f32): ONE set of hop buffers shared
         by all hops plus two alternating y.  -> (y [N, DP], amax [k, HOP_AMAX_WORDS]).  keep=True (tests): a set of buffers per hop, returned
-        as a third value (KMQ, aa, rows, stats) laid out as stack_fwd's saved tensors."""
+        as a third value (KMQ, aa, rows, stats) laid out as stack_fwd's saved tensors.  attn=True (ops.attention_capture): one `a` buffer PER
+        HOP, returned as a third value [k, Ep, 4] in source order; everything else stays shared -- the same launches, only the address of a
+        differs."""
+        assert not (keep and attn)
         k = len(prms)
         N, DP, Ep, dev = graph.N, 4 * HP, graph.Ep, X.device
         kk = k if keep else 1
@@ -1396,8 +1406,57 @@ class HipKernels(metaclass=_GuardedMeta):
         ys = [rows[l, 3] if keep else rows[3 + (l & 1)] for l in range(k)]  # (shared set: aggr | h1 | out | y even | y odd)
         hops = self._hop_chain(graph, HP, qscale, X, S, ntype, prms, ys, (KMQ, aa, rows, stats), amax.data_ptr(), x_amax, s_amax, ws, False, eps, 0.0,
                                None, cols, shared=not keep)
+        if attn:
+            a_all = torch.empty((k, Ep, 4), dtype=torch.float32, device=dev)
+            for l in range(k):
+                hops[l].a = a_all.data_ptr() + l * Ep * 16
         self._check(self.lib.qagnn_stack_infer_f32(hops, k, self._stream()), 'qagnn_stack_infer_f32')
+        if attn:
+            return ys[-1], amax, a_all
         return (ys[-1], amax, (KMQ, aa, rows, stats)) if keep else (ys[-1], amax)
+
+    # -- the detailed evaluation (include/qagnn_hip_explain.h) ------------------------------------------------------------------------------
+    @staticmethod
+    def _chk_attn(graph, a):
+        """a: [k, Ep, 4] fp32 in source order, layers a multiple of 4 floats (>= 4 Ep) apart, rows contiguous -> (k, layer stride)"""
+        assert a.is_cuda and a.dtype == torch.float32 and a.dim() == 3 and a.shape[1:] == (graph.Ep, 4), \
+            f'a: need a [k, Ep = {graph.Ep}, 4] float32 device tensor, got {tuple(a.shape)} {a.dtype} {a.device}'
+        k = a.size(0)
+        ls = a.stride(0) if k > 1 else 4 * graph.Ep
+        assert k == 0 or ((graph.Ep == 1 or a.stride(1) == 4) and a.stride(2) == 1 and ls >= 4 * graph.Ep and ls % 4 == 0 and a.data_ptr() % 16 == 0), \
+            f'a: rows of 4 contiguous floats, layers a multiple of 4 floats apart, 16-byte aligned; got strides {a.stride()}'
+        return k, ls
+
+    def attn_export(self, graph, a, out=None):
+        """a [k, Ep, 4] (the hops' pre-degree softmax in source order; layers may be pitched) -> alpha [k, Ep, 4] in the caller's edge order, self
+        loops last: alpha[l][eid_s[p]] = a[l][p] for the rowptr_s[N] live positions, one launch (qagnn_attn_export_f32).  Rows behind the
+        live ones (a graph with an edge capacity) are not written.  out: a [k, Ep, 4] tensor to write into (layers may be pitched), else
+        allocated."""
+        k, ls = self._chk_attn(graph, a)
+        if out is None:
+            out = torch.empty((k, graph.Ep, 4), dtype=torch.float32, device=a.device)
+        ko, ols = self._chk_attn(graph, out)
+        assert ko == k and out.device == a.device
+        self._check(self.lib.qagnn_attn_export_f32(C.byref(graph.c), a.data_ptr() if k else None, ls, k, out.data_ptr() if k else None, ols,
+                                                   self._stream()), 'qagnn_attn_export_f32')
+        return out
+
+    def attn_trace(self, graph, a, B, n, root=0, head=-1, out=None):
+        """-> (flow [k + 1, N], best [k + 1, N], pred [k, N] int32): the attention a [k, Ep, 4] followed out of node slot `root` of each of
+        the B subgraphs of n node rows, one launch (qagnn_attn_trace_f32).  head: -1 the mean of the four heads, or one head.  out: the
+        three tensors to write into, else allocated."""
+        k, ls = self._chk_attn(graph, a)
+        N, dev = graph.N, a.device
+        if out is None:
+            out = (torch.empty((k + 1, N), dtype=torch.float32, device=dev), torch.empty((k + 1, N), dtype=torch.float32, device=dev),
+                   torch.empty((k, N), dtype=torch.int32, device=dev))
+        flow, best, pred = out
+        for t, rows, dt in ((flow, k + 1, torch.float32), (best, k + 1, torch.float32), (pred, k, torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.shape == (rows, N) and t.is_contiguous() and t.device == dev
+        self._check(self.lib.qagnn_attn_trace_f32(C.byref(graph.c), a.data_ptr() if k else None, ls, k, int(B), int(n), int(root), int(head),
+                                                  flow.data_ptr(), best.data_ptr(), pred.data_ptr() if k else None, self._stream()),
+                    'qagnn_attn_trace_f32')
+        return flow, best, pred
 
     # -- the whole k-hop stack per call (csrc/hop.hip: qagnn_stack_{fwd,bwd}_f32) -------------------------------------------------------
     def stack_fwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, runnings, cols=-1, x_amax=None, s_amax=None):

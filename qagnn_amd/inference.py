@@ -142,3 +142,46 @@ def evaluate_accuracy(eval_set, model, graphed=False):
             ops.kernels().choice_eval(logits.reshape(labels.size(0), -1), labels.to(logits.device, non_blocking=True).contiguous(), counts)
     n_correct, n_samples = fwd.counts() if graphed and fwd is not None else (counts.tolist() if counts is not None else (0, 0))
     return n_correct / n_samples
+
+
+def evaluate_detail(eval_set, model, preds_path=None, trace=False, head=-1):
+    """The reference's detailed evaluation (qagnn.py:401-430, and the save_test_preds branch of its training loop, :294-310): the loop
+    `for qids, labels, *input_data in eval_set` on the inference path, one prediction per question.  -> (accuracy, [(qid, pred)], traces):
+    pred the index of the chosen answer, traces None or, with trace=True, one explain.Trace per batch (the attention of the forward's k
+    hops followed out of the context node; head as explain.trace takes it).  preds_path: the reference's prediction file is written
+    there, one line '{qid},{letter}' per question.
+
+    The predictions are the argmax of qagnn_choice_eval_f32, kept on the device per batch; the two counts are accumulated there as in
+    evaluate_accuracy; the host reads everything with ONE synchronisation behind the last batch (the reference: two `.item()` per
+    question).  An empty set raises ZeroDivisionError, as evaluate_accuracy does.  Leaves the model in eval mode."""
+    from . import explain
+    model.eval()
+    counts, preds, words, qid_list, traces = None, [], [], [], ([] if trace else None)
+    K = ops.kernels()
+    with torch.no_grad(), ops.inference_path():
+        for qids, labels, *input_data in eval_set:
+            if trace:
+                rec, w = explain.trace_nosync(model, input_data, head)
+                logits = rec.logits
+                traces.append(rec)
+                words.append(w[:1].to(logits.device))
+            else:
+                logits, _ = model(*input_data)
+            if counts is None:
+                counts = torch.zeros(2, dtype=torch.long, device=logits.device)
+            Q = labels.size(0)
+            pred = torch.empty(Q, dtype=torch.long, device=logits.device)
+            K.choice_eval(logits.reshape(Q, -1), labels.to(logits.device, non_blocking=True).contiguous(), counts, pred=pred)
+            preds.append(pred)
+            qid_list += list(qids)
+    host = torch.cat([counts] + preds + words).tolist() if counts is not None else [0, 0]  # the one device-to-host copy of the pass
+    n_correct, n_samples = host[:2]
+    accuracy = n_correct / n_samples
+    for flag in host[2 + len(qid_list):]:
+        explain.check_block_flag(flag)
+    results = list(zip(qid_list, host[2:2 + len(qid_list)]))
+    if preds_path is not None:
+        with open(preds_path, 'w') as f:
+            for qid, p in results:
+                print('{},{}'.format(qid, chr(ord('A') + p)), file=f)  # (qagnn.py:307)
+    return accuracy, results, traces

@@ -406,10 +406,14 @@ class QAGNN_Message_Passing(nn.Module):
             Wes_t = F.pad(Wes.t(), (0, JP - h, 0, JP - h)).contiguous()
             npk = GATConvE.N_PACKED
             # the per-layer class-table / type-table operands side by side: one GEMM serves all k layers
-            We_all = torch.cat([L.pad(outs[l * npk + 6]) for l in range(self.k)], 0)        # [k*2DP, DP]
-            be_all = torch.cat([outs[l * npk + 7] for l in range(self.k)])                   # [k*2DP]
-            Wtype_all = torch.cat([outs[l * npk + 4] for l in range(self.k)], 1)            # [d/2, k*3DP]
-            bias_all = torch.cat([outs[l * npk + 5] for l in range(self.k)])                 # [k*3DP]
+            if self.k > 0:
+                We_all = torch.cat([L.pad(outs[l * npk + 6]) for l in range(self.k)], 0)    # [k*2DP, DP]
+                be_all = torch.cat([outs[l * npk + 7] for l in range(self.k)])               # [k*2DP]
+                Wtype_all = torch.cat([outs[l * npk + 4] for l in range(self.k)], 1)        # [d/2, k*3DP]
+                bias_all = torch.cat([outs[l * npk + 5] for l in range(self.k)])             # [k*3DP]
+            else:  # (no hop: nothing reads the tables; empty operands keep the packed list's shape)
+                We_all, be_all = Vhw.new_zeros((0, L.DP)), Vhw.new_zeros(0)
+                Wtype_all, bias_all = Vhw.new_zeros((h, 0)), Vhw.new_zeros(0)
             eW1t = L.pad(F.pad(eW1, (0, FP - eW1.size(1))).t())                             # [FP, DP]
             eW2t, eW2p = _pad2(eW2, L)
             return outs + [Vh_t, Vh, Vx_t, Vx, L.pad(Vhb), L.pad(Vxb), Wes_t, Wes_t.t().contiguous(), F.pad(bes, (0, JP - h)),
@@ -466,7 +470,14 @@ class QAGNN_Message_Passing(nn.Module):
         # (the forward-only stack, ops.inference_path: opt-in, eval mode without autograd and with running statistics; it runs the form too)
         infer = (stack_native and ops.INFERENCE_PATH and not self.training and not torch.is_grad_enabled() and bn0.track_running_stats
                  and hasattr(Kp, 'stack_infer'))
-        pieces = ({2: 2, 3: 1}[Kp.gemm_split] if (stack_native and getattr(Kp, 'gemm_split', 1) >= 2 and (self.training or not bn0.track_running_stats or infer))
+        # (ops.attention_capture, opt-in: the forward-only stack with an `a` buffer per hop where the provider has that, else the per-layer
+        # loop, whose hops return their attention anyway; never a StackFn node)
+        cap = ops.ATTN_CAPTURE
+        if cap is not None:
+            cap.check(self.training)
+            infer = infer and getattr(Kp, 'infer_attn', False)
+            stack_native = infer
+        pieces =({2: 2, 3: 1}[Kp.gemm_split] if (stack_native and getattr(Kp, 'gemm_split', 1) >= 2 and (self.training or not bn0.track_running_stats or infer))
                   else 3)  # (3 -> one image: the reduced-precision form, on request only)
         pairs = []
         for pk in per_layer:
@@ -499,16 +510,22 @@ class QAGNN_Message_Passing(nn.Module):
                     runnings.append(bn_running(bn, L, Hp.size(0), self.training))
                 if infer:
                     Xp = ops.stack_infer(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms, bn0.eps,
-                                         tab_col=(self._tab_col, L.ones_col))
+                                         tab_col=(self._tab_col, L.ones_col), capture=cap)
                 else:
                     Xp = ops.gat_stack(Hp, S, ntype, graph, L.HP, 1.0 / math.sqrt(self.gnn_layers[0].dim_per_head), prms,
                                        self.training or not bn0.track_running_stats, bn0.eps, self.dropout_rate if self.training else 0.0,
                                        runnings, accX=accX, tab_col=(self._tab_col, L.ones_col))
                 per_layer = []
+            elif cap is not None:
+                attn = []
             for l, (layer, pk) in enumerate(zip(self.gnn_layers, per_layer)):  # mp_helper (:45-50): GATConvE -> GELU -> dropout, fused
-                Xp, _ = layer.hop(Xp, None, graph, None, L, apply_act=True, p_drop=self.dropout_rate, typed=(temb, ntype, S),
+                Xp, a = layer.hop(Xp, None, graph, None, L, apply_act=True, p_drop=self.dropout_rate, typed=(temb, ntype, S),
                                   packed=pk, tables=(TT[l], ekem[l]), acc=(accX if l == 0 else None, True, accS, l == 0),
                                   tab_col=self._tab_col)
+                if cap is not None:
+                    attn.append(a)
+            if cap is not None and not stack_native:
+                cap.hold(graph, torch.stack(attn) if attn else Hp.new_empty((0, graph.Ep, 4)))
             Y = ops.linear_nn(Hp, Vh_t, Vh, Xp, Vx_t, Vx, bias=bVh + bVx, acc=(accX, False, None, False))
         out = ops.gelu_dropout(Y, self.dropout_rate, self.training)  # :92-93
         if padded_output:

@@ -1029,13 +1029,52 @@ class inference_path:
         return False
 
 
-def stack_infer(X, S, ntype, graph, HP, qscale, prms, eps, tab_col=-1):
+class attention_capture:
+    """`with ops.inference_path(), ops.attention_capture() as cap:` -- an eval-mode forward under torch.no_grad() inside the scope leaves
+    the graph it ran on and the attention of its k hops in `cap.graph` and `cap.a` ([k, Ep, 4]: the per-source softmax before the
+    out-degree scaling, in SOURCE order -- the reference's `_alpha`; Kernels.attn_export / qagnn_amd.explain bring it into the caller's
+    edge order).  The forward-only stack then writes one `a` buffer per hop instead of one for all: the same launches, only that address
+    differs.  A forward in train mode or with autograd on is refused: its stack keeps the attention for its own backward and is not
+    what this scope reads.  Opt-in: outside the scope every forward is what it was."""
+
+    def __init__(self):
+        self.graph = self.a = None
+
+    def __enter__(self):
+        global ATTN_CAPTURE
+        self.prev = ATTN_CAPTURE
+        ATTN_CAPTURE = self
+        return self
+
+    def __exit__(self, *exc):
+        global ATTN_CAPTURE
+        ATTN_CAPTURE = self.prev
+        return False
+
+    @staticmethod
+    def check(training):
+        if training or torch.is_grad_enabled():
+            raise RuntimeError('ops.attention_capture() reads the attention of an EVALUATION forward: call model.eval() and run the forward '
+                               f'under torch.no_grad() (training={bool(training)}, grad enabled={torch.is_grad_enabled()})')
+
+    def hold(self, graph, a):
+        self.graph, self.a = graph, a
+
+
+ATTN_CAPTURE = None  # the innermost open attention_capture scope
+
+
+def stack_infer(X, S, ntype, graph, HP, qscale, prms, eps, tab_col=-1, capture=None):
     """All k hops (GELU after each) with BatchNorm's running statistics and no dropout, keeping nothing: a plain function, no autograd
     node, no seed drawn.  One set of hop buffers and two alternating outputs are allocated, whatever k (the training stack keeps
     K|M|Q, the attention, aggr, h1, out and y of every hop for its backward).  The last hop's max |y| is noted like StackFn's, so the
-    output layer behind the stack takes the three-MFMA form too."""
+    output layer behind the stack takes the three-MFMA form too.  capture: an attention_capture that receives the hops' attention."""
     K = kernels()
-    y, amax = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **_producer_words(X, S))
+    if capture is not None:
+        y, amax, a = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **_producer_words(X, S), attn=True)
+        capture.hold(graph, a)
+    else:
+        y, amax = K.stack_infer(graph, HP, qscale, X, S, ntype, prms, eps, tab_col, **_producer_words(X, S))
     if _hop_left_ymax(K, X, False, infer=True):
         _note_ymax(y, amax[len(prms) - 1])
     return y
