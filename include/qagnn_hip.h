@@ -523,7 +523,8 @@ typedef struct qagnn_hop_args {
   float* KMQ;                      /* [N, 3DP] */
   float* a; float* alpha;          /* [Ep, 4] each, source order */
   float* aggr; float* h1; float* out; float* y;   /* [N, DP]; y unused when apply_act == 0 */
-  float* stats;                    /* [5, DP]: mean, var, invstd, scale, shift */
+  float* stats;                    /* [5, DP]: mean, var, invstd, scale, shift; with batch_stats == 0 rows 0 and 1 (mean, var) are not written and
+                                      not read: the hop reads run_mean_p / run_var_p */
   /* backward only */
   const float* dy;                 /* [N, DP] */
   float* dX;                       /* [N, DP] or NULL */
@@ -554,7 +555,9 @@ typedef struct qagnn_hop_args {
                                       of a capture in progress on `stream`, the join closes the branch.  In a stack call the field of
                                       the LAST hop is the one that is read */
   uint32_t* amax;                  /* NULL, or QAGNN_HOP_AMAX_WORDS device words that belong to this hop and that the caller keeps, untouched, from
-                                      the forward call to the backward call (the library zeroes them at the start of the forward).  With
+                                      the forward call to the backward call (a call that runs the form zeroes them: the forward all of them at its start, every
+                                      backward its own three, QAGNN_HOP_AM_DOUT .. DKMQ, again; a call that does not run the form neither writes
+                                      nor reads them).  With
                                       gemm_split == 2 and batch statistics, the hop's large products then run in the three-MFMA form
                                       (csrc/gemm_nn2.hip): word QAGNN_HOP_AM_<name> (below) holds the bit pattern of that tensor's maximum, left
                                       behind by the kernel that produces the tensor (X, S of the first hop: one reduction pass each).  In a stack call

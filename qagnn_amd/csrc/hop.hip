@@ -379,10 +379,39 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   return QAGNN_OK;
 }
 
+// The backward's own maximum words (d out, d h1, d K|M|Q) are merged into by atomic maxima, like every word: they start EVERY backward at
+// zero.  The forward zeroes the whole block once; a second backward over the same saved state would otherwise merge into the first one's
+// maxima -- still a valid bound, so nothing turns non-finite, the scaled forms only lose the bits by which the gradients have shrunk
+// (tests/test_buffer_history.py).  One launch where the hops' blocks are one array (the module mirror's are), one per hop otherwise.
+static_assert(QAGNN_HOP_AM_DH1 == QAGNN_HOP_AM_DOUT + 1 && QAGNN_HOP_AM_DKMQ == QAGNN_HOP_AM_DOUT + 2, "the backward's words are three in a row");
+__global__ void k_zero_bwd_words(uint32_t* __restrict__ amax, int k) {  // amax: k blocks of QAGNN_HOP_AMAX_WORDS words
+  for (int i = threadIdx.x; i < 3 * k; i += blockDim.x) amax[(i / 3) * QAGNN_HOP_AMAX_WORDS + QAGNN_HOP_AM_DOUT + i % 3] = 0u;
+}
+static int zero_bwd_words(const qagnn_hop_args* hops, int k, hipStream_t main) {
+  bool all = true, any = false, one_array = true;
+  for (int l = 0; l < k; ++l) {
+    const bool h2 = hop_amax_stack(hops, k, l).on && hop_stat_width(hops[l].DP);  // (hop_bwd_one's condition for writing the words)
+    all = all && h2;
+    any = any || h2;
+    one_array = one_array && hops[l].amax != nullptr && hops[l].amax == hops[0].amax + (int64_t)l * QAGNN_HOP_AMAX_WORDS;
+  }
+  if (!any) return QAGNN_OK;
+  if (all && one_array) {
+    k_zero_bwd_words<<<1, 64, 0, main>>>(hops[0].amax, k);
+    QAGNN_LAUNCH_CHECK("k_zero_bwd_words");
+    return QAGNN_OK;
+  }
+  for (int l = 0; l < k; ++l)
+    if (hop_amax_stack(hops, k, l).on && hop_stat_width(hops[l].DP))
+      HOP_TRY(qagnn_zero_words(hops[l].amax + QAGNN_HOP_AM_DOUT, 3, (qagnn_stream_t)main));
+  return QAGNN_OK;
+}
+
 // k hops, last first; the buffer sets alternate and the main stream joins the weight-gradient stream before it returns
 static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main) {
   // every hop, before an event is recorded or a kernel enqueued: a refused stack leaves every buffer as it was
   for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], k > 1 ? "stack_bwd" : "hop_bwd", true));
+  HOP_TRY(zero_bwd_words(hops, k, main));
   SideSync ss;
   HOP_TRY(side_sync_init(&ss, main, (hipStream_t)hops[k - 1].side_stream));
   hipEvent_t done[2] = {nullptr, nullptr};

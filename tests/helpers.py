@@ -3,6 +3,7 @@
 Nothing in here touches /root/reference; `tests/golden/make_golden.py` (authoring container only)
 is the one script that does.
 """
+import contextlib
 import os
 import re
 import sys
@@ -1076,3 +1077,194 @@ def apply_form(name):
             yield name
     else:
         yield name
+
+
+# Buffer history -----------------------------------------------------------------------------------------------------------------------
+# The binding allocates its outputs, saved buffers and workspaces uninitialised (torch.empty) and the headers promise that no result
+# depends on what such a buffer held: a workspace is "undefined before and after", an output without `accumulate` is defined by the call
+# alone.  fresh_buffers(fill) hands the package every uninitialised allocation pre-filled, check_history_free() holds a call to the same
+# bits under every fill (tests/test_buffer_history.py).  Fills are BYTE patterns, so one policy serves the fp32 buffers, the fp16 / bf16
+# images inside the uint8 workspaces and their fp32 scales alike: 0x00; 0xFF, a NaN in every float format; 0x7B, finite and huge (fp32
+# 1.3e36, fp16 61 280, bf16 1.3e36): it ruins any sum it leaks into and lies outside the non-finite contract.  Integer and bool buffers
+# (graph storage, index staging, pred) get 0 under 'zero' and 1 otherwise, never an out-of-range value: a leak shows as changed bits,
+# not as a wild address.
+FILL_BYTES = {'zero': 0x00, 'nan': 0xFF, 'big': 0x7B}
+FILLS = tuple(FILL_BYTES)
+UNINITIALISED = ('empty', 'empty_like', 'new_empty')  # the allocation forms the policy covers (and the only ones the package may use)
+
+
+def fill_word(fill, dtype=None):
+    """what one element of a freshly filled buffer of `dtype` holds, as an integer: the int32 bit pattern of an fp32 element (default),
+    else the value of an integer / bool element"""
+    import torch
+    if dtype is None or dtype == torch.float32:
+        b = FILL_BYTES[fill]
+        w = b | b << 8 | b << 16 | b << 24
+        return w - (1 << 32) if w >= 1 << 31 else w
+    if dtype == torch.uint8:
+        return FILL_BYTES[fill]
+    assert not dtype.is_floating_point
+    return 0 if fill == 'zero' else 1
+
+
+def policy_fill_(t, fill):
+    """fill a freshly allocated tensor (it owns its whole storage) by the policy above, in place"""
+    import torch
+    if t.numel() == 0:
+        return t
+    with torch.no_grad():
+        d = t.detach()
+        if d.dtype.is_floating_point or d.dtype.is_complex or d.dtype == torch.uint8:
+            torch.empty(0, dtype=torch.uint8, device=d.device).set_(d.untyped_storage()).fill_(FILL_BYTES[fill])
+        else:
+            d.fill_(0 if fill == 'zero' else 1)
+    return t
+
+
+class _TorchWithPolicy:
+    """stands in for the `torch` global of a qagnn_amd module: every attribute is torch's, torch.empty / torch.empty_like fill their result"""
+
+    def __init__(self, torch, fill):
+        self.__dict__['_torch'], self.__dict__['_fill'] = torch, fill
+
+    def __getattr__(self, name):
+        return getattr(self._torch, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._torch, name, value)
+
+    def empty(self, *a, **kw):
+        return policy_fill_(self._torch.empty(*a, **kw), self._fill)
+
+    def empty_like(self, *a, **kw):
+        return policy_fill_(self._torch.empty_like(*a, **kw), self._fill)
+
+
+def package_modules():
+    """every module of qagnn_amd (each file of the package, imported), by name"""
+    import importlib
+    names = sorted(f[:-3] for f in os.listdir(os.path.join(ROOT, 'qagnn_amd')) if f.endswith('.py') and f != '__init__.py')
+    return {n: importlib.import_module('qagnn_amd.' + n) for n in names}
+
+
+_FRESH = [None]  # the open fill (scopes do not nest)
+
+
+@contextlib.contextmanager
+def fresh_buffers(fill):
+    """While open, every buffer the PACKAGE allocates uninitialised -- torch.empty and torch.empty_like through the `torch` global of a
+    qagnn_amd module, Tensor.new_empty called from a qagnn_amd module -- arrives filled by the policy above.  torch's own allocations
+    (torch.randn, autograd's, a test's) are untouched; on exit, also by an exception, everything is as it was.  Tests only."""
+    import torch
+    assert fill in FILL_BYTES, fill
+    assert _FRESH[0] is None, 'fresh_buffers does not nest'
+    mods = [m for m in package_modules().values() if m.__dict__.get('torch') is torch]
+    proxy = _TorchWithPolicy(torch, fill)
+    own = torch.Tensor.__dict__.get('new_empty')  # (None: inherited from the C base class, as torch ships it)
+    plain = torch.Tensor.new_empty
+
+    def new_empty(self, *a, **kw):
+        out = plain(self, *a, **kw)
+        caller = sys._getframe(1).f_globals.get('__name__', '')
+        return policy_fill_(out, fill) if caller == 'qagnn_amd' or caller.startswith('qagnn_amd.') else out
+
+    _FRESH[0] = fill
+    try:
+        for m in mods:
+            m.torch = proxy
+        torch.Tensor.new_empty = new_empty
+        yield proxy
+    finally:
+        _FRESH[0] = None
+        for m in mods:
+            m.torch = torch
+        if own is None:
+            del torch.Tensor.new_empty
+        else:
+            torch.Tensor.new_empty = own
+
+
+class Exempt:
+    """A region of a returned tensor that the header declares unwritten.  index: which returned tensor; region: t -> the view of t that is
+    exempt (applied to a mask of t's shape); quote: the header's sentence, verbatim; reader: the case of the table that consumes the tensor."""
+
+    def __init__(self, index, region, quote, reader):
+        self.index, self.region, self.quote, self.reader = index, region, quote, reader
+
+
+def _bits(t):
+    """the comparable form of a returned tensor on the host: fp32 as its int32 bit patterns, integer / bool data as it is"""
+    import torch
+    t = t.detach().cpu().contiguous()
+    if t.dtype == torch.float32:
+        return t.view(torch.int32)
+    assert not t.dtype.is_floating_point or t.dtype == torch.float64, t.dtype
+    return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+
+def _fill_bits(fill, t):
+    """what an untouched element of the returned tensor t holds under `fill`, in the terms of _bits"""
+    import torch
+    if t.dtype == torch.float64:
+        b = FILL_BYTES[fill]
+        w = sum(b << (8 * i) for i in range(8))
+        return w - (1 << 64) if w >= 1 << 63 else w
+    return fill_word(fill, t.dtype)
+
+
+def check_history_free(call, exempt=(), reset=None, fills=FILLS, what='', log=None):
+    """call() -> a tensor or a tuple of tensors, run under 'zero' twice and then under each other fill of `fills` (reset() before every run:
+    the dropout seeds).  The two 'zero' runs must agree bit for bit ("not deterministic", a failure of its own); every returned tensor
+    must then be bit-identical under all fills -- no tolerance: the arithmetic does not depend on what a buffer held.  exempt: Exempt
+    regions; each must still hold the fill, bit for bit, under every fill (a region that is written but differs is a failure), and none
+    may cover a whole tensor.  -> (compared elements, exempt elements); `log` receives one FIGURE line."""
+    import torch
+
+    def run(fill):
+        if reset is not None:
+            reset()
+        with fresh_buffers(fill):
+            out = call()
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+        out = (out,) if torch.is_tensor(out) else tuple(out)
+        return [(t.dtype, _bits(t)) for t in out]
+
+    assert fills[0] == 'zero'
+    base, again = run('zero'), run('zero')
+    assert len(base) == len(again)
+    for i, ((_, a), (_, b)) in enumerate(zip(base, again)):
+        assert a.shape == b.shape and torch.equal(a, b), \
+            f'{what}: not deterministic -- output {i} differs between two runs from zeroed buffers at {int((a != b).sum())} of {a.numel()} elements'
+    masks = [torch.zeros(b.shape, dtype=torch.bool) for _, b in base]
+    for ex in exempt:
+        ex.region(masks[ex.index])[...] = True
+    n_ex = [int(m.sum()) for m in masks]
+    for i, (m, n) in enumerate(zip(masks, n_ex)):
+        assert n < max(m.numel(), 1) or m.numel() == 0, f'{what}: the exemptions cover the whole of output {i}'
+    failures = []
+    for fill in fills:
+        got = base if fill == 'zero' else run(fill)
+        assert len(got) == len(base)
+        for i, ((dt, g), (_, b), m) in enumerate(zip(got, base, masks)):
+            if g.shape != b.shape:
+                failures.append(f'output {i} under {fill}: shape {tuple(g.shape)} vs {tuple(b.shape)}')
+                continue
+            differ = (g != b) & ~m
+            if bool(differ.any()):
+                idx = tuple(differ.nonzero()[0].tolist())
+                failures.append(f'output {i} under {fill}: {int(differ.sum())} of {b.numel()} elements depend on what a fresh buffer held, first at '
+                                f'{list(idx)}: {g[idx].item():#x} against {b[idx].item():#x} from zeros' if not dt == torch.bool else
+                                f'output {i} under {fill}: {int(differ.sum())} of {b.numel()} elements depend on what a fresh buffer held, first at {list(idx)}')
+            if n_ex[i]:
+                held = g[m] == _fill_bits(fill, torch.empty(0, dtype=dt))
+                if not bool(held.all()):
+                    failures.append(f'output {i} under {fill}: {int((~held).sum())} of {n_ex[i]} exempt elements were written: not an exemption')
+    compared = sum(b.numel() for _, b in base) - sum(n_ex)
+    line = f'FIGURE history {what}: {len(base)} outputs, {compared} elements compared, exempt ' + \
+        (', '.join(f'output {ex.index}: {n_ex[ex.index]} ({ex.reader})' for ex in exempt) if exempt else 'none')
+    print(line)
+    if log is not None:
+        log.append(line)
+    assert not failures, f'{what}: ' + '; '.join(failures[:8])
+    return compared, sum(n_ex)

@@ -225,10 +225,11 @@ def test_edge_attention_refuses_a_pitch_outside_the_range(HP):
     assert all(bool((t == CANARY).all()) for t in outs), 'the refused backward wrote to an output'
 
 
-def _canaried_hop(K, g, nt, HP, backward, T=4):
+def _canaried_hop(K, g, nt, HP, backward, T=4, canary=CANARY, amax_word=123):
     """a complete qagnn_hop_args at pitch HP (and a node-type table of T rows) on graph g whose every output, saved buffer and workspace
-    holds the canary -> (struct, the canaried tensors, everything that must stay alive)"""
+    holds the canary (the maximum words: amax_word) -> (struct, the canaried tensors, everything that must stay alive)"""
     from qagnn_amd import _lib
+    _canary = lambda *shape: torch.full(shape, canary, device='cuda')  # noqa: E731
     DP, SP = 4 * HP, -(-2 * HP // 16) * 16
     gen = torch.Generator().manual_seed(HP)
     rnd = lambda *shape: (torch.randn(*shape, generator=gen) * 0.1).cuda()  # noqa: E731
@@ -238,7 +239,7 @@ def _canaried_hop(K, g, nt, HP, backward, T=4):
     X, S, dy = rnd(g.N, DP), rnd(g.N, SP), rnd(g.N, DP)
     h = K._hop_struct(g, HP, 0.25, X, S, nt, prm, True, 1e-5, 0.0, 0, True)
     guarded = [_canary(g.N, 3 * DP), _canary(2, g.Ep, 4), _canary(4, g.N, DP), _canary(5, DP)]
-    amax = torch.full((_lib.HOP_AMAX_WORDS,), 123, dtype=torch.int32, device='cuda')
+    amax = torch.full((_lib.HOP_AMAX_WORDS,), amax_word, dtype=torch.int32, device='cuda')
     K._set_saved(h, *[t.data_ptr() for t in guarded], amax.data_ptr(), g.Ep, g.N * DP * 4)
     if backward:
         sizes, offs = K._grad_sizes(DP, SP, T, g.C)
