@@ -36,6 +36,9 @@ EXPORTS_INFER = ['qagnn_infer_version', 'qagnn_bn_relu_absmax_scratch_elems', 'q
 EXPORTS_LOSS = ['qagnn_loss_version', 'qagnn_choice_loss_f32', 'qagnn_choice_loss_bwd_f32']
 # include/qagnn_hip_explain.h, the extension header of the detailed evaluation: attention export and its trace from the context node (likewise)
 EXPORTS_EXPLAIN = ['qagnn_explain_version', 'qagnn_attn_export_f32', 'qagnn_attn_trace_f32']
+# include/qagnn_hip_defer.h, the extension header of the stack backward that finishes dEkEm and db1 of all layers after its last hop (likewise)
+EXPORTS_DEFER = ['qagnn_defer_version', 'qagnn_stack_bwd_defer_elems', 'qagnn_stack_bwd_deferred_f32']
+DEFER_MAX_HOPS = 16  # QAGNN_DEFER_MAX_HOPS
 TRACE_MAX_N = 1024  # QAGNN_TRACE_MAX_N
 LOSS_KINDS = {'cross_entropy': 0, 'margin_rank': 1}  # QAGNN_LOSS_CROSS_ENTROPY, QAGNN_LOSS_MARGIN_RANK
 LOSS_THREADS = 256  # QAGNN_LOSS_THREADS
@@ -198,7 +201,11 @@ def load_library(path=LIB_PATH):
     lib.qagnn_explain_version.argtypes = []
     lib.qagnn_attn_export_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _vp, _i64, _vp]
     lib.qagnn_attn_trace_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN:
+    lib.qagnn_defer_version.argtypes = []
+    lib.qagnn_stack_bwd_defer_elems.restype = _i64
+    lib.qagnn_stack_bwd_defer_elems.argtypes = [_i32, _i32, _i32, _i32]
+    lib.qagnn_stack_bwd_deferred_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp, _i64, _vp]
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -351,6 +358,13 @@ class HipGraph:
         T4 = (T + 3) // 4 * 4
         w = self.array('err', 16 + 4 + 2 * T4)[16:]
         return w[4:4 + T], w[4 + T4:4 + T4 + T], w[:1]
+
+    def live_classes(self):
+        """(live_cls [C], n_live [1]): the classes with an edge in this batch, ascending in live_cls[:n_live] -- int32 views of the words
+        behind the live k-tiles (include/qagnn_hip_defer.h; the class reduction of the edge backward gives blocks to these only)"""
+        T4 = ((self.N + 31) // 32 + 3) // 4 * 4
+        w = self.array('err', 16 + 4 + 2 * T4 + 4 + self.C)[16 + 4 + 2 * T4:]
+        return w[4:4 + self.C], w[:1]
 
     @property
     def cls_part_rows(self):
@@ -1477,9 +1491,10 @@ class HipKernels(metaclass=_GuardedMeta):
         return ys[k - 1], (KMQ, aa, rows, stats, amax, x_amax if x_amax is not None else ext, s_amax if s_amax is not None else ext)
 
     def stack_bwd(self, graph, HP, qscale, X, S, ntype, prms, batch_stats, eps, p, seeds, saved, dy, need_dX, need_dS, dX_acc=None, tab_col=-1,
-                  overlap=True):
+                  overlap=True, defer=True):
         """-> (dX, dS, [per layer: (dWx_t, dWs_t, dTT, dEkEm, dW1t, db1, dgamma, dbeta, dW2t, db2)]); dX_acc: an existing running total of
-        the stack input's gradient (the output GEMM's share), added to in place."""
+        the stack input's gradient (the output GEMM's share), added to in place.  defer: dEkEm and db1 of all layers are reduced once,
+        behind the last hop (qagnn_stack_bwd_deferred_f32: bit-identical to qagnn_stack_bwd_f32, which defer=False calls)."""
         k = len(prms)
         KMQ, aa, rows, stats = saved[:4]
         p_amax = saved[4].data_ptr() if len(saved) > 4 else None
@@ -1509,5 +1524,9 @@ class HipKernels(metaclass=_GuardedMeta):
                 h.dX, h.accumulate_dX = dX.data_ptr(), (1 if dX_acc is not None else 0)
             if dS is not None:
                 h.dS, h.accumulate_dS = dS.data_ptr(), (0 if l == k - 1 else 1)  # hop k-1's backward runs first
-        self._check(self.lib.qagnn_stack_bwd_f32(hops, k, self._stream()), 'qagnn_stack_bwd_f32')
+        if defer and k <= DEFER_MAX_HOPS:  # (the hops of this chain share one graph and one shape: what the deferral asks for)
+            dws = torch.empty(self.lib.qagnn_stack_bwd_defer_elems(N, DP, graph.cls_part_rows, k), dtype=torch.float32, device=dev)
+            self._check(self.lib.qagnn_stack_bwd_deferred_f32(hops, k, dws.data_ptr(), dws.numel(), self._stream()), 'qagnn_stack_bwd_deferred_f32')
+        else:
+            self._check(self.lib.qagnn_stack_bwd_f32(hops, k, self._stream()), 'qagnn_stack_bwd_f32')
         return dX, dS, grads

@@ -23,7 +23,8 @@ def hashed_files():
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_tn.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_infer.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_loss.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_explain.h')]
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_explain.h'),
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_defer.h')]
 
 
 def source_hash():

@@ -163,6 +163,14 @@ inline LiveTiles live_tiles_of(const qagnn_graph* g) {
   int32_t* const p = g->err + 16;
   return LiveTiles{T, p, p + 4, p + 4 + T4};
 }
+// ... and behind the live k-tiles the LIVE CLASSES of the batch: n_live [4] | list [roundup4(C)] -- the classes with at least one edge,
+// ascending (graph_prep.hip: k_live_classes).  The class reduction of the edge backward gives blocks to these only.
+struct LiveClasses { int32_t *n_live, *list; };
+inline LiveClasses live_classes_of(const qagnn_graph* g) {
+  const LiveTiles lt = live_tiles_of(g);
+  int32_t* const p = lt.list + ((lt.n_tiles + 3) & ~3);
+  return LiveClasses{p, p + 4};
+}
 
 // producers that can leave max |output| behind for the three-MFMA GEMM form (elementwise.hip; amax = nullptr: plain launch)
 int launch_gelu_dropout(const float* X, const float* dY, float* out, int64_t n, float p, uint64_t seed, uint32_t* amax, float* amax_part,
@@ -170,7 +178,12 @@ int launch_gelu_dropout(const float* X, const float* dY, float* out, int64_t n, 
 int64_t gelu_amax_scratch_elems(int64_t n);
 int launch_bn_relu_bwd_colsum(const float* dR, const float* Hh, float* dH, int ld, int R, int Cc, const float* mean, const float* invstd,
                               const float* scale, const float* shift, const float* gamma, const float* sum_dy, const float* sum_dy_hhat,
-                              float inv_rows, const float* roww, float* colsum, float* workspace, uint32_t* amax, hipStream_t stream);
+                              float inv_rows, const float* roww, float* colsum, float* workspace, uint32_t* amax, bool finalize, hipStream_t stream);
+// reductions whose result nothing inside a stack of hops reads, finished for all its layers in one launch each (hop.hip: stack_bwd_impl)
+constexpr int DEFER_LAYERS_MAX = 16;
+struct LayerOut { float* p[DEFER_LAYERS_MAX]; };  // where each layer's result goes
+int64_t bn_colsum_part_elems(int R, int Cc);  // floats of column partials launch_bn_relu_bwd_colsum leaves in its workspace
+int launch_colreduce_final_layers(const float* part, int64_t layer_stride, int layers, const LayerOut& outs, int R, int Cc, hipStream_t stream);
 int launch_bn_stats_finalize(const float* part, int n_tiles, int R, int Cc, const float* gamma, const float* beta, float eps, float* stats,
                              float* run_mean, float* run_var, int64_t* nbt, int d, float momentum, float unbias, int ones_col, uint32_t* amax_bound,
                              hipStream_t stream);
@@ -179,7 +192,10 @@ int launch_edge_attn_fwd(const qagnn_graph* g, const float* KMQ, int32_t ldk, co
                          float* score, float* a, float* alpha, float* aggr, int32_t lda, float* amax_part /* [N] or nullptr */, hipStream_t stream);
 int launch_edge_attn_bwd(const qagnn_graph* g, const float* KMQ, int32_t ldk, const float* EkEm, int32_t lde, int32_t HP, float qscale,
                          const float* a, const float* alpha, const float* G, int32_t ldg, float* dKMQ, float* dEkEm, float* ga, float* rs,
-                         float* cls_part, float* amax_part /* [3 N] or nullptr */, uint32_t* amax_slot, hipStream_t stream);
+                         float* cls_part, float* amax_part /* [3 N] or nullptr */, uint32_t* amax_slot, bool reduce_now, hipStream_t stream);
+// the class reduction the call above ends with, for several layers at once (edge_attn.hip)
+int launch_cls_reduce(const qagnn_graph* g, int32_t HP, float* cls_part, int64_t layer_stride, int layers, const LayerOut& out, int32_t lde,
+                      hipStream_t stream);
 int launch_amax_reduce(const float* part, int64_t n, uint32_t* slot, hipStream_t stream);  // max of n non-negative floats -> *slot (elementwise.hip)
 // max relu(scale * H + shift) over R x Cc -> *slot, through per-block partials in `part` (infer.hip: qagnn_bn_relu_absmax_f32 after its checks)
 int launch_bn_relu_absmax(const float* H, int ldh, int R, int Cc, const float* scale, const float* shift, uint32_t* slot, float* part, hipStream_t stream);

@@ -442,13 +442,27 @@ __global__ __launch_bounds__(256) void k_edge_bwd_tgt(const int* __restrict__ ro
 
 // one wave per class chunk (<= QAGNN_CLS_CHUNK edges of one class inside one position group), walked 64 edges at a time
 // (chunks of 256 edges were measured: 4x fewer partials for the big classes, but the class pass itself went 65 -> 89 us).
+// amax_part != nullptr: the launch also folds the node-side kernels' per-node maxima (npart non-negative floats, complete: those kernels
+// precede this one on the stream) into *amax_slot -- its first CLS_AMAX_BLOCKS blocks a slice each, one atomic per block (common.h), before
+// any of them may leave: the hop's next products read that word, while the class reduction behind this kernel may run much later.
+constexpr int CLS_AMAX_BLOCKS = 64;
 __global__ __launch_bounds__(256) void k_edge_bwd_cls(const int* __restrict__ n_chunks, const int* __restrict__ chunk_beg,
                                                       const int* __restrict__ chunk_len, const int* __restrict__ src_c,
                                                       const int* __restrict__ tgt_c, const int* __restrict__ pos_c,
                                                       const float* __restrict__ KMQ, int ldk, int HP,
                                                       const float* __restrict__ alpha, const float* __restrict__ gsb,
-                                                      const float* __restrict__ G, int ldg, float* __restrict__ cls_part, int N) {
+                                                      const float* __restrict__ G, int ldg, float* __restrict__ cls_part, int N,
+                                                      const float* __restrict__ amax_part, int npart, uint32_t* __restrict__ amax_slot) {
   __shared__ float4 slab[2][4][SLAB_ROWS];  // gs | alpha of the current 64 edges
+  if (amax_part) {  // (kernel argument: uniform over the block, as the barrier inside block_amax_merge needs)
+    const int nfold = min((int)gridDim.x, CLS_AMAX_BLOCKS);
+    if ((int)blockIdx.x < nfold) {
+      __shared__ float red[16];
+      float m = 0.f;
+      for (int i = blockIdx.x * 256 + threadIdx.x; i < npart; i += nfold * 256) m = fmaxf(m, amax_part[i]);
+      block_amax_merge(m, amax_slot, red);
+    }
+  }
   // chunks are in (position group, class) order: the remap gives every XCD a contiguous run of groups, whose node rows its L2
   // then serves (the grid is sized for max_chunks, so the remap runs over the blocks that really have a chunk)
   const int nch = *n_chunks, nb_real = (nch + 3) >> 2;
@@ -492,16 +506,25 @@ __global__ __launch_bounds__(256) void k_edge_bwd_cls(const int* __restrict__ n_
   }
 }
 
-// ordered sum of a class's chunk partials over all position groups, two stages.  Stage 1: block (c, s) sums the chunks of class c
-// in the groups g = s, s + S, ... (S = QAGNN_CLS_SLICES): columns x partitions, partition p takes the slice's chunks number
-// p, p + P, ..., partitions added in order.  Stage 2 adds the S slices in order.  (One block per class left the largest class --
-// the self loops of the KG nodes, ~900 partials -- as a 100-deep chain of dependent loads: 58 of the stage's 62 us.)
-__global__ __launch_bounds__(1024) void k_cls_reduce(const int* __restrict__ chunkptr, const float* __restrict__ cls_part,
-                                                     float* __restrict__ slices, int DP2, int C, int NG) {
+// ordered sum of a class's chunk partials over all position groups, two stages.  Stage 1: block (i, s, l) sums the chunks of the i-th
+// LIVE class c of the batch (common.h: live_classes_of) in the groups g = s, s + S, ... (S = QAGNN_CLS_SLICES) of layer l: columns x
+// partitions, partition p takes the slice's chunks number p, p + P, ..., partitions added in order.  Stage 2 adds the S slices in order
+// and gives the classes without an edge their zeros.  (One block per class left the largest class -- the self loops of the KG nodes,
+// ~900 partials -- as a 100-deep chain of dependent loads: 58 of the stage's 62 us.)
+// The grid is sized for all C classes (launch shapes follow capacities only); a block behind the live count leaves before it loads
+// anything else -- a CSQA batch uses a fraction of its classes, and a block's cost here is fixed cost: its loads of the chunk ranges, two
+// barriers, the LDS sum.  Layers: the partials of layer l lie l * layer_stride floats behind cls_part, its slices likewise behind
+// `slices` (one launch for the whole stack: hop.hip).
+__global__ __launch_bounds__(1024) void k_cls_reduce(const int* __restrict__ n_live, const int* __restrict__ live_cls,
+                                                     const int* __restrict__ chunkptr, const float* __restrict__ cls_part,
+                                                     float* __restrict__ slices, int64_t layer_stride, int DP2, int C, int NG) {
   extern __shared__ float4 sm4[];
   // the class's chunk ranges of all groups first (one load per thread, not 2 dependent loads per group and thread)
   __shared__ int cp_lo[QAGNN_CLS_GROUPS], cp_hi[QAGNN_CLS_GROUPS];
-  const int c = blockIdx.x, sl = blockIdx.y;
+  if ((int)blockIdx.x >= min(*n_live, C)) return;
+  const int c = __builtin_amdgcn_readfirstlane(live_cls[blockIdx.x]), sl = blockIdx.y;
+  cls_part += (int64_t)blockIdx.z * layer_stride;
+  slices += (int64_t)blockIdx.z * layer_stride;
   if (threadIdx.x < NG) {
     cp_lo[threadIdx.x] = chunkptr[threadIdx.x * C + c];
     cp_hi[threadIdx.x] = chunkptr[threadIdx.x * C + c + 1];
@@ -528,26 +551,21 @@ __global__ __launch_bounds__(1024) void k_cls_reduce(const int* __restrict__ chu
     st4(slices + ((int64_t)c * QAGNN_CLS_SLICES + sl) * DP2 + threadIdx.x * 4, s);
   }
 }
-// amax_part != nullptr: the launch also folds the node-side kernels' per-node maxima (npart non-negative floats) into *amax_slot -- every
-// block a slice, one atomic per block (common.h): the last small kernel of the edge backward carries the reduction instead of a launch of its own
-__global__ __launch_bounds__(256) void k_cls_reduce2(const float* __restrict__ slices, float* __restrict__ dEkEm, int lde, int DP2, int C,
-                                                     const float* __restrict__ amax_part, int npart, uint32_t* __restrict__ amax_slot) {
+// (blockIdx.y: the layer.  A class is live exactly when it has an edge: cls_count is what the live list was made from.)
+__global__ __launch_bounds__(256) void k_cls_reduce2(const float* __restrict__ slices, int64_t layer_stride, const int* __restrict__ cls_count,
+                                                     const LayerOut out, int lde, int DP2, int C) {
   const int ncol4 = DP2 >> 2;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < C * ncol4) {
-    const int c = i / ncol4, col4 = i - c * ncol4;
-    const float* p = slices + (int64_t)c * QAGNN_CLS_SLICES * DP2 + col4 * 4;
-    float4 s = ld4(p);
+  if (i >= C * ncol4) return;
+  const int c = i / ncol4, col4 = i - c * ncol4;
+  float4 s = zero4();
+  if (cls_count[c] > 0) {
+    const float* p = slices + (int64_t)blockIdx.y * layer_stride + (int64_t)c * QAGNN_CLS_SLICES * DP2 + col4 * 4;
+    s = ld4(p);
 #pragma unroll
     for (int q = 1; q < QAGNN_CLS_SLICES; ++q) s = add4(s, ld4(p + (int64_t)q * DP2));
-    st4(dEkEm + (int64_t)c * lde + col4 * 4, s);
   }
-  if (amax_part) {
-    __shared__ float red[16];
-    float m = 0.f;
-    for (int k = i; k < npart; k += (int)(gridDim.x * blockDim.x)) m = fmaxf(m, amax_part[k]);
-    block_amax_merge(m, amax_slot, red);
-  }
+  st4(out.p[blockIdx.y] + (int64_t)c * lde + col4 * 4, s);
 }
 
 static int check_common(const qagnn_graph* g, const float* KMQ, int ldk, const float* EkEm, int lde, int HP, const char* who) {
@@ -593,14 +611,16 @@ extern "C" int qagnn_edge_attn_fwd_f32(const qagnn_graph* g, const float* KMQ, i
 extern "C" int qagnn_edge_attn_bwd_f32(const qagnn_graph* g, const float* KMQ, int32_t ldk, const float* EkEm, int32_t lde,
                                        int32_t HP, float qscale, const float* a, const float* alpha, const float* G, int32_t ldg,
                                        float* dKMQ, float* dEkEm, float* ga, float* rs, float* cls_part, qagnn_stream_t stream_) {
-  return launch_edge_attn_bwd(g, KMQ, ldk, EkEm, lde, HP, qscale, a, alpha, G, ldg, dKMQ, dEkEm, ga, rs, cls_part, nullptr, nullptr, (hipStream_t)stream_);
+  return launch_edge_attn_bwd(g, KMQ, ldk, EkEm, lde, HP, qscale, a, alpha, G, ldg, dKMQ, dEkEm, ga, rs, cls_part, nullptr, nullptr, true, (hipStream_t)stream_);
 }
 
 // amax_part != nullptr: [3 N] floats of scratch for max |d M row|, |d Q row|, |d K row| per node (the three node-side kernels), folded into
-// *amax_slot (max |d K|M|Q|, bit pattern; the caller zeroed it) by the last kernel of the call
+// *amax_slot (max |d K|M|Q|, bit pattern; the caller zeroed it) by the class pass (k_edge_bwd_cls)
+// reduce_now == false: the call ends with the chunk partials in cls_part and leaves dEkEm alone; the caller owes launch_cls_reduce over
+// that cls_part (hop.hip: one launch for all layers of a stack, after the last hop -- nothing inside the stack reads dEkEm)
 int qagnn::launch_edge_attn_bwd(const qagnn_graph* g, const float* KMQ, int32_t ldk, const float* EkEm, int32_t lde, int32_t HP, float qscale,
                                 const float* a, const float* alpha, const float* G, int32_t ldg, float* dKMQ, float* dEkEm, float* ga, float* rs,
-                                float* cls_part, float* amax_part, uint32_t* amax_slot, hipStream_t stream) {
+                                float* cls_part, float* amax_part, uint32_t* amax_slot, bool reduce_now, hipStream_t stream) {
   TimedScope timed(3, stream);
   int rc = check_common(g, KMQ, ldk, EkEm, lde, HP, "edge_attn_bwd");
   if (rc != QAGNN_OK) return rc;
@@ -618,18 +638,35 @@ int qagnn::launch_edge_attn_bwd(const qagnn_graph* g, const float* KMQ, int32_t 
   k_edge_bwd_tgt<<<nb, 256, 0, stream>>>(g->rowptr_t, g->src_t, g->pos_t, KMQ, ldk, HP, ga, dKMQ, g->N, g->err + 4, amax_part ? amax_part + 2 * (int64_t)g->N : nullptr);
   QAGNN_LAUNCH_CHECK("k_edge_bwd_tgt");
   k_edge_bwd_cls<<<cdiv(g->max_chunks, 4), 256, 0, stream>>>(g->n_chunks, g->chunk_beg, g->chunk_len, g->src_c, g->tgt_c, g->pos_c,
-                                                             KMQ, ldk, HP, alpha, ga, G, ldg, cls_part, g->N);
+                                                             KMQ, ldk, HP, alpha, ga, G, ldg, cls_part, g->N, amax_slot ? amax_part : nullptr,
+                                                             3 * g->N, amax_slot);
   QAGNN_LAUNCH_CHECK("k_edge_bwd_cls");
+  if (!reduce_now) return QAGNN_OK;
+  LayerOut out = {};
+  out.p[0] = dEkEm;
+  return launch_cls_reduce(g, HP, cls_part, 0, 1, out, lde, stream);
+}
+
+// dEkEm of `layers` layers from their chunk partials: layer l's cls_part (as launch_edge_attn_bwd takes it: the chunk partials, the
+// slices behind them) lies l * layer_stride floats behind cls_part, its result goes to out.p[l].  Two launches whatever the layer count.
+int qagnn::launch_cls_reduce(const qagnn_graph* g, int32_t HP, float* cls_part, int64_t layer_stride, int layers, const LayerOut& out, int32_t lde,
+                             hipStream_t stream) {
+  TimedScope timed(3, stream);  // (part of the edge backward, wherever it runs)
+  QAGNN_REQUIRE(g && cls_part && layers >= 1 && layers <= DEFER_LAYERS_MAX, QAGNN_EINVAL, "cls_reduce: %d layers (1..%d)", layers, DEFER_LAYERS_MAX);
+  QAGNN_REQUIRE(HP > 0 && HP % 4 == 0 && HP <= 64 && lde >= 8 * HP && lde % 4 == 0 && layer_stride % 4 == 0, QAGNN_EINVAL, "cls_reduce: bad pitch");
+  for (int l = 0; l < layers; ++l) QAGNN_REQUIRE(out.p[l] && aligned16(out.p[l]), QAGNN_EINVAL, "cls_reduce: bad output pointer of layer %d", l);
+  const int DP2 = 8 * HP;
   // 1024 threads = 9 partitions per (class, slice) where the large classes have hundreds of chunk partials; a small graph (the
-  // reference's 10-subgraph mini-batch: a handful of chunks per class) only pays for launching 2 448 x 16 waves: 256 threads there.
+  // reference's 10-subgraph mini-batch: a handful of chunks per class) only pays for launching 16-wave blocks: 256 threads there.
   // (The choice follows g->Ep, the capacity the arrays are laid out for: a fixed function of the launch shape, like every other grid here.)
   const int cr_threads = g->Ep < 65536 && DP2 / 4 <= 128 ? 256 : 1024;
   const int P = cr_threads / (DP2 / 4);
+  const LiveClasses lc = live_classes_of(g);
   float* slices = cls_part + (int64_t)g->max_chunks * DP2;  // [C][QAGNN_CLS_SLICES][DP2] behind the chunk partials
-  k_cls_reduce<<<dim3(g->C, QAGNN_CLS_SLICES), cr_threads, (size_t)P * (DP2 / 4) * sizeof(float4), stream>>>(g->chunkptr, cls_part, slices, DP2,
-                                                                                                          g->C, g->n_groups);
+  k_cls_reduce<<<dim3(g->C, QAGNN_CLS_SLICES, layers), cr_threads, (size_t)P * (DP2 / 4) * sizeof(float4), stream>>>(
+      lc.n_live, lc.list, g->chunkptr, cls_part, slices, layer_stride, DP2, g->C, g->n_groups);
   QAGNN_LAUNCH_CHECK("k_cls_reduce");
-  k_cls_reduce2<<<cdiv((int64_t)g->C * (DP2 / 4), 256), 256, 0, stream>>>(slices, dEkEm, lde, DP2, g->C, amax_slot ? amax_part : nullptr, 3 * g->N, amax_slot);
+  k_cls_reduce2<<<dim3(cdiv((int64_t)g->C * (DP2 / 4), 256), layers), 256, 0, stream>>>(slices, layer_stride, g->cls_count, out, lde, DP2, g->C);
   QAGNN_LAUNCH_CHECK("k_cls_reduce2");
   return QAGNN_OK;
 }

@@ -96,12 +96,16 @@ __global__ __launch_bounds__(256) void k_colreduce(const float* __restrict__ X, 
 // ordered sum of the chunk partials: 64 outputs x 16 chunk partitions per block (partition q takes chunks q, q+16, ...),
 // partitions combined in fixed order.  16 partitions because the kernel is pure latency: 500 partials per output behind
 // 4 partitions took 8 us, 31 times per step.
+// blockIdx.y: the layer -- its partials lie layer_stride floats behind the previous layer's, its sums go to outs.p[layer] (one launch for
+// a gradient of every layer of a stack: launch_colreduce_final_layers)
 constexpr int CF_Q = 16;
-__global__ __launch_bounds__(64 * CF_Q) void k_colreduce_final(const float* __restrict__ part, float* __restrict__ out, int nchunks,
+__global__ __launch_bounds__(64 * CF_Q) void k_colreduce_final(const float* __restrict__ part, int64_t layer_stride, const LayerOut outs, int nchunks,
                                                                int tot, float out_scale) {
   __shared__ float red[CF_Q][64];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int o = blockIdx.x * 64 + lane;
+  part += (int64_t)blockIdx.y * layer_stride;
+  float* const __restrict__ out = outs.p[blockIdx.y];
   float s0 = 0.f, s1 = 0.f;
   if (o < tot) {
     int c = q;
@@ -461,7 +465,7 @@ extern "C" int qagnn_colreduce_f32(int32_t mode, const float* X, int32_t ldx, co
   }
   QAGNN_LAUNCH_CHECK("k_colreduce");
   const int tot = nout * Cc;
-  k_colreduce_final<<<cdiv(tot, 64), 64 * CF_Q, 0, stream>>>(workspace, out, grid.y, tot, out_scale);
+  k_colreduce_final<<<cdiv(tot, 64), 64 * CF_Q, 0, stream>>>(workspace, 0, LayerOut{{out}}, grid.y, tot, out_scale);
   QAGNN_LAUNCH_CHECK("k_colreduce_final");
   return QAGNN_OK;
 }
@@ -677,9 +681,19 @@ extern "C" int qagnn_sin_basis_f32(const float* score, const float* js, float* o
 // qagnn_bn_relu_bwd_f32 that also returns colsum[c] = sum_r dH[r][c] (the bias gradient of the Linear in front of the BatchNorm)
 namespace qagnn {
 // amax != nullptr: the launch also merges max |dH| into that word
+// finalize == false: the column partials stay in `workspace` (bn_colsum_part_elems floats) and colsum is left alone; the caller owes
+// launch_colreduce_final_layers over them
+int64_t bn_colsum_part_elems(int R, int Cc) { return (int64_t)cdiv(R, 4 * cr_wr(R)) * Cc; }
+int launch_colreduce_final_layers(const float* part, int64_t layer_stride, int layers, const LayerOut& outs, int R, int Cc, hipStream_t stream) {
+  QAGNN_REQUIRE(part && layers >= 1 && layers <= DEFER_LAYERS_MAX && layer_stride >= 0, QAGNN_EINVAL, "colreduce_final: %d layers", layers);
+  for (int l = 0; l < layers; ++l) QAGNN_REQUIRE(outs.p[l], QAGNN_EINVAL, "colreduce_final: null output of layer %d", l);
+  k_colreduce_final<<<dim3(cdiv(Cc, 64), layers), 64 * CF_Q, 0, stream>>>(part, layer_stride, outs, cdiv(R, 4 * cr_wr(R)), Cc, 1.0f);
+  QAGNN_LAUNCH_CHECK("k_colreduce_final");
+  return QAGNN_OK;
+}
 int launch_bn_relu_bwd_colsum(const float* dR, const float* Hh, float* dH, int ld, int R, int Cc, const float* mean, const float* invstd,
                               const float* scale, const float* shift, const float* gamma, const float* sum_dy, const float* sum_dy_hhat,
-                              float inv_rows, const float* roww, float* colsum, float* workspace, uint32_t* amax, hipStream_t stream) {
+                              float inv_rows, const float* roww, float* colsum, float* workspace, uint32_t* amax, bool finalize, hipStream_t stream) {
   dim3 grid(cdiv(Cc, 256), cdiv(R, 4 * cr_wr(R)));
   if (cr_wr(R) == CR_WR_SMALL)
     k_bn_relu_bwd_colsum<CR_WR_SMALL><<<grid, 256, 0, stream>>>(dR, Hh, dH, ld, R, Cc, mean, invstd, scale, shift, gamma, sum_dy, sum_dy_hhat,
@@ -688,9 +702,8 @@ int launch_bn_relu_bwd_colsum(const float* dR, const float* Hh, float* dH, int l
     k_bn_relu_bwd_colsum<CR_WR_BIG><<<grid, 256, 0, stream>>>(dR, Hh, dH, ld, R, Cc, mean, invstd, scale, shift, gamma, sum_dy, sum_dy_hhat,
                                                               inv_rows, roww, workspace, amax);
   QAGNN_LAUNCH_CHECK("k_bn_relu_bwd_colsum");
-  k_colreduce_final<<<cdiv(Cc, 64), 64 * CF_Q, 0, stream>>>(workspace, colsum, grid.y, Cc, 1.0f);
-  QAGNN_LAUNCH_CHECK("k_colreduce_final");
-  return QAGNN_OK;
+  if (!finalize) return QAGNN_OK;
+  return launch_colreduce_final_layers(workspace, 0, 1, LayerOut{{colsum}}, R, Cc, stream);
 }
 }  // namespace qagnn
 
@@ -704,7 +717,7 @@ extern "C" int qagnn_bn_relu_bwd_colsum_f32(const float* dR, const float* Hh, fl
   QAGNN_REQUIRE(R > 0 && Cc > 0 && Cc % 4 == 0 && ld % 4 == 0, QAGNN_EINVAL, "bn_relu_bwd_colsum: bad sizes");
   QAGNN_REQUIRE(ld >= Cc, QAGNN_EINVAL, "bn_relu_bwd_colsum: ld=%d below Cc=%d", ld, Cc);
   return launch_bn_relu_bwd_colsum(dR, Hh, dH, ld, R, Cc, mean, invstd, scale, shift, gamma, sum_dy, sum_dy_hhat, inv_rows, roww, colsum, workspace,
-                                   nullptr, stream);
+                                   nullptr, true, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -553,6 +553,33 @@ __global__ __launch_bounds__(1024) void k_live_tiles(const int* __restrict__ row
   if (threadIdx.x == 0) *n_live = L;
 }
 
+// Live classes (common.h: live_classes_of): the classes with at least one edge -- hence at least one chunk -- in this batch, ascending, and
+// their number.  The class reduction of the edge backward launches blocks for these only (edge_attn.hip).  One block walks the class counts
+// 1024 at a time; a class's slot is the number of live classes before it (ballots inside a wave, the waves' counts through LDS): no
+// atomics, the list is a pure function of cls_count.  Runs behind k_cls_hist, which completes the counts.
+__global__ __launch_bounds__(1024) void k_live_classes(const int* __restrict__ cls_count, int C, int* __restrict__ list, int* __restrict__ n_live) {
+  __shared__ int wc[16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));  // lanes below this one
+  int base = 0;
+  for (int c0 = 0; c0 < C; c0 += 1024) {
+    const int c = c0 + (int)threadIdx.x;
+    const bool live = c < C && cls_count[c] > 0;
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) wc[w] = __builtin_popcountll(m);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int i = 0; i < 16; ++i) {
+      if (i < w) off += wc[i];
+      tot += wc[i];
+    }
+    if (live) list[off + __builtin_popcountll(m & lt)] = c;
+    base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *n_live = base;
+}
+
 // the work table of the live-tile weight gradient as its kernels see it (qagnn_tn_work_table: tests)
 __global__ void k_tn_work_table(const int* __restrict__ n_live, int T, int S, int chunk_tiles, int* __restrict__ out) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
@@ -631,6 +658,7 @@ static carved carve(qagnn_graph* g, int32_t* storage, int N, int E, int R, int T
   g->chunk_cls = take(maxch); g->chunk_beg = take(maxch); g->chunk_len = take(maxch);
   g->n_chunks = take(4); g->err = take(16);  // err[4 .. 12]: the XCD partition of the node blocks (k_xcd_partition)
   take(4 + 2 * up4(cdiv(N, 32)));           // the live k-tiles behind err: n_live | live_tiles | live_list (common.h: live_tiles_of)
+  take(4 + up4(C));                         // the live classes behind those: n_live_cls | live_cls (common.h: live_classes_of)
   // ---- scratch; the zero-initialised region comes first (cls_count, which sits just before it, must be zero too) ----
   cv.cnt_s = take(N); cv.cnt_t = take(N);
   cv.es = take(Ep); cv.et = take(Ep); cv.ec = take(Ep);
@@ -646,6 +674,9 @@ static int class_pass(qagnn_graph* g, int32_t* hist, int32_t* gc_cnt, int32_t* g
   const int* Ep = g->rowptr_s + g->N;  // device: the true E' (g->Ep is the capacity the arrays and the grids are sized for)
   k_cls_hist<<<nblk, 256, C * sizeof(int), stream>>>(g->cls_s, hist, g->cls_count, Ep, C);
   QAGNN_LAUNCH_CHECK("k_cls_hist");
+  const LiveClasses lc = live_classes_of(g);
+  k_live_classes<<<1, 1024, 0, stream>>>(g->cls_count, C, lc.list, lc.n_live);
+  QAGNN_LAUNCH_CHECK("k_live_classes");
   k_grp_count<<<cdiv(pairs, TB), TB, 0, stream>>>(hist, gc_cnt, nblk, C, gb, NG);
   QAGNN_LAUNCH_CHECK("k_grp_count");
   k_chunk_counts<<<cdiv(pairs, 1024), 1024, 0, stream>>>(gc_cnt, nch, pairs);
@@ -683,6 +714,7 @@ extern "C" int64_t qagnn_graph_storage_elems(int32_t N, int32_t E, int32_t R, in
   tot += up4(nblk * C);       // per-block class histograms
   const int64_t tiles = ((int64_t)N + 31) / 32;
   tot += 2 * up4(tiles) + up4(4) + up4(tiles + 1);  // live_tiles, live_list, n_live, the scan of the flags
+  tot += up4(4) + up4(C);     // n_live_cls, live_cls
   return tot;
 }
 

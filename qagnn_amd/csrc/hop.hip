@@ -10,6 +10,7 @@
 // No allocation, no synchronisation: the caller hands in every buffer, including one scratch region whose size comes from
 // qagnn_hop_{fwd,bwd}_workspace_elems().
 #include "common.h"
+#include "../../include/qagnn_hip_defer.h"
 
 #include <mutex>
 
@@ -59,6 +60,17 @@ struct HopBwdWs : HopWs {
   float* const pkws = take(hop_pack_elems(DP));  // packed B images of the data-gradient products: main stream only
   float* const ampart = take(max64(3 * N, gelu_amax_scratch_elems(N * DP)));
   static HopBwdWs layout(int N, int Ep, int DP, int SP, int cls_part_rows, float* base) { return {{base}, N, Ep, DP, SP, cls_part_rows}; }
+};
+
+// What a stack's backward may finish after its last hop (include/qagnn_hip_defer.h): the class-table gradient dEkEm and the bias gradient
+// db1 of every layer.  Nothing inside the stack reads either, so each hop leaves the partial sums in a region of its own here -- the hops
+// share ONE workspace, whose cls_part / crws the next hop overwrites -- and three launches reduce all layers at once.
+struct StackDeferWs : HopWs {
+  const int64_t N, DP, cls_part_rows, k;
+  const int64_t cls_stride = up4(cls_part_rows * 2 * DP), db1_stride = up4(bn_colsum_part_elems((int)N, (int)DP));
+  float* const cls_part = take(k * cls_stride);  // layer l: as HopBwdWs::cls_part, l * cls_stride floats in
+  float* const db1_part = take(k * db1_stride);  // layer l: the column partials of launch_bn_relu_bwd_colsum
+  static StackDeferWs layout(int N, int DP, int cls_part_rows, int k, float* base) { return {{base}, N, DP, cls_part_rows, k}; }
 };
 
 static int check_hop(const qagnn_hop_args* h, const char* who, bool bwd = false) {  // bwd: the entry point runs the backward
@@ -283,7 +295,8 @@ static int stream_after(hipStream_t to, hipStream_t from, hipEvent_t ev) {
 // side stream they leave the chain (fork after each of their operands is complete, join at the end of the stack).  What they read
 // from the workspace (d out, d h1, d K|M|Q) lives in buffer set `set`; the caller alternates sets from hop to hop and makes the
 // main stream wait for `*done` before it reuses one, so the side stream may lag the main stream by a whole hop.
-static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss, int set, hipEvent_t* done) {
+// d != nullptr: layer l's dEkEm and db1 stop at their partial sums, in d's regions of that layer (stack_bwd_impl finishes them)
+static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss, int set, hipEvent_t* done, const StackDeferWs* d = nullptr, int l = 0) {
   // (h has passed check_hop: stack_bwd_impl validates every hop before the first enqueue)
   QAGNN_REQUIRE(h->dy && h->dWx_t && h->dTT && h->dEkEm && h->dW1t && h->db1 && h->dbn && h->dW2t && h->db2, QAGNN_EINVAL,
                 "hop_bwd: null gradient pointer");
@@ -326,7 +339,8 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   // BatchNorm + ReLU backward: dbn[0] = d beta, dbn[1] = d gamma, then d h1
   HOP_TRY(qagnn_colreduce_f32(2, bufB, DP, h->h1, DP, N, DP, nullptr, 1, mean, invstd, scale, shift, nullptr, 1.0f, h->dbn, w.crws, stream));
   HOP_TRY(launch_bn_relu_bwd_colsum(bufB, h->h1, bufC, DP, N, DP, mean, invstd, scale, shift, h->gamma, h->dbn, h->dbn + DP,
-                                    h->batch_stats ? (float)(1.0 / (double)N) : 0.f, nullptr, h->db1, w.crws, w_dh1, (hipStream_t)stream));
+                                    h->batch_stats ? (float)(1.0 / (double)N) : 0.f, nullptr, h->db1, d ? d->db1_part + l * d->db1_stride : w.crws, w_dh1,
+                                    d == nullptr, (hipStream_t)stream));
   // first Linear (db1 = colsum(d h1) came out of the pass above)
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
   HOP_TRY(hop_tn(h, h->aggr, DP, nullptr, 0, bufC, DP, h->dW1t, nullptr, nullptr, w_aggr, nullptr, w_dh1, w.tnws, wstream));
@@ -335,8 +349,8 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
   nn_scaled(h, &gg, w_dh1);
   HOP_TRY(hop_nn(h, &gg, h->W1t, DP, nullptr, 0, w.pkws, stream));
   // attention backward
-  HOP_TRY(launch_edge_attn_bwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, h->a, h->alpha, bufB, DP, dKMQ, h->dEkEm, w.gab, w.rs, w.cls_part,
-                               h2 ? w.ampart : nullptr, w_dkmq, (hipStream_t)stream));
+  HOP_TRY(launch_edge_attn_bwd(h->g, h->KMQ, 3 * DP, h->EkEm, 2 * DP, h->HP, h->qscale, h->a, h->alpha, bufB, DP, dKMQ, h->dEkEm, w.gab, w.rs,
+                               d ? d->cls_part + l * d->cls_stride : w.cls_part, h2 ? w.ampart : nullptr, w_dkmq, d == nullptr, (hipStream_t)stream));
   // projection: weight gradients, node-type-table gradient, data gradients
   if (ss->side) HOP_TRY(stream_after(ss->side, ss->main, ss->take()));
   if (SP > 0 && h->dWs_t == h->dWx_t + (int64_t)DP * 3 * DP) {  // the two gradients are one [DP + SP, 3 DP] matrix: one product
@@ -407,10 +421,31 @@ static int zero_bwd_words(const qagnn_hop_args* hops, int k, hipStream_t main) {
   return QAGNN_OK;
 }
 
+// The deferral needs hops of one shape on one graph (one launch covers all layers) and no more layers than the launches' pointer table
+// holds.  A stack that is not is REFUSED when it comes with a deferral workspace: the caller asked for something it would not get
+static_assert(DEFER_LAYERS_MAX == QAGNN_DEFER_MAX_HOPS, "the header states the pointer table's length");
+static bool stack_defers(const qagnn_hop_args* hops, int k) {
+  if (k > DEFER_LAYERS_MAX) return false;
+  for (int l = 1; l < k; ++l)
+    if (hops[l].g != hops[0].g || hops[l].N != hops[0].N || hops[l].DP != hops[0].DP || hops[l].HP != hops[0].HP) return false;
+  return true;
+}
+
 // k hops, last first; the buffer sets alternate and the main stream joins the weight-gradient stream before it returns
-static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main) {
+// defer_ws != nullptr: qagnn_stack_bwd_deferred_f32
+static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main, float* defer_ws = nullptr, int64_t defer_elems = 0) {
   // every hop, before an event is recorded or a kernel enqueued: a refused stack leaves every buffer as it was
   for (int l = 0; l < k; ++l) HOP_TRY(check_hop(&hops[l], k > 1 ? "stack_bwd" : "hop_bwd", true));
+  const bool defer = defer_ws != nullptr;
+  QAGNN_REQUIRE(!defer || stack_defers(hops, k), QAGNN_EUNSUPPORTED,
+                "stack_bwd: a deferral workspace with %d hops that do not share one graph, N, DP and HP, or with more than %d hops", k, DEFER_LAYERS_MAX);
+  // (without a deferral: the layout of no layers at no address -- nothing reads it)
+  const StackDeferWs dws = defer ? StackDeferWs::layout(hops[0].N, hops[0].DP, hop_cls_part_rows(hops[0].g), k, defer_ws) : StackDeferWs::layout(0, 0, 0, 0, nullptr);
+  if (defer) {
+    QAGNN_REQUIRE(aligned16(defer_ws) && defer_elems >= dws.total, QAGNN_EINVAL, "stack_bwd: deferral workspace of %lld floats is too small (%lld) or unaligned",
+                  (long long)defer_elems, (long long)dws.total);
+    for (int l = 0; l < k; ++l) QAGNN_REQUIRE(hops[l].dEkEm && hops[l].db1, QAGNN_EINVAL, "stack_bwd: null gradient pointer");
+  }
   HOP_TRY(zero_bwd_words(hops, k, main));
   SideSync ss;
   HOP_TRY(side_sync_init(&ss, main, (hipStream_t)hops[k - 1].side_stream));
@@ -422,7 +457,14 @@ static int stack_bwd_impl(const qagnn_hop_args* hops, int k, hipStream_t main) {
       hipError_t he = hipStreamWaitEvent(ss.main, done[set], 0);
       if (he != hipSuccess) { set_error("stack_bwd: hipStreamWaitEvent failed: %s", hipGetErrorString(he)); rc = QAGNN_EHIP; break; }
     }
-    rc = hop_bwd_one(&hops[l], hop_amax_stack(hops, k, l), &ss, set, &done[set]);
+    rc = hop_bwd_one(&hops[l], hop_amax_stack(hops, k, l), &ss, set, &done[set], defer ? &dws : nullptr, l);
+  }
+  // the deferred reductions of all layers, on the main stream behind the last hop: each in the order of additions of its per-hop launch
+  if (defer && rc == QAGNN_OK) {
+    LayerOut cls = {}, db1 = {};
+    for (int l = 0; l < k; ++l) cls.p[l] = hops[l].dEkEm, db1.p[l] = hops[l].db1;
+    rc = launch_cls_reduce(hops[0].g, hops[0].HP, dws.cls_part, dws.cls_stride, k, cls, 2 * hops[0].DP, main);
+    if (rc == QAGNN_OK) rc = launch_colreduce_final_layers(dws.db1_part, dws.db1_stride, k, db1, hops[0].N, hops[0].DP, main);
   }
   // join even after an error: whatever was forked must not outlive the call (a capture would be left with an unjoined branch)
   if (ss.side) {
@@ -499,4 +541,14 @@ extern "C" int qagnn_stack_infer_f32(const qagnn_hop_args* hops, int32_t k, qagn
 extern "C" int qagnn_stack_bwd_f32(const qagnn_hop_args* hops, int32_t k, qagnn_stream_t stream) {
   QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_bwd: no hops");
   return stack_bwd_impl(hops, k, (hipStream_t)stream);
+}
+
+// ---- include/qagnn_hip_defer.h ------------------------------------------------------------------------------------------------------
+extern "C" int qagnn_defer_version(void) { return 1; }
+extern "C" int64_t qagnn_stack_bwd_defer_elems(int32_t N, int32_t DP, int32_t cls_part_rows, int32_t k) {
+  return N > 0 && DP > 0 && cls_part_rows >= 0 && k > 0 ? StackDeferWs::layout(N, DP, cls_part_rows, k, nullptr).total : 0;
+}
+extern "C" int qagnn_stack_bwd_deferred_f32(const qagnn_hop_args* hops, int32_t k, float* defer_ws, int64_t defer_elems, qagnn_stream_t stream) {
+  QAGNN_REQUIRE(hops && k > 0, QAGNN_EINVAL, "stack_bwd: no hops");
+  return stack_bwd_impl(hops, k, (hipStream_t)stream, defer_ws, defer_elems);
 }
