@@ -38,6 +38,11 @@ EXPORTS_LOSS = ['qagnn_loss_version', 'qagnn_choice_loss_f32', 'qagnn_choice_los
 EXPORTS_EXPLAIN = ['qagnn_explain_version', 'qagnn_attn_export_f32', 'qagnn_attn_trace_f32']
 # include/qagnn_hip_defer.h, the extension header of the stack backward that finishes dEkEm and db1 of all layers after its last hop (likewise)
 EXPORTS_DEFER = ['qagnn_defer_version', 'qagnn_stack_bwd_defer_elems', 'qagnn_stack_bwd_deferred_f32']
+# include/qagnn_hip_rows.h, the extension header of the trainable entity table's gradient: row grouping, segment sums, row scatter (likewise)
+EXPORTS_ROWS = ['qagnn_rows_version', 'qagnn_row_groups_workspace_elems', 'qagnn_row_groups', 'qagnn_row_segment_sum_workspace_elems',
+                'qagnn_row_segment_sum_f32', 'qagnn_rows_scatter_f32']
+ROWS_CHUNK = 64  # QAGNN_ROWS_CHUNK
+ROWS_MAX_N, ROWS_MAX_TABLE = 1 << 20, 1 << 26  # QAGNN_ROWS_MAX_N, QAGNN_ROWS_MAX_TABLE
 DEFER_MAX_HOPS = 16  # QAGNN_DEFER_MAX_HOPS
 TRACE_MAX_N = 1024  # QAGNN_TRACE_MAX_N
 LOSS_KINDS = {'cross_entropy': 0, 'margin_rank': 1}  # QAGNN_LOSS_CROSS_ENTROPY, QAGNN_LOSS_MARGIN_RANK
@@ -205,7 +210,15 @@ def load_library(path=LIB_PATH):
     lib.qagnn_stack_bwd_defer_elems.restype = _i64
     lib.qagnn_stack_bwd_defer_elems.argtypes = [_i32, _i32, _i32, _i32]
     lib.qagnn_stack_bwd_deferred_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp, _i64, _vp]
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER:
+    lib.qagnn_rows_version.argtypes = []
+    lib.qagnn_row_groups_workspace_elems.restype = _i64
+    lib.qagnn_row_groups_workspace_elems.argtypes = [_i32]
+    lib.qagnn_row_groups.argtypes = [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    lib.qagnn_row_segment_sum_workspace_elems.restype = _i64
+    lib.qagnn_row_segment_sum_workspace_elems.argtypes = [_i32, _i32]
+    lib.qagnn_row_segment_sum_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _vp]
+    lib.qagnn_rows_scatter_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp]
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER + EXPORTS_ROWS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -1399,6 +1412,48 @@ class HipKernels(metaclass=_GuardedMeta):
         assert out.dtype == torch.float32 and out.shape == (Q, nc) and out.device == g.device and (out.stride(1) == 1 or nc == 1)
         self._check(self.lib.qagnn_choice_loss_bwd_f32(g.data_ptr(), _ld(g), grad_out.data_ptr(), out.data_ptr(), _ld(out), Q, nc, self._stream()),
                     'qagnn_choice_loss_bwd_f32')
+        return out
+
+    # -- the trainable entity table's gradient (include/qagnn_hip_rows.h).  The caller owns every output and workspace: nothing is allocated here
+    def row_groups_workspace_elems(self, N):
+        """int32 words of workspace row_groups() needs for N positions"""
+        return int(self.lib.qagnn_row_groups_workspace_elems(int(N)))
+
+    def row_groups(self, ridx, table_rows, order, seg, uniq, count, workspace):
+        """ridx int64 [N] -> order int32 [N], seg int32 [N + 1], uniq int64 [N], count int32 [1]: the positions with 0 <= ridx < table_rows
+        grouped by row id (qagnn_row_groups).  workspace: int32, at least row_groups_workspace_elems(N) words.  No synchronisation."""
+        N = ridx.numel()
+        dev = ridx.device
+        assert ridx.is_cuda and ridx.dtype == torch.long and ridx.is_contiguous()
+        for t, dt, ne in ((order, torch.int32, N), (seg, torch.int32, N + 1), (uniq, torch.long, N), (count, torch.int32, 1), (workspace, torch.int32, 0)):
+            assert t.device == dev and t.dtype == dt and t.is_contiguous() and t.numel() >= ne
+        self._check(self.lib.qagnn_row_groups(ridx.data_ptr(), N, int(table_rows), order.data_ptr(), seg.data_ptr(), uniq.data_ptr(), count.data_ptr(),
+                                              workspace.data_ptr(), workspace.numel(), self._stream()), 'qagnn_row_groups')
+        return order, seg, uniq, count
+
+    def row_segment_sum_workspace_elems(self, N, cols):
+        """floats of workspace row_segment_sum() needs for N positions of `cols` floats"""
+        return int(self.lib.qagnn_row_segment_sum_workspace_elems(int(N), int(cols)))
+
+    def row_segment_sum(self, X, order, seg, count, G, workspace):
+        """G[u] = the sum of X[order[j]] over group u in the fixed order of include/qagnn_hip_rows.h, zeros from row *count on
+        (qagnn_row_segment_sum_f32).  X [N, cols], G [g_rows <= N, cols]: fp32, rows may be pitched; workspace: fp32."""
+        _chkp(X, 'X'), _chkp(G, 'G')
+        N, cols = X.shape
+        assert G.size(1) == cols and order.dtype == torch.int32 and seg.dtype == torch.int32 and count.dtype == torch.int32
+        assert order.numel() >= N and seg.numel() >= N + 1 and order.is_contiguous() and seg.is_contiguous() and workspace.dtype == torch.float32
+        self._check(self.lib.qagnn_row_segment_sum_f32(X.data_ptr(), _ld(X), cols, order.data_ptr(), seg.data_ptr(), count.data_ptr(), N, G.data_ptr(),
+                                                       _ld(G), G.size(0), workspace.data_ptr(), workspace.numel(), self._stream()),
+                    'qagnn_row_segment_sum_f32')
+        return G
+
+    def rows_scatter(self, R, uniq, count, out, accumulate=False):
+        """out[uniq[u]] = R[u] (or +=) for u < min(*count, rows of R); no other word of `out` is touched (qagnn_rows_scatter_f32).
+        R [n_rows, cols], out [table_rows, cols]: fp32, rows may be pitched; uniq int64 [>= n_rows], ids distinct."""
+        _chkp(R, 'R'), _chkp(out, 'out')
+        assert R.size(1) == out.size(1) and uniq.dtype == torch.long and uniq.is_contiguous() and uniq.numel() >= R.size(0) and count.dtype == torch.int32
+        self._check(self.lib.qagnn_rows_scatter_f32(R.data_ptr(), _ld(R), R.size(1), uniq.data_ptr(), count.data_ptr(), R.size(0), out.data_ptr(), _ld(out),
+                                                    out.size(0), 1 if accumulate else 0, self._stream()), 'qagnn_rows_scatter_f32')
         return out
 
     def stack_infer(self, graph, HP, qscale, X, S, ntype, prms, eps, cols=-1, x_amax=None, s_amax=None, keep=False, attn=False):

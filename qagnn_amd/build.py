@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libqagnn_hip.so')
 STAMP = LIB + '.srchash'
-SOURCES = ['graph_prep.hip', 'gemm.hip', 'elementwise.hip', 'edge_attn.hip', 'pool.hip', 'hop.hip', 'optim.hip', 'gemm_split.hip', 'gemm_nn2.hip', 'gemm_dispatch.hip', 'timing.hip', 'infer.hip', 'loss.hip', 'explain.hip']
+SOURCES = ['graph_prep.hip', 'gemm.hip', 'elementwise.hip', 'edge_attn.hip', 'pool.hip', 'hop.hip', 'optim.hip', 'gemm_split.hip', 'gemm_nn2.hip', 'gemm_dispatch.hip', 'timing.hip', 'infer.hip', 'loss.hip', 'explain.hip', 'rows.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 
 
@@ -24,7 +24,8 @@ def hashed_files():
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_infer.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_loss.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_explain.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_defer.h')]
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_defer.h'),
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_rows.h')]
 
 
 def source_hash():

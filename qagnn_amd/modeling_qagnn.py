@@ -579,8 +579,10 @@ class QAGNN(nn.Module):
         dev = node_type_ids.device
         n = node_type_ids.size(1)
         ce = self.concept_emb
+        # (a trainable table: its gradient is the row-grouped one of ops.ConceptInputFn, where the provider has it and the switch is on)
         fused_input = (emb_data is None and not ce.use_contextualized and hasattr(ce, 'cpt_transform') and ce.scale == 1.0
-                       and not ce.emb.weight.requires_grad and ce.emb.weight.size(1) % 16 == 0)
+                       and ce.emb.weight.size(1) % 16 == 0
+                       and (not ce.emb.weight.requires_grad or (ops.TRAINABLE_TABLE_FUSED and ops.table_rows_supported())))
         graph, join_graph = None, None
         node_type_ids = node_type_ids.contiguous()
         if fused_input and self.gnn.k > 0:

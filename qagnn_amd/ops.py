@@ -1187,6 +1187,9 @@ def table_amax(K, table):
     bumps the version and costs a new pass; an edit through `.data` bumps nothing and cannot be seen.  None where the form does not
     apply (table not 16-byte / 4-element aligned, provider without the form).
 
+    A TRAINABLE table (requires_grad) gets None too, on purpose: its maximum moves with every optimiser step, and a word reduced per step
+    would cost a pass over the whole table.  The gathered forward product of a trainable table therefore runs in the exact form.
+
     A live table object keeps ONE word for its whole life: a new version is reduced into the word it already has.  A captured graph has
     that word's address baked in; `table_words` hands a capture the (table, word) pairs it read, and refresh_table_words() brings them
     up to date in front of a replay (a load_state_dict between two replays runs no eager forward that would)."""
@@ -1243,8 +1246,12 @@ class ConceptInputFn(torch.autograd.Function):
 
     The frozen entity-table gather is folded into the GEMM's operand load (`a_rowidx`), so the [N, concept_in_dim]
     gathered matrix (260 MB at the CSQA batch) is never materialised; `rowidx` is -1 on the context-node rows, whose
-    pre-activation `ctx_pre` = svec2nvec(sent_vecs) is written in instead.  The table receives no gradient (frozen,
-    freeze_ent_emb=True is the only mode this path takes)."""
+    pre-activation `ctx_pre` = svec2nvec(sent_vecs) is written in instead.
+
+    A frozen table (freeze_ent_emb=True) receives no gradient.  A TRAINABLE one (freeze_ent_emb=False, or requires_grad_(True) later)
+    receives the dense [table_rows, in] gradient nn.Embedding hands the optimiser in the reference: zeroed by the library's own kernel,
+    then the rows of table_row_gradient() scattered in -- reduced per row id first, projected second, so the [N, in] per-node gradient
+    is not formed and no atomic is used (include/qagnn_hip_rows.h).  Its forward product runs in the exact form (table_amax)."""
 
     @staticmethod
     @_fwd
@@ -1252,11 +1259,14 @@ class ConceptInputFn(torch.autograd.Function):
         K = kernels()
         # (the frozen table's maximum: the gathered product then runs in the three-MFMA form like the stack's -- csrc/gemm_nn2.hip)
         tam = table_amax(K, emb_w) if rowidx.numel() >= pack_min_rows(K) else None
-        pre = K.gemm_nn(emb_w, Wc_t, bias=bc, a_rowidx=rowidx, B1n=Wc if Wc is not None else Wc_t.t().contiguous(),
-                        **(dict(a_amax1=tam) if tam is not None else {}))
+        Wcn = Wc if Wc is not None else Wc_t.t().contiguous()
+        pre = K.gemm_nn(emb_w, Wc_t, bias=bc, a_rowidx=rowidx, B1n=Wcn, **(dict(a_amax1=tam) if tam is not None else {}))
         B = ctx_pre.size(0)
         pre.view(B, n, -1)[:, 0] = ctx_pre
-        ctx.save_for_backward(emb_w, rowidx, pre)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(emb_w, rowidx, pre, Wc_t, Wcn)
+        else:
+            ctx.save_for_backward(emb_w, rowidx, pre)
         ctx.cfg = (n, p, seed)
         if _wants_amax(K, pre):
             Hp, word = K.gelu_dropout_fwd(pre, p, seed, amax=True)
@@ -1267,13 +1277,59 @@ class ConceptInputFn(torch.autograd.Function):
     @_bwd
     def backward(ctx, dHp):
         K = kernels()
-        emb_w, rowidx, pre = ctx.saved_tensors
+        emb_w, rowidx, pre = ctx.saved_tensors[:3]
         n, p, seed = ctx.cfg
         dpre = K.gelu_dropout_bwd(pre, dHp.contiguous(), p, seed)
         dctx = dpre.view(-1, n, dpre.size(1))[:, 0].contiguous()
         dWc_t, cs = K.gemm_tn(emb_w, dpre, a_rowidx=rowidx), K.colsum(dpre)
         dbc = cs[0] - dctx.sum(0)  # the bias only acts on the entity rows (context-node rows were overwritten)
-        return None, None, dWc_t, dbc, dctx, None, None, None, None
+        demb = None
+        if ctx.needs_input_grad[0]:
+            Wc_t, Wcn = ctx.saved_tensors[3:]
+            uniq, count, rows = table_row_gradient(rowidx, dpre, Wcn, emb_w.size(0), Wc_t=Wc_t)
+            # (zeroed by qagnn_zero_words, not by a memset node: a replayed hipMemsetAsync node is the README's round-5 fault)
+            demb = K.zero_words(torch.empty(emb_w.shape, dtype=emb_w.dtype, device=emb_w.device))
+            K.rows_scatter(rows, uniq, count, demb)
+        return demb, None, dWc_t, dbc, dctx, None, None, None, None
+
+
+# A trainable entity table takes the fused input stage (modeling_qagnn.QAGNN.forward) when this is on and the provider has the three row
+# methods; off: the stock path (nn.Embedding, the materialised [B, n - 1, in] matrix, rocBLAS) as before -- the A/B switch and the way back
+TRAINABLE_TABLE_FUSED = True
+_ROW_METHODS = ('row_groups', 'row_segment_sum', 'rows_scatter')
+
+
+def table_rows_supported(K=None):
+    """whether the provider computes the row-grouped table gradient (include/qagnn_hip_rows.h); probed like HEAD_LIMITS"""
+    K = kernels() if K is None else K
+    return all(hasattr(K, m) for m in _ROW_METHODS)
+
+
+def table_row_gradient(ridx, dpre, Wc, table_rows, Wc_t=None):
+    """The row-sparse gradient of an entity table gathered by ridx int64 [N] (-1: no row) and projected by Wc [DP, in] (cpt_transform in
+    the kernels' layout), from dpre fp32 [N, DP], the gradient of the projected rows:
+
+        -> (uniq int64 [cap], count int32 [1], rows fp32 [cap, in]),  cap = min(N, table_rows)
+        rows[u] = (sum of dpre[i] over ridx[i] == uniq[u]) @ Wc  for u < U = count[0]: the distinct row ids ascending; uniq is -1 and
+        rows are zero behind U.
+
+    U stays on the device (no synchronisation: safe inside a stream capture), so the product runs over the capacity.  The sum's order is
+    fixed (include/qagnn_hip_rows.h): the same bits on every run.  Wc_t [in, DP]: the same weight the other way round (optional: the
+    product then runs on the matrix cores by exact operand splitting, as K.gemm_nn says)."""
+    K = kernels()
+    N, DP = dpre.shape
+    assert ridx.dtype == torch.long and ridx.numel() == N and Wc.size(0) == DP
+    dev = dpre.device
+    cap = min(N, int(table_rows))
+    order = torch.empty(N, dtype=torch.int32, device=dev)
+    seg = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    uniq = torch.empty(N, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    K.row_groups(ridx.contiguous(), table_rows, order, seg, uniq, count, torch.empty(K.row_groups_workspace_elems(N), dtype=torch.int32, device=dev))
+    G = torch.empty((cap, DP), dtype=dpre.dtype, device=dev)
+    K.row_segment_sum(dpre, order, seg, count, G, torch.empty(K.row_segment_sum_workspace_elems(N, DP), dtype=dpre.dtype, device=dev))
+    rows = K.gemm_nn(G, Wc, **(dict(B1n=Wc_t) if Wc_t is not None else {}))
+    return uniq[:cap], count, rows
 
 
 def concept_input(emb_w, rowidx, Wc_t, bc, ctx_pre, n, p, training, Wc=None):
