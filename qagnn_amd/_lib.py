@@ -41,6 +41,9 @@ EXPORTS_DEFER = ['qagnn_defer_version', 'qagnn_stack_bwd_defer_elems', 'qagnn_st
 # include/qagnn_hip_rows.h, the extension header of the trainable entity table's gradient: row grouping, segment sums, row scatter (likewise)
 EXPORTS_ROWS = ['qagnn_rows_version', 'qagnn_row_groups_workspace_elems', 'qagnn_row_groups', 'qagnn_row_segment_sum_workspace_elems',
                 'qagnn_row_segment_sum_f32', 'qagnn_rows_scatter_f32']
+# include/qagnn_hip_dual.h, the extension header of the two-output NN product: a hop's dX and dS from one pass over dK|dM|dQ (likewise)
+EXPORTS_DUAL = ['qagnn_dual_version', 'qagnn_gemm_nn_dual_f32', 'qagnn_gemm_nn_dual_query', 'qagnn_dual_launches', 'qagnn_dual_blocks_per_cu',
+                'qagnn_nn_dual_enable']
 ROWS_CHUNK = 64  # QAGNN_ROWS_CHUNK
 ROWS_MAX_N, ROWS_MAX_TABLE = 1 << 20, 1 << 26  # QAGNN_ROWS_MAX_N, QAGNN_ROWS_MAX_TABLE
 DEFER_MAX_HOPS = 16  # QAGNN_DEFER_MAX_HOPS
@@ -218,7 +221,14 @@ def load_library(path=LIB_PATH):
     lib.qagnn_row_segment_sum_workspace_elems.argtypes = [_i32, _i32]
     lib.qagnn_row_segment_sum_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _vp]
     lib.qagnn_rows_scatter_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp]
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER + EXPORTS_ROWS:
+    lib.qagnn_dual_version.argtypes = []
+    lib.qagnn_gemm_nn_dual_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i64, _vp]
+    lib.qagnn_gemm_nn_dual_query.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i64]
+    lib.qagnn_dual_launches.restype = _i64
+    lib.qagnn_dual_launches.argtypes = []
+    lib.qagnn_nn_dual_enable.argtypes = [_i32]
+    lib.qagnn_dual_blocks_per_cu.argtypes = []
+    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER + EXPORTS_ROWS + EXPORTS_DUAL:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
             fn.restype = _i32
@@ -227,6 +237,16 @@ def load_library(path=LIB_PATH):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def dual_args(A, lda, M, K, a_amax, C1, ldc1, No1, C2, ldc2, No2, accumulate1=False, accumulate2=False):
+    """the two argument blocks of qagnn_gemm_nn_dual_f32 / qagnn_gemm_nn_dual_query from raw addresses (the query needs no device)"""
+    out = []
+    for Cp, ldc, No, acc in ((C1, ldc1, No1, accumulate1), (C2, ldc2, No2, accumulate2)):
+        a = qagnn_gemm_nn_args()
+        a.A1, a.lda1, a.K1, a.C, a.ldc, a.M, a.No, a.accumulate, a.a_amax1 = A, lda, K, Cp, ldc, M, No, 1 if acc else 0, a_amax
+        out.append(a)
+    return out
 
 
 def choice_loss_bound(kind, nc, Q, max_abs=1.0, margin=0.0, weight=1.0, threads=LOSS_THREADS):
@@ -861,6 +881,31 @@ class HipKernels(metaclass=_GuardedMeta):
                                               self._stream())
         self._check(rc, 'qagnn_gemm_tn_graph_f32')
         return out
+
+    def gemm_nn_dual(self, A, B1n, B2n, a_amax, out1, out2, accumulate1=False, accumulate2=False, ws=None):
+        """out1 (+)= A B1n^T and out2 (+)= A B2n^T in ONE launch (qagnn_gemm_nn_dual_f32: bit-identical to the two gemm_nn calls).  B1n / B2n:
+        the weights as [No, K]; a_amax: the absmax() word of A.  ws: the caller's uint8 scratch for the images that are not registered
+        (qagnn_gemm_nn_pack_bytes(624, 208, 208) holds both), or None.  Returns the status (0, or QAGNN_EUNSUPPORTED = 2 when the pair is
+        not one the launch takes: nothing was enqueued); other errors raise."""
+        for t, n in ((A, 'A'), (B1n, 'B1n'), (B2n, 'B2n'), (out1, 'out1'), (out2, 'out2')):
+            _chkp(t, n)
+        assert ws is None or (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous())
+        a1, a2 = dual_args(A.data_ptr(), _ld(A), A.size(0), A.size(1), _ptr(a_amax), out1.data_ptr(), _ld(out1), B1n.size(0),
+                           out2.data_ptr(), _ld(out2), B2n.size(0), accumulate1, accumulate2)
+        rc = self.lib.qagnn_gemm_nn_dual_f32(C.byref(a1), B1n.data_ptr(), _ld(B1n), C.byref(a2), B2n.data_ptr(), _ld(B2n),
+                                             _ptr(ws), ws.numel() if ws is not None else 0, self._stream())
+        if rc != 2:
+            self._check(rc, 'qagnn_gemm_nn_dual_f32')
+        return rc
+
+    def nn_dual_enable(self, on):
+        """TESTS AND A/B RUNS ONLY: the process-wide mode of the two-output dX / dS launch (qagnn_nn_dual_enable): 0 off, 1 where the separate
+        launches would keep their full column tiles, 2 at every row count of the packed forms; -1 reads.  Returns the previous value."""
+        return int(self.lib.qagnn_nn_dual_enable(int(on)))
+
+    def dual_launches(self):
+        """launches of the two-output kernel since the library was loaded (qagnn_dual_launches)"""
+        return int(self.lib.qagnn_dual_launches())
 
     def tn_route_query(self, R, Ka1, Ka2, No):
         """host-only: (family, chunk_rows, nchunks, live) of the weight gradient [A1 | A2]^T B (qagnn_gemm_tn_route_query); family 3 = k_gemm_tn_ws"""

@@ -25,7 +25,8 @@ def hashed_files():
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_loss.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_explain.h'),
                                                                  os.path.join(HERE, '..', 'include', 'qagnn_hip_defer.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_rows.h')]
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_rows.h'),
+                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_dual.h')]
 
 
 def source_hash():

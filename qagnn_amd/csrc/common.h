@@ -52,12 +52,28 @@ inline void nn_grid(NnRoute& r, int M, int No, int rows_per_tile, int per_cu) {
 }
 NnRoute nn_route(const NnProduct& p);
 bool nn_rows_packed(int64_t M);  // rows from which products take packed B images and the scaled forms (qagnn_packed_min_rows)
+int nn_validate(const NnProduct& p);  // the argument checks of every NN entry point (gemm_nn runs them itself)
 int gemm_nn(const NnProduct& p, hipStream_t stream);
 int launch_nn(const NnRoute& r, const qagnn_gemm_nn_args& a, hipStream_t stream);
 int launch_nn_split(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
 // (b != IN_KERNEL: B1n = the image, ldn1 = its column tiles per k-tile)
 int launch_nn2(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream);
 int launch_pack_b(int np, const qagnn_gemm_nn_args& a, const float* B1n, int ldn1, const float* B2n, int ldn2, void* ws, hipStream_t stream);
+// Two NN products over ONE A operand as one launch (include/qagnn_hip_dual.h; k_gemm_nn2_dual in gemm_nn2.hip): C[0] = A B[0] over 13 column
+// tiles, C[1] = A B[1] over 7, both B as two-piece images.  Filled by nn_dual_route (gemm_dispatch.hip), which is where the shapes are checked.
+struct NnDual {
+  const float* A; int lda, K, M;
+  const uint32_t* a_amax;
+  const void* image[2];
+  float* C[2]; int ldc[2], No[2], accumulate[2];
+};
+int launch_nn2_dual(const NnDual& d, hipStream_t stream);
+int nn2_dual_blocks_per_cu();  // what the runtime reports for k_gemm_nn2_dual (80 KB of LDS per block: two fill a CU)
+// the route of such a pair: ok = the one launch takes it; pack[i]: image i is packed into the scratch at ws_off[i] first (else it is registered)
+struct NnDualRoute { bool ok; NnDual d; bool pack[2]; int64_t ws_off[2]; };
+NnDualRoute nn_dual_route(const NnProduct& p1, const NnProduct& p2);  // (both validated; the scratch: p1.ws / p1.ws_bytes)
+int gemm_nn_dual(const NnProduct& p1, const NnProduct& p2, const NnDualRoute& r, hipStream_t stream);
+bool nn_dual_enabled();  // QAGNN_NN_DUAL / qagnn_nn_dual_enable: hop.hip sends a hop's dX and dS through the one launch
 namespace nn2 { int walk_tiles(int K1, int K2); }  // k-tiles of 32 that k_gemm_nn2 walks over the two segments
 int64_t nn2_pack_bytes(int No, int K1, int K2, int np);
 const void* nn2_prepack_lookup(const float* B1n, int ldn1, int K1, const float* B2n, int ldn2, int K2, int No, int np);

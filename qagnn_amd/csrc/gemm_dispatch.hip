@@ -12,6 +12,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "../../include/qagnn_hip_dual.h"
 
 namespace qagnn {
 
@@ -55,6 +56,9 @@ static bool nn2_staggered(int nt, const qagnn_gemm_nn_args& a) {
   return nt >= 8 && nn2::walk_tiles(a.K1, a.K2) >= 10 && (int64_t)cdiv(a.No, nt * 16) * cdiv(a.M, 256) * 10 >= num_cus() * 9;
 }
 
+// fewer than about 1.5 blocks per CU at `nt` column tiles per block: nn_route narrows the column tile then (its comment, below)
+static bool nn_few_blocks(int M, int No, int nt) { return cdiv(M, 128) * cdiv(No, nt * 16) < num_cus() * 3 / 2; }
+
 NnRoute nn_route(const NnProduct& p) {
   const qagnn_gemm_nn_args& a = *p.a;
   NnRoute r = {};
@@ -76,7 +80,7 @@ NnRoute nn_route(const NnProduct& p) {
   // (18.6 at 32); 624 -> 208 at 12 800 rows 63 -> 37 us.  The arithmetic per output element does not depend on the tile shape:
   // results are bit-identical.
   for (int c : {7, 4, 2})
-    if (cdiv(a.M, 128) * cdiv(a.No, r.nt * 16) < num_cus() * 3 / 2 && c < r.nt) r.nt = c;
+    if (nn_few_blocks(a.M, a.No, r.nt) && c < r.nt) r.nt = c;
   r.wv = 4;
   r.stats = a.colstat_part != nullptr;
   if (!nn2_ok(a, p.ldn1, p.ldn2)) {  // first generation: 4-wave blocks on 128-row tiles, two per CU
@@ -107,7 +111,7 @@ NnRoute nn_route(const NnProduct& p) {
   return r;
 }
 
-static int nn_validate(const NnProduct& p) {
+int nn_validate(const NnProduct& p) {
   QAGNN_REQUIRE(p.a, QAGNN_EINVAL, "gemm_nn: null pointer");
   const qagnn_gemm_nn_args& a = *p.a;
   const float* B1 = p.split ? p.B1n : a.B1, *B2 = p.split ? p.B2n : a.B2;
@@ -153,6 +157,67 @@ int gemm_nn(const NnProduct& p, hipStream_t stream) {
     if (int rc = launch_pack_b(r.np, a, p.B1n, p.ldn1, p.B2n, p.ldn2, p.ws, stream)) return rc;
   }
   return launch_nn2(r, a, static_cast<const float*>(r.b == NnB::PACK ? p.ws : r.image), cdiv(a.No, 16), nullptr, 0, stream);
+}
+
+// ---- two NN products over one A operand as one launch (include/qagnn_hip_dual.h) ---------------------------------------------------
+// The switch hop.hip asks (QAGNN_NN_DUAL starts it; qagnn_nn_dual_enable moves it) and the count of launches tests read.  0: off; 1: on
+// where the separate launches would keep their full 13 / 7 column tiles; 2: on at every row count the packed forms take (tests)
+static std::atomic<int> g_nn_dual{-1};  // -1: not set by a call -- the environment decides
+static std::atomic<int64_t> g_nn_dual_launches{0};
+static int nn_dual_mode() {
+  static const int env = [] { const char* e = getenv("QAGNN_NN_DUAL"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
+  const int v = g_nn_dual.load(std::memory_order_relaxed);
+  return v < 0 ? env : v;
+}
+bool nn_dual_enabled() { return nn_dual_mode() != 0; }
+
+// Which pairs take k_gemm_nn2_dual: the conditions of the header, in its order; p1 and p2 have passed nn_validate.  The kernel's blocks
+// are 128 rows x (13 + 7) column tiles at every M, so with few row tiles (10 subgraphs' worth up to about 49 000 rows on 256 CUs) the
+// launch would be a handful of long serial blocks where nn_route narrows the separate products' column tiles to fill the chip: there
+// the pair keeps its two launches.
+NnDualRoute nn_dual_route(const NnProduct& p1, const NnProduct& p2) {
+  NnDualRoute r = {};
+  if (!p1.split || !p2.split) return r;
+  const qagnn_gemm_nn_args& a = *p1.a, &b = *p2.a;
+  if (a.A1 != b.A1 || a.lda1 != b.lda1 || a.K1 != b.K1 || a.M != b.M || a.a_amax1 != b.a_amax1 || !a.a_amax1) return r;
+  if (a.pieces == 1 || b.pieces == 1) return r;  // (the one-MFMA form stays on its two launches)
+  for (const qagnn_gemm_nn_args* q : {&a, &b})
+    if (q->K2 != 0 || q->bias || q->rowtab || q->a_scale || q->a_shift || q->colstat_part || q->a_rowidx) return r;
+  if (cdiv(a.No, 16) != 13 || cdiv(b.No, 16) != 7) return r;
+  if (!nn2_ok(a, p1.ldn1, 0) || !nn2_ok(b, p2.ldn1, 0) || !nn_rows_packed(a.M)) return r;
+  if (nn_dual_mode() != 2 && (nn_few_blocks(a.M, a.No, 13) || nn_few_blocks(b.M, b.No, 7))) return r;  // (nn_route would narrow either)
+  // the two-piece images: registered, or packed into the scratch one behind the other
+  const NnProduct* ps[2] = {&p1, &p2};
+  int64_t used = 0;
+  for (int i = 0; i < 2; ++i) {
+    const qagnn_gemm_nn_args& q = *ps[i]->a;
+    r.d.image[i] = nn2_prepack_lookup(ps[i]->B1n, ps[i]->ldn1, q.K1, nullptr, 0, 0, q.No, 2);
+    if (!r.d.image[i]) {
+      const int64_t need = (nn2_pack_bytes(q.No, q.K1, 0, 2) + 15) & ~(int64_t)15;
+      if (!p1.ws || !aligned16(p1.ws) || used + need > p1.ws_bytes) return r;
+      r.pack[i] = true;
+      r.ws_off[i] = used;
+      r.d.image[i] = static_cast<const unsigned char*>(p1.ws) + used;
+      used += need;
+    }
+  }
+  r.d.A = a.A1; r.d.lda = a.lda1; r.d.K = a.K1; r.d.M = a.M; r.d.a_amax = a.a_amax1;
+  r.d.C[0] = a.C; r.d.ldc[0] = a.ldc; r.d.No[0] = a.No; r.d.accumulate[0] = a.accumulate;
+  r.d.C[1] = b.C; r.d.ldc[1] = b.ldc; r.d.No[1] = b.No; r.d.accumulate[1] = b.accumulate;
+  r.ok = true;
+  return r;
+}
+
+// the launch of an accepted pair (r.ok): the images the scratch has to hold, then the one kernel; one timing entry
+int gemm_nn_dual(const NnProduct& p1, const NnProduct& p2, const NnDualRoute& r, hipStream_t stream) {
+  TimedScope timed(0, stream);
+  const NnProduct* ps[2] = {&p1, &p2};
+  for (int i = 0; i < 2; ++i)
+    if (r.pack[i])
+      if (int rc = launch_pack_b(2, *ps[i]->a, ps[i]->B1n, ps[i]->ldn1, nullptr, 0, static_cast<unsigned char*>(p1.ws) + r.ws_off[i], stream)) return rc;
+  if (int rc = launch_nn2_dual(r.d, stream)) return rc;
+  g_nn_dual_launches.fetch_add(1, std::memory_order_relaxed);
+  return QAGNN_OK;
 }
 
 // ---- TN (weight gradients): split-K over row chunks, partials summed in order ------------------------------------------------------
@@ -325,6 +390,40 @@ extern "C" int qagnn_gemm_nn_split_f32(const qagnn_gemm_nn_args* a, const float*
 extern "C" int qagnn_gemm_nn_split_ws_f32(const qagnn_gemm_nn_args* a, const float* B1n, int32_t ldn1, const float* B2n, int32_t ldn2,
                                           void* ws, int64_t ws_bytes, qagnn_stream_t stream) {
   return gemm_nn(NnProduct{a, true, B1n, ldn1, B2n, ldn2, ws, ws_bytes}, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_dual_version(void) { return 1; }
+
+extern "C" int qagnn_gemm_nn_dual_f32(const qagnn_gemm_nn_args* p1, const float* B1n, int32_t ldn1, const qagnn_gemm_nn_args* p2, const float* B2n,
+                                      int32_t ldn2, void* pack_ws, int64_t pack_bytes, qagnn_stream_t stream) {
+  const NnProduct q1{p1, true, B1n, ldn1, nullptr, 0, pack_ws, pack_bytes}, q2{p2, true, B2n, ldn2, nullptr, 0, nullptr, 0};
+  QAGNN_REQUIRE(p1 && p2, QAGNN_EINVAL, "gemm_nn_dual: null pointer");
+  QAGNN_REQUIRE(p1->K2 == 0 && p2->K2 == 0, QAGNN_EUNSUPPORTED, "gemm_nn_dual: one K segment per product (K2 = %d / %d)", p1->K2, p2->K2);
+  if (int rc = nn_validate(q1)) return rc;
+  if (int rc = nn_validate(q2)) return rc;
+  const NnDualRoute r = nn_dual_route(q1, q2);
+  QAGNN_REQUIRE(r.ok, QAGNN_EUNSUPPORTED, "gemm_nn_dual: not a pair the two-output launch takes (include/qagnn_hip_dual.h)");
+  return gemm_nn_dual(q1, q2, r, (hipStream_t)stream);
+}
+
+extern "C" int qagnn_gemm_nn_dual_query(const qagnn_gemm_nn_args* p1, const float* B1n, int32_t ldn1, const qagnn_gemm_nn_args* p2, const float* B2n,
+                                        int32_t ldn2, const void* pack_ws, int64_t pack_bytes) {
+  alignas(16) static char any_ws;  // (pack_ws == NULL, pack_bytes < 0: as if both images were registered -- any scratch, of any size)
+  const bool assume = !pack_ws && pack_bytes < 0;
+  const NnProduct q1{p1, true, B1n, ldn1, nullptr, 0, assume ? &any_ws : const_cast<void*>(pack_ws), assume ? INT64_MAX : pack_bytes};
+  const NnProduct q2{p2, true, B2n, ldn2, nullptr, 0, nullptr, 0};
+  if (nn_validate(q1) != QAGNN_OK || nn_validate(q2) != QAGNN_OK) return 0;
+  return nn_dual_route(q1, q2).ok ? 1 : 0;
+}
+
+extern "C" int64_t qagnn_dual_launches(void) { return g_nn_dual_launches.load(); }
+
+extern "C" int qagnn_dual_blocks_per_cu(void) { return nn2_dual_blocks_per_cu(); }
+
+extern "C" int qagnn_nn_dual_enable(int32_t on) {
+  const int was = nn_dual_mode();
+  if (on >= 0) g_nn_dual.store(on > 2 ? 2 : on);
+  return was;
 }
 
 extern "C" int64_t qagnn_gemm_tn_workspace_elems(int32_t R, int32_t Ka, int32_t No) { return tn_ws_bound(R, Ka, No); }

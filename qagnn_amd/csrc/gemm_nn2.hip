@@ -608,6 +608,195 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #undef QAGNN_NN2_SIX
 #undef QAGNN_NN2_SIX_T
 
+// ---- two outputs from one pass over A (include/qagnn_hip_dual.h) --------------------------------------------------------------------
+// dX = dK|dM|dQ Wx and dS = dK|dM|dQ Ws of a hop's backward read the same [N, 624] operand; as two launches of the packed 4-wave kernel
+// above each of them loads it and splits it into fp16 pieces, and that A-side work -- not the MFMAs -- is most of either launch
+// (profiles/r6_run19_nn2_narrow_blocks_three_waves.txt: with two thirds of the MFMAs gone the 7-tile product still costs what the
+// 13-tile one does).  Here a block carries NT1 + NT2 column tiles: tiles j < NT1 take their B fragments from image 0 and belong to
+// C[0], the others from image 1 and belong to C[1]; the two images are what the packer makes for the separate products, a k-tile of B
+// is two DMA ranges.  Per output tile nothing changes -- k-tiles in order, the three MFMAs in mfma_pieces' order, A's one scale and the
+// column tile's own B scale, product + old value -- so the results are bit-identical to the two launches.  One segment (K2 = 0), no
+// affine / bias / table / statistics, the DIRECT epilogue of the packed 4-wave blocks; one k-tile of raw A in flight, as there.
+// Registers: 2 x 20 x 4 = 160 accumulators per lane of the 256 a wave has at two waves per SIMD; LDS: 2 images x 20 x NP KB.
+// The epilogue of one output: cv[i] = byte offset of (row i, column 4 c) of C, cl[i] = the same where the LAST column tile's four columns lie
+// below No, else OOB (ceil(No / 16) == NTH: every other tile is inside) -- the column tile's 64 bytes travel as the instruction's offset
+template <int J0, int NTH, int NT>
+__device__ __forceinline__ void dual_add_old(f32x4s (&acc)[2][NT], const __amdgpu_buffer_rsrc_t rC, const uint32_t (&cv)[2], const uint32_t (&cl)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    f32x4s t[NTH];
+#pragma unroll
+    for (int j = 0; j < NTH; ++j) t[j] = bload<f32x4s>(rC, j + 1 < NTH ? cv[i] : cl[i], (uint32_t)j * 64u);
+#pragma unroll
+    for (int j = 0; j < NTH; ++j) acc[i][J0 + j] += t[j];
+  }
+}
+template <int J0, int NTH, int NT>
+__device__ __forceinline__ void dual_store(const f32x4s (&acc)[2][NT], const __amdgpu_buffer_rsrc_t rC, const uint32_t (&cv)[2], const uint32_t (&cl)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < NTH; ++j)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, acc[i][J0 + j]), rC, (int)(j + 1 < NTH ? cv[i] : cl[i]), j * 64, 0);
+}
+
+template <int NT1, int NT2, int NP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm_nn2_dual(NnDual a, int ntiles) {
+  static_assert(NP == 2, "the three-MFMA form");
+  constexpr int NT = NT1 + NT2, BM = 128;
+  constexpr int IMG = NT * NP * 1024;  // one B image set: [column tile of either product][piece][64 slots x 16 B]
+  static_assert((NT * NP) % 4 == 0, "the DMA blocks of a k-tile are dealt out evenly over the four waves");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  // lane l of a wave: k chunk l >> 4 (8 k) of a tile on the A side, fragment slot ((l & 15) ^ 2 (l >> 4)) + 16 (l >> 4) on the B side
+  const int tid = threadIdx.x;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int M = a.M, K = a.K;
+  const int nkt = (K + 31) >> 5;
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A), 0, M * a.lda * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC1 = __builtin_amdgcn_make_buffer_rsrc(a.C[0], 0, M * a.ldc[0] * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC2 = __builtin_amdgcn_make_buffer_rsrc(a.C[1], 0, M * a.ldc[1] * 4, 0x00020000);
+  const unsigned char* const pk1 = static_cast<const unsigned char*>(a.image[0]);
+  const unsigned char* const pk2 = static_cast<const unsigned char*>(a.image[1]);
+  const uint32_t fa = __builtin_amdgcn_readfirstlane(h2_scale_field(a.a_amax[0]));
+  const float sa = h2_field_to_scale(fa);
+  // the B scales, one word per column tile behind each image's own k-tiles and slack: wave-uniform, read once into scalar registers
+  uint32_t fb[NT];
+  {
+    const uint32_t* const bf1 = reinterpret_cast<const uint32_t*>(pk1 + ((int64_t)nkt * NT1 + 13) * (NP * 1024));
+    const uint32_t* const bf2 = reinterpret_cast<const uint32_t*>(pk2 + ((int64_t)nkt * NT2 + 13) * (NP * 1024));
+#pragma unroll
+    for (int j = 0; j < NT; ++j) fb[j] = __builtin_amdgcn_readfirstlane(j < NT1 ? bf1[j] : bf2[j - NT1]);
+  }
+
+  u32x4s ra[2][2];
+  for (int vb = blockIdx.x; vb < ntiles; vb += gridDim.x) {
+    const int m0 = xcd_remap(vb, ntiles) * BM;
+    // (the tile's lane-derived offsets -- here and in the epilogue -- start from an opaque copy of the thread index: hoisted out of the
+    // tile loop they would live across the k-loop, where the accumulators leave no room for them)
+    uint32_t arow[2];
+    {
+      int t_ = tid;
+      asm volatile("" : "+v"(t_));
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = m0 + w * 32 + i * 16 + (t_ & 15);
+        arow[i] = row < M ? (uint32_t)row * (uint32_t)a.lda * 4u + (uint32_t)((t_ >> 4) & 3) * 32u : OOB;
+      }
+    }
+    f32x4s acc[2][NT];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4s){0.f, 0.f, 0.f, 0.f};
+    u32x4s af[2][NP];
+
+#define QAGNN_DUAL_GLOAD(IT)                                                     \
+    {                                                                            \
+      const int kb_ = (IT)*32;                                                   \
+      int tg_ = tid;                                                             \
+      asm volatile("" : "+v"(tg_));                                              \
+      const bool ain_ = kb_ + ((tg_ >> 4) & 3) * 8 < K;                          \
+      _Pragma("unroll") for (int i = 0; i < 2; ++i) {                            \
+        const uint32_t off_ = ain_ ? arow[i] : OOB;                              \
+        ra[i][0] = bload<u32x4s>(rA, off_, (uint32_t)kb_ * 4u);                  \
+        ra[i][1] = bload<u32x4s>(rA, off_, (uint32_t)kb_ * 4u + 16u);            \
+      }                                                                          \
+    }
+    // the NT1 * NP KB of image 0's k-tile IT and the NT2 * NP KB of image 1's -> the image set BUF by DMA, 1-KB blocks dealt out over the waves
+#define QAGNN_DUAL_GLDS(IT, BUF)                                                                                         \
+    {                                                                                                                    \
+      const unsigned char* const s1_ = pk1 + (int64_t)(IT) * (NT1 * NP * 1024);                                          \
+      const unsigned char* const s2_ = pk2 + (int64_t)(IT) * (NT2 * NP * 1024);                                          \
+      int td_ = tid;                                                                                                     \
+      asm volatile("" : "+v"(td_)); /* (opaque: ten per-lane 64-bit addresses hoisted out of the k-loop would not fit the registers) */ \
+      const uint32_t vo_ = (uint32_t)(td_ & 63) * 16u;                                                                   \
+      _Pragma("unroll") for (int b = 0; b < NT * NP / 4; ++b) {                                                          \
+        const int blk_ = w + b * 4;                                                                                      \
+        /* (wave-uniform: a scalar base, the lane's 16 bytes as the vector offset) */                                    \
+        const unsigned char* const src_ = blk_ < NT1 * NP ? s1_ + blk_ * 1024 : s2_ + (blk_ - NT1 * NP) * 1024;          \
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_ + vo_),                    \
+                                         (__attribute__((address_space(3))) void*)((BUF) + blk_ * 1024), 16, 0, 0);      \
+      }                                                                                                                  \
+    }
+#define QAGNN_DUAL_SPLIT_A                                                                                               \
+    {                                                                                                                    \
+      _Pragma("unroll") for (int i = 0; i < 2; ++i) split_frag2<false, NP>(ra[i], af[i], nullptr, nullptr, 0.f, sa);     \
+    }
+    // (as QAGNN_NN2_MFMA_TILE of the kernel above: fragments read one column tile ahead, operands swapped for the direct stores)
+#define QAGNN_DUAL_MFMA_TILE(CUR)                                                                                        \
+    {                                                                                                                    \
+      __builtin_amdgcn_s_setprio(1);                                                                                     \
+      int tm_ = tid;                                                                                                     \
+      asm volatile("" : "+v"(tm_));                                                                                      \
+      const int rd_ = (((tm_ & 15) ^ (2 * ((tm_ >> 4) & 3))) + 16 * ((tm_ >> 4) & 3)) * 16; /* this lane's fragment slot (the header) */ \
+      u32x4s bfa[NP], bfb[NP];                                                                                           \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p) bfa[p] = *reinterpret_cast<const u32x4s*>((CUR) + p * 1024 + rd_);  \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                                                   \
+        u32x4s(&bf)[NP] = (j & 1) ? bfb : bfa;                                                                           \
+        u32x4s(&bn)[NP] = (j & 1) ? bfa : bfb;                                                                           \
+        if (j + 1 < NT) {                                                                                                \
+          _Pragma("unroll") for (int p = 0; p < NP; ++p)                                                                 \
+              bn[p] = *reinterpret_cast<const u32x4s*>((CUR) + ((j + 1) * NP + p) * 1024 + rd_);                         \
+        }                                                                                                                \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = mfma_pieces<NP, true>(af[i], bf, acc[i][j]);           \
+        __builtin_amdgcn_sched_barrier(0);                                                                               \
+      }                                                                                                                  \
+      __builtin_amdgcn_s_setprio(0);                                                                                     \
+    }
+
+    __syncthreads();  // the previous tile's last-image reads are done
+    QAGNN_DUAL_GLOAD(0)
+    QAGNN_DUAL_GLDS(0, smem)
+    QAGNN_DUAL_SPLIT_A
+    __syncthreads();
+    // the loads of tile it + 1 are issued at the top of iteration it and consumed inside it: nothing in flight across the back edge
+    for (int it = 0; it + 1 < nkt; ++it) {
+      unsigned char* const cur = smem + (it & 1) * IMG;
+      unsigned char* const nxt = smem + ((it & 1) ^ 1) * IMG;
+      QAGNN_DUAL_GLDS(it + 1, nxt)
+      QAGNN_DUAL_GLOAD(it + 1)
+      QAGNN_DUAL_MFMA_TILE(cur)
+      QAGNN_DUAL_SPLIT_A
+      __syncthreads();  // nxt is complete; everybody is done reading cur
+    }
+    {
+      unsigned char* const cur = smem + ((nkt - 1) & 1) * IMG;
+      QAGNN_DUAL_MFMA_TILE(cur)
+    }
+#undef QAGNN_DUAL_GLOAD
+#undef QAGNN_DUAL_GLDS
+#undef QAGNN_DUAL_SPLIT_A
+#undef QAGNN_DUAL_MFMA_TILE
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {  // undo the operand scales: one exact power of two per column tile
+      uint32_t f = fb[j];
+      asm volatile("" : "+s"(f));  // (opaque: twenty splatted register pairs of inverse scales hoisted out of the tile loop would not fit)
+      const float inv = h2_inv_scale(fa, f);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) acc[i][j] *= inv;
+    }
+    int te = tid;
+    asm volatile("" : "+v"(te));
+    const int c4 = 4 * ((te >> 4) & 3), lrow = te & 15;
+    uint32_t cv1[2], cl1[2], cv2[2], cl2[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = m0 + w * 32 + i * 16 + lrow;
+      cv1[i] = row < M ? (uint32_t)row * (uint32_t)a.ldc[0] * 4u + (uint32_t)c4 * 4u : OOB;
+      cv2[i] = row < M ? (uint32_t)row * (uint32_t)a.ldc[1] * 4u + (uint32_t)c4 * 4u : OOB;
+      cl1[i] = (NT1 - 1) * 16 + c4 < a.No[0] ? cv1[i] : OOB;
+      cl2[i] = (NT2 - 1) * 16 + c4 < a.No[1] ? cv2[i] : OOB;
+    }
+    // product + old value; every addend of both outputs is in before the first store is issued (a load behind a store would wait for
+    // the store's acknowledgement too).  The stores of C[1] start a row of their own: tiles NT1, NT1 + 1 complete each other's lines
+    if (a.accumulate[0]) dual_add_old<0, NT1>(acc, rC1, cv1, cl1);
+    if (a.accumulate[1]) dual_add_old<NT1, NT2>(acc, rC2, cv2, cl2);
+    dual_store<0, NT1>(acc, rC1, cv1, cl1);
+    dual_store<NT1, NT2>(acc, rC2, cv2, cl2);
+  }
+}
+
 // PACKED: B1n = the packed buffer, ldn1 = its column tiles per k-tile.  WV = 8: the staggered 256-row block, one per CU.
 template <int NT, bool AFFINE, bool STATS, int NP, bool PACKED, int WV>
 static int launch_i(const NnRoute& r, const qagnn_gemm_nn_args& b, const float* B1n, int ldn1, const float* B2n, int ldn2, hipStream_t stream) {
@@ -738,6 +927,24 @@ int launch_nn2(const NnRoute& r, const qagnn_gemm_nn_args& a, const float* B1n, 
       }
     });
   });
+}
+
+// The two-output launch: one instantiation, (13, 7) column tiles in the three-MFMA form.  128-row tiles walked by at most two blocks per CU
+// like the 4-wave blocks of launch_nn2; 80 KB of LDS per block, so two blocks fill a CU's 160 KB exactly.
+constexpr int NN2_DUAL_LDS = 2 * (13 + 7) * 2 * 1024;
+int launch_nn2_dual(const NnDual& d, hipStream_t stream) {
+  if (int rc = raise_lds_limit<nn2::k_gemm_nn2_dual<13, 7, 2>>(NN2_DUAL_LDS, "k_gemm_nn2_dual")) return rc;
+  const int ntiles = cdiv(d.M, 128), cap = (num_cus() * 2) & ~7;
+  nn2::k_gemm_nn2_dual<13, 7, 2><<<ntiles < cap ? ntiles : cap, 256, NN2_DUAL_LDS, stream>>>(d, ntiles);
+  QAGNN_LAUNCH_CHECK("k_gemm_nn2_dual");
+  return QAGNN_OK;
+}
+// blocks of that kernel the runtime places on one CU (0: no device, or the query failed)
+int nn2_dual_blocks_per_cu() {
+  int n = 0;
+  if (raise_lds_limit<nn2::k_gemm_nn2_dual<13, 7, 2>>(NN2_DUAL_LDS, "k_gemm_nn2_dual") != QAGNN_OK) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, nn2::k_gemm_nn2_dual<13, 7, 2>, 256, NN2_DUAL_LDS) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return n;
 }
 
 // bytes of the packed image of B for one product (13 column tiles of slack: the last column block of a k-tile reads its full width);

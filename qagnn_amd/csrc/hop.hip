@@ -376,20 +376,28 @@ static int hop_bwd_one(const qagnn_hop_args* h, const HopAmax& am, SideSync* ss,
     hipError_t he = hipEventRecord(*done, ss->side);
     QAGNN_REQUIRE(he == hipSuccess, QAGNN_EHIP, "hop_bwd: hipEventRecord failed: %s", hipGetErrorString(he));
   }
+  // data gradients dX = dK|dM|dQ Wx and dS = dK|dM|dQ Ws: one launch that reads and splits dK|dM|dQ once where the pair is one the
+  // two-output kernel takes (nn_dual_route: the three-MFMA form at (13, 7) column tiles -- bit-identical), else one launch each
+  qagnn_gemm_nn_args gx = {}, gs = {};
   if (h->dX) {
-    qagnn_gemm_nn_args gx = {};
     gx.A1 = dKMQ; gx.lda1 = 3 * DP; gx.K1 = 3 * DP; gx.B1 = h->Wx; gx.ldb1 = DP; gx.C = h->dX; gx.ldc = DP; gx.M = N; gx.No = DP;
     gx.accumulate = h->accumulate_dX;
     nn_scaled(h, &gx, w_dkmq);
-    HOP_TRY(hop_nn(h, &gx, h->Wx_t, 3 * DP, nullptr, 0, w.pkws, stream));
   }
   if (SP > 0 && h->dS) {
-    qagnn_gemm_nn_args gs = {};
     gs.A1 = dKMQ; gs.lda1 = 3 * DP; gs.K1 = 3 * DP; gs.B1 = h->Ws; gs.ldb1 = SP; gs.C = h->dS; gs.ldc = SP; gs.M = N; gs.No = SP;
     gs.accumulate = h->accumulate_dS;
     nn_scaled(h, &gs, w_dkmq);
-    HOP_TRY(hop_nn(h, &gs, h->Ws_t, 3 * DP, nullptr, 0, w.pkws, stream));
   }
+  if (h->dX && SP > 0 && h->dS && h->gemm_split != 0 && nn_dual_enabled()) {
+    const NnProduct px{&gx, true, h->Wx_t, 3 * DP, nullptr, 0, w.pkws, hop_pack_elems(DP) * 4}, ps{&gs, true, h->Ws_t, 3 * DP, nullptr, 0, nullptr, 0};
+    HOP_TRY(nn_validate(px));
+    HOP_TRY(nn_validate(ps));
+    const NnDualRoute r = nn_dual_route(px, ps);
+    if (r.ok) return gemm_nn_dual(px, ps, r, (hipStream_t)stream);
+  }
+  if (h->dX) HOP_TRY(hop_nn(h, &gx, h->Wx_t, 3 * DP, nullptr, 0, w.pkws, stream));
+  if (SP > 0 && h->dS) HOP_TRY(hop_nn(h, &gs, h->Ws_t, 3 * DP, nullptr, 0, w.pkws, stream));
   return QAGNN_OK;
 }
 
