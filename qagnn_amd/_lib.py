@@ -1,4 +1,4 @@
-"""ctypes binding of libqagnn_hip.so (include/qagnn_hip.h) + a thin tensor-level wrapper.
+"""ctypes binding of libqagnn_hip.so, generated from include/*.h by _abi.py, + a thin tensor-level wrapper.
 
 PyTorch is used here for exactly three things: device memory (torch.empty), the current HIP stream handle and
 raw data pointers.  All compute goes through the C ABI.  There is no fallback: if the shared library is missing
@@ -10,228 +10,46 @@ import os
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('QAGNN_LIB') or os.path.join(_HERE, 'libqagnn_hip.so')  # QAGNN_LIB: an alternate build (kernel A/B runs)
 
-EXPORTS = ['qagnn_last_error', 'qagnn_abi_version', 'qagnn_graph_storage_elems', 'qagnn_graph_prep', 'qagnn_graph_prep_blocked',
-           'qagnn_graph_from_blobs', 'qagnn_radam_step_f32', 'qagnn_node_prep_f32', 'qagnn_seed_epoch_advance', 'qagnn_seed_epoch_set',
-           'qagnn_gemm_nn_f32', 'qagnn_gemm_nn_split_f32', 'qagnn_gemm_nn_pack_bytes', 'qagnn_gemm_nn_ws_bytes', 'qagnn_gemm_nn_split_ws_f32', 'qagnn_gemm_nn_prepack_bytes', 'qagnn_gemm_nn_prepack_f32',
-           'qagnn_gemm_nn_prepack_clear', 'qagnn_gemm_tn_workspace_elems', 'qagnn_gemm_tn_f32', 'qagnn_gemm_tn2_f32', 'qagnn_gemm_tn_colsum_f32',
-           'qagnn_colreduce_workspace_elems', 'qagnn_colreduce_f32', 'qagnn_bn_finalize_f32', 'qagnn_bn_stats_finalize_f32', 'qagnn_bn_relu_bwd_f32',
-           'qagnn_gelu_dropout_fwd_f32', 'qagnn_gelu_dropout_bwd_f32', 'qagnn_sin_basis_f32',
-           'qagnn_bn_relu_bwd_colsum_f32',
-           'qagnn_pool_attn_fwd_f32', 'qagnn_pool_attn_bwd_f32', 'qagnn_head_post_fwd_f32', 'qagnn_head_post_bwd_f32', 'qagnn_add_row0_f32', 'qagnn_gather_multi_f32', 'qagnn_gather_multi_sum_f32',
-           'qagnn_edge_attn_fwd_f32', 'qagnn_edge_attn_bwd_f32',
-           'qagnn_hop_fwd_workspace_elems', 'qagnn_hop_bwd_workspace_elems', 'qagnn_hop_fwd_f32', 'qagnn_hop_bwd_f32',
-           'qagnn_stack_fwd_f32', 'qagnn_stack_bwd_f32', 'qagnn_absmax_f32', 'qagnn_zero_words', 'qagnn_gemm_tn_h2_f32', 'qagnn_gelu_dropout_fwd_amax_f32', 'qagnn_gelu_dropout_amax_scratch_elems',
-           'qagnn_timing_enable', 'qagnn_timing_read', 'qagnn_gemm_tn_h1_f32', 'qagnn_gelu_dropout_bwd_amax_f32', 'qagnn_packed_min_rows',
-           'qagnn_radam_step_scaled_f32', 'qagnn_grad_norm_workspace_elems', 'qagnn_grad_norm_f32', 'qagnn_scale_multi_f32', 'qagnn_graph_prep_cap',
-           'qagnn_store_gather', 'qagnn_graph_from_store']
-# include/qagnn_hip_tn.h, the extension header of the live-tile weight gradient (qagnn_hip.h and its ABI number are unchanged by it)
-EXPORTS_TN = ['qagnn_gemm_tn_graph_f32', 'qagnn_gemm_tn_route_query', 'qagnn_tn_work_table', 'qagnn_tn_live_tiles']
-# include/qagnn_hip_infer.h, the extension header of the forward-only (evaluation) path (likewise)
-EXPORTS_INFER = ['qagnn_infer_version', 'qagnn_bn_relu_absmax_scratch_elems', 'qagnn_bn_relu_absmax_f32', 'qagnn_stack_infer_f32',
-                 'qagnn_choice_eval_f32']
-# include/qagnn_hip_loss.h, the extension header of the training losses (likewise)
-EXPORTS_LOSS = ['qagnn_loss_version', 'qagnn_choice_loss_f32', 'qagnn_choice_loss_bwd_f32']
-# include/qagnn_hip_explain.h, the extension header of the detailed evaluation: attention export and its trace from the context node (likewise)
-EXPORTS_EXPLAIN = ['qagnn_explain_version', 'qagnn_attn_export_f32', 'qagnn_attn_trace_f32']
-# include/qagnn_hip_defer.h, the extension header of the stack backward that finishes dEkEm and db1 of all layers after its last hop (likewise)
-EXPORTS_DEFER = ['qagnn_defer_version', 'qagnn_stack_bwd_defer_elems', 'qagnn_stack_bwd_deferred_f32']
-# include/qagnn_hip_rows.h, the extension header of the trainable entity table's gradient: row grouping, segment sums, row scatter (likewise)
-EXPORTS_ROWS = ['qagnn_rows_version', 'qagnn_row_groups_workspace_elems', 'qagnn_row_groups', 'qagnn_row_segment_sum_workspace_elems',
-                'qagnn_row_segment_sum_f32', 'qagnn_rows_scatter_f32']
-# include/qagnn_hip_dual.h, the extension header of the two-output NN product: a hop's dX and dS from one pass over dK|dM|dQ (likewise)
-EXPORTS_DUAL = ['qagnn_dual_version', 'qagnn_gemm_nn_dual_f32', 'qagnn_gemm_nn_dual_query', 'qagnn_dual_launches', 'qagnn_dual_blocks_per_cu',
-                'qagnn_nn_dual_enable']
-ROWS_CHUNK = 64  # QAGNN_ROWS_CHUNK
-ROWS_MAX_N, ROWS_MAX_TABLE = 1 << 20, 1 << 26  # QAGNN_ROWS_MAX_N, QAGNN_ROWS_MAX_TABLE
-DEFER_MAX_HOPS = 16  # QAGNN_DEFER_MAX_HOPS
-TRACE_MAX_N = 1024  # QAGNN_TRACE_MAX_N
-LOSS_KINDS = {'cross_entropy': 0, 'margin_rank': 1}  # QAGNN_LOSS_CROSS_ENTROPY, QAGNN_LOSS_MARGIN_RANK
-LOSS_THREADS = 256  # QAGNN_LOSS_THREADS
-
-CLS_SLICES = 4  # QAGNN_CLS_SLICES
+_H = _abi.headers()  # the ABI as include/*.h state it: prototypes, structs and constants are read there and declared nowhere else
+_MAIN = _H['qagnn_hip.h']
+EXPORTS = _MAIN.names
+EXPORTS_TN = _H['qagnn_hip_tn.h'].names            # the live-tile weight gradient
+EXPORTS_INFER = _H['qagnn_hip_infer.h'].names      # the forward-only (evaluation) path
+EXPORTS_LOSS = _H['qagnn_hip_loss.h'].names        # the training losses
+EXPORTS_EXPLAIN = _H['qagnn_hip_explain.h'].names  # the detailed evaluation: attention export and its trace from the context node
+EXPORTS_DEFER = _H['qagnn_hip_defer.h'].names      # the stack backward that finishes dEkEm and db1 of all layers after its last hop
+EXPORTS_ROWS = _H['qagnn_hip_rows.h'].names        # the trainable entity table's gradient: row grouping, segment sums, row scatter
+EXPORTS_DUAL = _H['qagnn_hip_dual.h'].names        # the two-output NN product: a hop's dX and dS from one pass over dK|dM|dQ
+ROWS_CHUNK, ROWS_MAX_N, ROWS_MAX_TABLE = (_H['qagnn_hip_rows.h'].define('QAGNN_ROWS_' + n) for n in ('CHUNK', 'MAX_N', 'MAX_TABLE'))
+DEFER_MAX_HOPS = _H['qagnn_hip_defer.h'].define('QAGNN_DEFER_MAX_HOPS')
+TRACE_MAX_N = _H['qagnn_hip_explain.h'].define('QAGNN_TRACE_MAX_N')
+LOSS_KINDS = {k: _H['qagnn_hip_loss.h'].define('QAGNN_LOSS_' + k.upper()) for k in ('cross_entropy', 'margin_rank')}
+LOSS_THREADS = _H['qagnn_hip_loss.h'].define('QAGNN_LOSS_THREADS')
+CLS_SLICES, GATHER_MAX, HOP_AMAX_WORDS = (_MAIN.define('QAGNN_' + n) for n in ('CLS_SLICES', 'GATHER_MAX', 'HOP_AMAX_WORDS'))
+HOP_AM_X, HOP_AM_S, HOP_AM_AGGR, HOP_AM_H1, HOP_AM_Y, HOP_AM_DOUT, HOP_AM_DH1, HOP_AM_DKMQ = (
+    _MAIN.define('QAGNN_HOP_AM_' + n) for n in ('X', 'S', 'AGGR', 'H1', 'Y', 'DOUT', 'DH1', 'DKMQ'))  # the words of qagnn_hop_args.amax in use
+qagnn_graph, qagnn_store, qagnn_gather_tabs, qagnn_pack_desc, qagnn_gemm_nn_args, qagnn_hop_args = (
+    _MAIN.structs[n] for n in ('qagnn_graph', 'qagnn_store', 'qagnn_gather_tabs', 'qagnn_pack_desc', 'qagnn_gemm_nn_args', 'qagnn_hop_args'))
 ABI_VERSION = 25  # bumped when the ABI of include/qagnn_hip.h changes (2: qagnn_graph.tgt_t; 3: (group, class) class order; 4: qagnn_hop_args.accumulate_dX; 5: qagnn_graph_from_blobs; 6: qagnn_edge_attn_fwd_lds_f32 replaces the first LDS kernel; 7: qagnn_graph.pk_s / pk_t / sub_ncls / sub_cls; 8: qagnn_hop_args.gemm_split; 9: qagnn_stack_{fwd,bwd}_f32; 10: qagnn_node_prep_f32 checks the concept ids; 11: qagnn_graph_from_blobs takes an edge CAPACITY, seed epoch, column statistics in the GEMM epilogue, LDS-resident edge forward removed; 12: qagnn_hop_args.side_stream, two buffer sets in the backward workspace; 13: qagnn_gemm_tn2_f32; 14: qagnn_gemm_nn_split_ws_f32 / qagnn_gemm_nn_pack_bytes, hop workspaces carry the pack buffer, qagnn_gemm_nn_prepack_{bytes,f32,clear}; 15: qagnn_head_post_{fwd,bwd}_f32, qagnn_add_row0_f32, qagnn_gather_multi{,_sum}_f32; 16: qagnn_gemm_nn_ws_bytes; 17: the three-MFMA GEMM form -- qagnn_gemm_nn_args.a_amax1 / a_amax2, qagnn_pack_desc.pieces, qagnn_hop_args.amax, qagnn_absmax_f32, qagnn_zero_words, qagnn_gemm_tn_h2_f32; 18: qagnn_hop_args.x_amax / s_amax, qagnn_gelu_dropout_fwd_amax_f32, qagnn_timing_enable / qagnn_timing_read; 19: the reduced-precision form on request -- qagnn_gemm_nn_args.pieces, qagnn_gemm_tn_h1_f32, qagnn_hop_args.gemm_split == 3; 20: qagnn_gelu_dropout_bwd_amax_f32; 21: qagnn_gemm_nn_args.a_rows; 22: qagnn_packed_min_rows; 23: gradient clipping -- qagnn_grad_norm_workspace_elems, qagnn_grad_norm_f32, qagnn_scale_multi_f32, qagnn_radam_step_scaled_f32; 24: qagnn_graph_prep_cap -- the int64 edge-list protocol with an edge CAPACITY; 25: qagnn_store, qagnn_store_gather, qagnn_graph_from_store -- the dataset's graphs resident on the device)
-
-_i32, _i64, _f32, _u64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_void_p
-
-
-class qagnn_graph(C.Structure):
-    _fields_ = ([(n, _i32) for n in ('N', 'E', 'Ep', 'R', 'T', 'C')] +
-                [(n, _vp) for n in ('rowptr_s', 'tgt_s', 'src_s', 'cls_s', 'eid_s', 'rowptr_t', 'src_t', 'tgt_t', 'cls_t', 'pos_t',
-                                    'cls_count', 'src_c', 'tgt_c', 'pos_c', 'chunk_cls', 'chunk_beg',
-                                    'chunk_len', 'n_chunks', 'chunkptr')] +
-                [('max_chunks', _i32), ('err', _vp), ('block_n', _i32), ('n_groups', _i32)])
-
-
-class qagnn_store(C.Structure):
-    """Mirror of qagnn_store in include/qagnn_hip.h: device pointers of a data_utils.DeviceGraphStore."""
-    _fields_ = ([(n, _vp) for n in ('blobs', 'blob_off', 'concept_ids', 'node_type', 'node_scores', 'adj_len')] +
-                [('S', _i32), ('n', _i32), ('W', _i64)])
-
-
-GATHER_MAX = 160
-
-
-class qagnn_gather_tabs(C.Structure):
-    _fields_ = [('p', _vp * GATHER_MAX), ('n', _i32)]
-
-
-class qagnn_pack_desc(C.Structure):
-    _fields_ = [('B1n', _vp), ('ldn1', _i32), ('K1', _i32), ('B2n', _vp), ('ldn2', _i32), ('K2', _i32), ('No', _i32), ('pieces', _i32)]
-
-
-class qagnn_gemm_nn_args(C.Structure):
-    _fields_ = [('A1', _vp), ('lda1', _i32), ('K1', _i32), ('B1', _vp), ('ldb1', _i32),
-                ('A2', _vp), ('lda2', _i32), ('K2', _i32), ('B2', _vp), ('ldb2', _i32),
-                ('C', _vp), ('ldc', _i32), ('M', _i32), ('No', _i32),
-                ('bias', _vp), ('rowtab', _vp), ('ldt', _i32), ('rowidx', _vp),
-                ('a_scale', _vp), ('a_shift', _vp), ('accumulate', _i32), ('a_rowidx', _vp), ('xcd_remap', _i32), ('colstat_part', _vp),
-                ('a_amax1', _vp), ('a_amax2', _vp), ('a_rows', _i64), ('pieces', _i32)]
-
-
-class qagnn_hop_args(C.Structure):
-    """Mirror of qagnn_hop_args in include/qagnn_hip.h (field order is the ABI)."""
-    _fields_ = ([('g', C.POINTER(qagnn_graph))] + [(n, _i32) for n in ('N', 'DP', 'SP', 'HP', 'T')] + [('qscale', _f32)] +
-                [(n, _vp) for n in ('X', 'S', 'ntype', 'Wx_t', 'Wx', 'Ws_t', 'Ws', 'TT', 'EkEm', 'W1t', 'W1', 'b1', 'gamma', 'beta',
-                                    'W2t', 'W2', 'b2')] +
-                [('batch_stats', _i32), ('eps', _f32), ('run_mean_p', _vp), ('run_var_p', _vp), ('run_mean', _vp), ('run_var', _vp),
-                 ('num_batches_tracked', _vp), ('dense_pos', _vp), ('d', _i32), ('momentum', _f32),
-                 ('apply_act', _i32), ('p_drop', _f32), ('seed', _u64)] +
-                [(n, _vp) for n in ('KMQ', 'a', 'alpha', 'aggr', 'h1', 'out', 'y', 'stats', 'dy', 'dX', 'dS')] +
-                [('accumulate_dS', _i32), ('accumulate_dX', _i32)] +
-                [(n, _vp) for n in ('dWx_t', 'dWs_t', 'dTT', 'dEkEm', 'dW1t', 'db1', 'dbn', 'dW2t', 'db2', 'ws')] +
-                [('ws_elems', _i64), ('gemm_split', _i32), ('ones_col', _i32), ('tab_col', _i32), ('side_stream', _vp), ('amax', _vp), ('x_amax', _vp), ('s_amax', _vp)])
-
-
-HOP_AMAX_WORDS = 16  # QAGNN_HOP_AMAX_WORDS
-HOP_AM_X, HOP_AM_S, HOP_AM_AGGR, HOP_AM_H1, HOP_AM_Y, HOP_AM_DOUT, HOP_AM_DH1, HOP_AM_DKMQ = range(8)  # QAGNN_HOP_AM_*: the words in use
 
 
 def load_library(path=LIB_PATH):
-    """dlopen the C-ABI library and declare prototypes.  Raises OSError if it has not been built."""
+    """dlopen the C-ABI library and declare every prototype of the headers.  Raises OSError if it has not been built, or lacks one."""
     if not os.path.exists(path):
         raise OSError(f'{path} not found: build it with `python -m qagnn_amd.build` (hipcc, gfx950)')
     lib = C.CDLL(path)
-    lib.qagnn_last_error.restype = C.c_char_p
-    lib.qagnn_abi_version.restype = _i32
-    lib.qagnn_graph_storage_elems.restype = _i64
-    lib.qagnn_graph_storage_elems.argtypes = [_i32, _i32, _i32, _i32]
-    lib.qagnn_graph_prep.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
-    lib.qagnn_graph_prep_blocked.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
-    lib.qagnn_graph_prep_cap.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]
-    lib.qagnn_graph_from_blobs.argtypes = [C.POINTER(qagnn_graph), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]
-    lib.qagnn_store_gather.argtypes = [C.POINTER(qagnn_store), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    lib.qagnn_graph_from_store.argtypes = [C.POINTER(qagnn_graph), _vp, C.POINTER(qagnn_store), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
-    lib.qagnn_node_prep_f32.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]
-    lib.qagnn_seed_epoch_advance.argtypes = [_u64, _vp]
-    lib.qagnn_seed_epoch_set.argtypes = [_u64, _vp]
-    lib.qagnn_radam_step_f32.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp] + [C.c_double] * 6 + [_i32, _vp]
-    lib.qagnn_radam_step_scaled_f32.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp] + [C.c_double] * 6 + [_i32, _vp, _vp]
-    lib.qagnn_grad_norm_workspace_elems.restype = _i64
-    lib.qagnn_grad_norm_workspace_elems.argtypes = [_i32, _vp]
-    lib.qagnn_grad_norm_f32.argtypes = [_i32, _vp, _vp, C.c_double, _vp, _vp, _vp]
-    lib.qagnn_scale_multi_f32.argtypes = [_i32, _vp, _vp, _vp, _vp]
-    lib.qagnn_gemm_nn_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp]
-    lib.qagnn_gemm_nn_split_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i32, _vp]
-    lib.qagnn_gemm_nn_pack_bytes.restype = _i64
-    lib.qagnn_gemm_nn_pack_bytes.argtypes = [_i32, _i32, _i32]
-    lib.qagnn_gemm_nn_split_ws_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i32, _vp, _i64, _vp]
-    lib.qagnn_gemm_nn_ws_bytes.restype = _i64
-    lib.qagnn_gemm_nn_ws_bytes.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i32]
-    lib.qagnn_gemm_nn_prepack_bytes.restype = _i64
-    lib.qagnn_gemm_nn_prepack_bytes.argtypes = [C.POINTER(qagnn_pack_desc), _i32]
-    lib.qagnn_gemm_nn_prepack_f32.argtypes = [C.POINTER(qagnn_pack_desc), _i32, _vp, _i64, _i64, _vp]
-    lib.qagnn_gemm_nn_prepack_clear.argtypes = [_i64]
-    lib.qagnn_gemm_tn_workspace_elems.restype = _i64
-    lib.qagnn_gemm_tn_workspace_elems.argtypes = [_i32, _i32, _i32]
-    lib.qagnn_gemm_tn_f32.argtypes = [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]
-    lib.qagnn_gemm_tn2_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]
-    lib.qagnn_gemm_tn_h2_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    lib.qagnn_gemm_tn_h1_f32.argtypes = lib.qagnn_gemm_tn_h2_f32.argtypes
-    lib.qagnn_gemm_tn_graph_f32.argtypes = [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32,
-                                            C.POINTER(qagnn_graph), _vp, _vp]
-    lib.qagnn_gemm_tn_route_query.argtypes = [_i32, _i32, _i32, _i32, _vp]
-    lib.qagnn_tn_work_table.argtypes = [C.POINTER(qagnn_graph), _i32, _i32, _vp, _vp]
-    lib.qagnn_tn_live_tiles.argtypes = [_i32]
-    lib.qagnn_absmax_f32.argtypes = [_vp, _i64, _vp, _vp]
-    lib.qagnn_zero_words.argtypes = [_vp, _i64, _vp]
-    lib.qagnn_timing_enable.argtypes = [_i32]
-    lib.qagnn_timing_read.argtypes = [_vp, _vp]
-    lib.qagnn_packed_min_rows.restype = _i64
-    lib.qagnn_packed_min_rows.argtypes = [_i64]
-    lib.qagnn_gemm_tn_colsum_f32.argtypes = [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
-                                             _vp, _vp]
-    lib.qagnn_colreduce_workspace_elems.restype = _i64
-    lib.qagnn_colreduce_workspace_elems.argtypes = [_i32, _i32, _i32]
-    lib.qagnn_colreduce_f32.argtypes = [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]
-    lib.qagnn_bn_finalize_f32.argtypes = [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp]
-    lib.qagnn_bn_stats_finalize_f32.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp]
-    lib.qagnn_bn_relu_bwd_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp]
-    lib.qagnn_gelu_dropout_fwd_f32.argtypes = [_vp, _vp, _i64, _f32, _u64, _vp]
-    lib.qagnn_gelu_dropout_bwd_f32.argtypes = [_vp, _vp, _vp, _i64, _f32, _u64, _vp]
-    lib.qagnn_gelu_dropout_fwd_amax_f32.argtypes = [_vp, _vp, _i64, _f32, _u64, _vp, _vp, _vp]
-    lib.qagnn_gelu_dropout_bwd_amax_f32.argtypes = [_vp, _vp, _vp, _i64, _f32, _u64, _vp, _vp, _vp]
-    lib.qagnn_gelu_dropout_amax_scratch_elems.restype = _i64
-    lib.qagnn_gelu_dropout_amax_scratch_elems.argtypes = [_i64]
-    lib.qagnn_sin_basis_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _vp]
-    lib.qagnn_bn_relu_bwd_colsum_f32.argtypes = [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]
-    lib.qagnn_pool_attn_fwd_f32.argtypes = [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _vp, _vp, _vp, _vp]
-    lib.qagnn_pool_attn_bwd_f32.argtypes = [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
-    lib.qagnn_head_post_fwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64,
-                                            _vp, _vp, _vp, _vp]
-    lib.qagnn_head_post_bwd_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64,
-                                            _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]
-    lib.qagnn_add_row0_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _vp]
-    lib.qagnn_gather_multi_f32.argtypes = [C.POINTER(qagnn_gather_tabs), _vp, _vp, _vp, _i32, _vp]
-    lib.qagnn_gather_multi_sum_f32.argtypes = [C.POINTER(qagnn_gather_tabs), _vp, _vp, _i32, _i32, _vp, _vp]
-    lib.qagnn_edge_attn_fwd_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]
-    lib.qagnn_edge_attn_bwd_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _i32,
-                                            _vp, _vp, _vp, _vp, _vp, _vp]
-    lib.qagnn_hop_fwd_workspace_elems.restype = _i64
-    lib.qagnn_hop_fwd_workspace_elems.argtypes = [_i32, _i32, _i32]
-    lib.qagnn_hop_bwd_workspace_elems.restype = _i64
-    lib.qagnn_hop_bwd_workspace_elems.argtypes = [_i32, _i32, _i32, _i32, _i32]
-    lib.qagnn_hop_fwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _vp]
-    lib.qagnn_hop_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _vp]
-    lib.qagnn_stack_fwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
-    lib.qagnn_stack_bwd_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
-    lib.qagnn_infer_version.argtypes = []
-    lib.qagnn_bn_relu_absmax_scratch_elems.restype = _i64
-    lib.qagnn_bn_relu_absmax_scratch_elems.argtypes = [_i32, _i32]
-    lib.qagnn_bn_relu_absmax_f32.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
-    lib.qagnn_stack_infer_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp]
-    lib.qagnn_choice_eval_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp]
-    lib.qagnn_loss_version.argtypes = []
-    lib.qagnn_choice_loss_f32.argtypes = [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]
-    lib.qagnn_choice_loss_bwd_f32.argtypes = [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]
-    lib.qagnn_explain_version.argtypes = []
-    lib.qagnn_attn_export_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _vp, _i64, _vp]
-    lib.qagnn_attn_trace_f32.argtypes = [C.POINTER(qagnn_graph), _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
-    lib.qagnn_defer_version.argtypes = []
-    lib.qagnn_stack_bwd_defer_elems.restype = _i64
-    lib.qagnn_stack_bwd_defer_elems.argtypes = [_i32, _i32, _i32, _i32]
-    lib.qagnn_stack_bwd_deferred_f32.argtypes = [C.POINTER(qagnn_hop_args), _i32, _vp, _i64, _vp]
-    lib.qagnn_rows_version.argtypes = []
-    lib.qagnn_row_groups_workspace_elems.restype = _i64
-    lib.qagnn_row_groups_workspace_elems.argtypes = [_i32]
-    lib.qagnn_row_groups.argtypes = [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
-    lib.qagnn_row_segment_sum_workspace_elems.restype = _i64
-    lib.qagnn_row_segment_sum_workspace_elems.argtypes = [_i32, _i32]
-    lib.qagnn_row_segment_sum_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _vp]
-    lib.qagnn_rows_scatter_f32.argtypes = [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp]
-    lib.qagnn_dual_version.argtypes = []
-    lib.qagnn_gemm_nn_dual_f32.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i64, _vp]
-    lib.qagnn_gemm_nn_dual_query.argtypes = [C.POINTER(qagnn_gemm_nn_args), _vp, _i32, C.POINTER(qagnn_gemm_nn_args), _vp, _i32, _vp, _i64]
-    lib.qagnn_dual_launches.restype = _i64
-    lib.qagnn_dual_launches.argtypes = []
-    lib.qagnn_nn_dual_enable.argtypes = [_i32]
-    lib.qagnn_dual_blocks_per_cu.argtypes = []
-    for name in EXPORTS + EXPORTS_TN + EXPORTS_INFER + EXPORTS_LOSS + EXPORTS_EXPLAIN + EXPORTS_DEFER + EXPORTS_ROWS + EXPORTS_DUAL:
-        fn = getattr(lib, name)
-        if fn.restype is C.c_int and name not in ('qagnn_abi_version',):
-            fn.restype = _i32
+    for hdr, h in _H.items():
+        for name, restype, argtypes in h.prototypes:
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise OSError(f'{path} does not export {name}, which include/{hdr} declares: rebuild it with `python -m qagnn_amd.build --force`') from None
+            fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
@@ -909,8 +727,8 @@ class HipKernels(metaclass=_GuardedMeta):
 
     def tn_route_query(self, R, Ka1, Ka2, No):
         """host-only: (family, chunk_rows, nchunks, live) of the weight gradient [A1 | A2]^T B (qagnn_gemm_tn_route_query); family 3 = k_gemm_tn_ws"""
-        out = (_i32 * 4)()
-        self._check(self.lib.qagnn_gemm_tn_route_query(R, Ka1, Ka2, No, C.cast(out, _vp)), 'qagnn_gemm_tn_route_query')
+        out = (C.c_int32 * 4)()
+        self._check(self.lib.qagnn_gemm_tn_route_query(R, Ka1, Ka2, No, C.cast(out, C.c_void_p)), 'qagnn_gemm_tn_route_query')
         return tuple(out)
 
     def tn_work_table(self, graph, S, chunk_tiles):

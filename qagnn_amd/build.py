@@ -19,14 +19,9 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 def hashed_files():
     """Everything the library is compiled from: the sources, every header next to them, the public headers."""
     headers = sorted(f for f in os.listdir(CSRC) if f.endswith('.h'))
-    return [os.path.join(CSRC, s) for s in SOURCES + headers] + [os.path.join(HERE, '..', 'include', 'qagnn_hip.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_tn.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_infer.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_loss.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_explain.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_defer.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_rows.h'),
-                                                                 os.path.join(HERE, '..', 'include', 'qagnn_hip_dual.h')]
+    include = os.path.join(HERE, '..', 'include')
+    public = sorted(f for f in os.listdir(include) if f.endswith('.h'))
+    return [os.path.join(CSRC, s) for s in SOURCES + headers] + [os.path.join(include, f) for f in public]
 
 
 def source_hash():
