@@ -21,6 +21,7 @@
 //     mode 0             :  moments only (step_size < 0: degenerated_to_sgd = False and N_sma < 5)
 // HBM-bound streaming: 4 reads + 3 writes of 4 bytes per element (the norm: 1 read; the in-place scale: 1 read + 1 write).
 #include "common.h"
+#include "../../include/ext/qagnn_hip_step.h"
 
 namespace qagnn {
 
@@ -141,6 +142,87 @@ __global__ __launch_bounds__(MT_THREADS) void k_scale_multi(const scale_pack a) 
   for (int i = threadIdx.x; i < n; i += MT_THREADS) g[i] = __fmul_rn(g[i], sc);
 }
 
+// ---- the tail of a CAPTURED training step (include/ext/qagnn_hip_step.h; graphed.GraphedStep(optimizer=...)) ------------------------------
+// A replayed launch repeats its arguments, so what changes from one optimiser step to the next -- lr, step_size, the branch -- cannot travel
+// in them: every tensor of the call names a RECORD in device memory (rec[slot]), which a launch of k_step_records_write in front of the
+// replay fills from ITS arguments.  The pointer tables stay in the argument: parameters, moments, window buffers and a capture's gradients
+// have fixed addresses.
+struct radam_rec_pack {
+  float* p[MT_MAX_TENSORS];
+  const float* g[MT_MAX_TENSORS];
+  float* m[MT_MAX_TENSORS];
+  float* v[MT_MAX_TENSORS];
+  int rec[MT_MAX_TENSORS];  // the record of the slot's tensor
+  block_map map;
+  const qagnn_step_record* records;
+  const float* grad_scale;  // SCALED only
+};
+
+// k_radam_multi with decay, s, mode (and the group's constants) read from the block's record: one uniform load per block, then the same
+// expressions in the same spelling, so the same bits
+template <bool SCALED>
+__global__ __launch_bounds__(MT_THREADS) void k_radam_multi_rec(const radam_rec_pack a) {
+  const int t = a.map.block_tensor[blockIdx.x];
+  const int base = a.map.block_chunk[blockIdx.x] * MT_CHUNK;
+  const int n = min(a.map.numel[t] - base, MT_CHUNK);
+  float* __restrict__ p = a.p[t] + base;
+  const float* __restrict__ g = a.g[t] + base;
+  float* __restrict__ m = a.m[t] + base;
+  float* __restrict__ v = a.v[t] + base;
+  const qagnn_step_record r = a.records[a.rec[t]];
+  const float ob1 = r.ob1, ob2 = r.ob2, decay = r.decay, s = r.s, beta1 = r.beta1, beta2 = r.beta2, eps = r.eps;
+  const int mode = r.mode;
+  float sc = 1.0f;
+  if constexpr (SCALED) sc = a.grad_scale[0];
+  for (int i = threadIdx.x; i < n; i += MT_THREADS) {
+    float gi = g[i];
+    if constexpr (SCALED) gi = __fmul_rn(gi, sc);
+    const float vi = fmaf(__fmul_rn(ob2, gi), gi, __fmul_rn(v[i], beta2));
+    const float mi = fmaf(ob1, gi, __fmul_rn(m[i], beta1));
+    v[i] = vi;
+    m[i] = mi;
+    if (mode) {
+      float pi = p[i];
+      if (decay != 0.0f) pi += decay * pi;
+      pi += mode == 2 ? s * (mi / (sqrtf(vi) + eps)) : s * mi;
+      p[i] = pi;
+    }
+  }
+}
+
+struct accum_pack {
+  float* dst[MT_MAX_TENSORS];
+  const float* src[MT_MAX_TENSORS];
+  block_map map;
+  const int32_t* first;
+};
+
+// dst = *first ? src : dst + src.  A SELECT: what a stale window holds (inf, NaN) is not read into the first mini-batch of the next one
+__global__ __launch_bounds__(MT_THREADS) void k_window_accumulate(const accum_pack a) {
+  const int t = a.map.block_tensor[blockIdx.x];
+  const int base = a.map.block_chunk[blockIdx.x] * MT_CHUNK;
+  const int n = min(a.map.numel[t] - base, MT_CHUNK);
+  float* __restrict__ dst = a.dst[t] + base;
+  const float* __restrict__ src = a.src[t] + base;
+  if (a.first[0]) {
+    for (int i = threadIdx.x; i < n; i += MT_THREADS) dst[i] = src[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += MT_THREADS) dst[i] = dst[i] + src[i];
+  }
+}
+
+constexpr int REC_PER_LAUNCH = 64;  // records of one k_step_records_write launch: 3 KiB of kernel argument
+
+struct records_pack {
+  qagnn_step_record r[REC_PER_LAUNCH];
+  qagnn_step_record* out;
+  int n;
+};
+
+__global__ __launch_bounds__(REC_PER_LAUNCH) void k_step_records_write(const records_pack a) {
+  if ((int)threadIdx.x < a.n) a.out[threadIdx.x] = a.r[threadIdx.x];
+}
+
 static inline int64_t mt_chunks(int64_t numel) { return (numel + MT_CHUNK - 1) / MT_CHUNK; }
 
 // Cuts tensors 0..n_tensors-1 into packs of at most MT_MAX_TENSORS tensor slots and MT_MAX_BLOCKS chunks (a tensor that does not fit is
@@ -259,6 +341,72 @@ extern "C" int qagnn_scale_multi_f32(int32_t n_tensors, float* const* g, const i
       [&](int nb, int64_t) -> int {
         k_scale_multi<<<nb, MT_THREADS, 0, stream>>>(a);
         QAGNN_LAUNCH_CHECK("k_scale_multi");
+        return QAGNN_OK;
+      });
+}
+
+// ---- include/ext/qagnn_hip_step.h ---------------------------------------------------------------------------------------------------------
+static_assert(sizeof(qagnn_step_record) == 48, "qagnn_step_record: twelve 4-byte words");
+
+extern "C" int qagnn_step_version(void) { return 1; }
+
+extern "C" int qagnn_step_records_write(qagnn_step_record* records, int32_t first, int32_t n, const qagnn_step_record* values,
+                                        qagnn_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  QAGNN_REQUIRE(first >= 0 && n >= 0 && (n == 0 || (records && values)), QAGNN_EINVAL, "step_records_write: null table or negative range");
+  for (int i = 0; i < n; ++i)
+    QAGNN_REQUIRE(values[i].mode >= 0 && values[i].mode <= 2, QAGNN_EINVAL, "step_records_write: record %d: mode %d", i, values[i].mode);
+  records_pack a;
+  for (int done = 0; done < n; done += REC_PER_LAUNCH) {
+    a.n = n - done < REC_PER_LAUNCH ? n - done : REC_PER_LAUNCH;
+    for (int i = 0; i < REC_PER_LAUNCH; ++i) a.r[i] = values[done + (i < a.n ? i : 0)];
+    a.out = records + first + done;
+    k_step_records_write<<<1, REC_PER_LAUNCH, 0, stream>>>(a);
+    QAGNN_LAUNCH_CHECK("k_step_records_write");
+  }
+  return QAGNN_OK;
+}
+
+extern "C" int qagnn_radam_step_records_f32(int32_t n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                            const int64_t* numel, const int32_t* rec_index, const qagnn_step_record* records,
+                                            int32_t n_records, const float* grad_scale, qagnn_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  QAGNN_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (p && g && m && v && numel && rec_index && records)), QAGNN_EINVAL,
+                "radam_step_records: null table");
+  for (int i = 0; i < n_tensors; ++i) {
+    QAGNN_REQUIRE(numel[i] >= 0 && numel[i] < (1ll << 31) && (numel[i] == 0 || (p[i] && g[i] && m[i] && v[i])), QAGNN_EINVAL,
+                  "radam_step_records: tensor %d: null pointer or bad size", i);
+    QAGNN_REQUIRE(rec_index[i] >= 0 && rec_index[i] < n_records, QAGNN_EINVAL, "radam_step_records: tensor %d: record %d of %d", i, rec_index[i],
+                  n_records);
+  }
+  radam_rec_pack a;
+  a.records = records; a.grad_scale = grad_scale;
+  return for_each_pack(
+      n_tensors, numel, a.map,
+      [&](int slot, int i) { a.p[slot] = p[i]; a.g[slot] = g[i]; a.m[slot] = m[i]; a.v[slot] = v[i]; a.rec[slot] = rec_index[i]; },
+      [&](int nb, int64_t) -> int {
+        if (grad_scale) k_radam_multi_rec<true><<<nb, MT_THREADS, 0, stream>>>(a);
+        else k_radam_multi_rec<false><<<nb, MT_THREADS, 0, stream>>>(a);
+        QAGNN_LAUNCH_CHECK("k_radam_multi_rec");
+        return QAGNN_OK;
+      });
+}
+
+extern "C" int qagnn_window_accumulate_f32(int32_t n_tensors, float* const* dst, const float* const* src, const int64_t* numel,
+                                           const int32_t* first, qagnn_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  QAGNN_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (dst && src && numel)), QAGNN_EINVAL, "window_accumulate: null table");
+  QAGNN_REQUIRE(first, QAGNN_EINVAL, "window_accumulate: null first-of-window word");
+  for (int i = 0; i < n_tensors; ++i)
+    QAGNN_REQUIRE(numel[i] >= 0 && numel[i] < (1ll << 31) && (numel[i] == 0 || (dst[i] && src[i])), QAGNN_EINVAL,
+                  "window_accumulate: tensor %d: null pointer or bad size", i);
+  accum_pack a;
+  a.first = first;
+  return for_each_pack(
+      n_tensors, numel, a.map, [&](int slot, int i) { a.dst[slot] = dst[i]; a.src[slot] = src[i]; },
+      [&](int nb, int64_t) -> int {
+        k_window_accumulate<<<nb, MT_THREADS, 0, stream>>>(a);
+        QAGNN_LAUNCH_CHECK("k_window_accumulate");
         return QAGNN_OK;
       });
 }

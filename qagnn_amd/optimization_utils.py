@@ -33,6 +33,23 @@ def radam_step_size(step, beta1, beta2, degenerated_to_sgd=True):
     return n_sma, step_size
 
 
+def radam_mode(n_sma, step_size):
+    """the branch of the update: 2 rectified (N_sma >= 5), 1 SGD-like, 0 moments only (step_size < 0: degenerated_to_sgd=False below 5)"""
+    return 2 if n_sma >= 5 else (1 if step_size > 0 else 0)
+
+
+def radam_record(group, step, degenerated_to_sgd=True):
+    """What the update of one tensor of `group` at step count `step` reads from its device record when the step is replayed from a captured
+    graph (include/ext/qagnn_hip_step.h: qagnn_step_record), as Python doubles: exactly the doubles RAdam.step() hands to
+    qagnn_radam_step_scaled_f32, combined as that entry point combines them.  The ONE rounding to fp32 happens where they are stored into
+    the record (_step.pack_records), as it happens there in the `(float)` casts."""
+    beta1, beta2 = group['betas']
+    lr, wd = float(group['lr']), float(group['weight_decay'])
+    n_sma, step_size = radam_step_size(step, beta1, beta2, degenerated_to_sgd)
+    return dict(decay=-wd * lr, s=-float(step_size) * lr, mode=radam_mode(n_sma, step_size), beta1=float(beta1), beta2=float(beta2),
+                ob1=1.0 - float(beta1), ob2=1.0 - float(beta2), eps=float(group['eps']))
+
+
 class AdamW(Optimizer):
     """`transformers.AdamW` as the reference imports it (utils/optimization_utils.py:3; transformers == 3.4.0 is pinned in the
     reference's README, the class has since been removed from transformers): its defaults -- eps = 1e-6, weight_decay = 0.0,
