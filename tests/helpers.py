@@ -1268,3 +1268,112 @@ def check_history_free(call, exempt=(), reset=None, fills=FILLS, what='', log=No
         log.append(line)
     assert not failures, f'{what}: ' + '; '.join(failures[:8])
     return compared, sum(n_ex)
+
+
+# Forced stream schedules (tests/test_stream_schedules.py) --------------------------------------------------------------------------------
+# Where two streams are ordered by events only, which of them is late is decided by the host's launch pace -- on small batches the device
+# waits for the host and the second stream never lags.  hold_stream() makes one stream late on purpose: a bounded spin (torch.cuda._sleep)
+# is enqueued on it, the call under test is enqueued while it spins, and the results are compared with the one-stream bits.  A hold that had
+# already ended when the enqueue finished proves nothing: check_under_hold() fails then.
+HOLD_CAP_MS = 250.0                 # no single hold is longer
+HOLD_TOO_SHORT = 'hold too short: the schedule was not adverse'
+_SPIN_CYCLES_PER_MS = [None]        # torch.cuda._sleep cycles per millisecond on this device: measured once per process
+
+
+def _timed_spin(n):
+    """ms between two events around torch.cuda._sleep(n), the shorter of two takes (the events also see the host's launch latency: the
+    first launch of a process loads the kernel's code object)"""
+    best = float('inf')
+    for _ in range(2):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        torch.cuda._sleep(n)
+        e1.record()
+        e1.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return best
+
+
+def spin_cycles_per_ms():
+    """cycles of torch.cuda._sleep per millisecond, measured once per process (the spin's counter and its rate are not documented for
+    gfx950).  After a warm-up launch the spin is lengthened by 4x until one lasts 4 ms; the rate is the SLOPE between that spin and one of
+    twice the cycles, so that whatever the two events see besides the spin (launch latency, a code object loaded on first use) cancels,
+    and a spin of 10 ms at that rate must then last 7 .. 15 ms.  The longest calibration spin stays below 32 ms."""
+    if _SPIN_CYCLES_PER_MS[0] is None:
+        torch.cuda._sleep(1000)
+        torch.cuda.synchronize()
+        n, t1 = 1 << 16, 0.0
+        for _ in range(16):
+            t1 = _timed_spin(n)
+            if t1 >= 4.0:
+                break
+            n *= 4
+        t2 = _timed_spin(2 * n)
+        if not (t1 >= 4.0 and 0.5 * t1 <= t2 - t1 <= 1.5 * t1):
+            raise RuntimeError(f'torch.cuda._sleep({n}) took {t1:.3f} ms and ({2 * n}) {t2:.3f} ms: the spin is unusable on this device')
+        rate = n / (t2 - t1)
+        check = _timed_spin(int(10.0 * rate))
+        if not 7.0 <= check <= 15.0:
+            raise RuntimeError(f'a spin calibrated to 10 ms took {check:.3f} ms ({rate:.0f} cycles per ms from {n} and {2 * n} cycles)')
+        _SPIN_CYCLES_PER_MS[0] = rate
+        print(f'FIGURE spin calibration: torch.cuda._sleep({n}) = {t1:.3f} ms, ({2 * n}) = {t2:.3f} ms -> {rate:.0f} cycles per ms; '
+              f'a spin of 10 ms at that rate took {check:.3f} ms')
+    return _SPIN_CYCLES_PER_MS[0]
+
+
+class StreamHold:
+    """what hold_stream returns: the event recorded behind the spin"""
+
+    def __init__(self, event, ms):
+        self.event, self.ms = event, ms
+
+    def still_held(self):
+        return not self.event.query()
+
+    def release_wait(self):
+        self.event.synchronize()
+
+
+def hold_stream(stream, ms):
+    """Enqueue a spin of `ms` milliseconds on `stream` (a torch.cuda.Stream) and record an event behind it -> StreamHold.  ValueError for a
+    hold above HOLD_CAP_MS or not above 0, and for anything that is not a stream of a GPU (a CPU tensor or device among them): refused before
+    the device is touched."""
+    if not (0.0 < float(ms) <= HOLD_CAP_MS):
+        raise ValueError(f'a hold of {ms} ms: holds are bounded by {HOLD_CAP_MS} ms')
+    if not isinstance(stream, torch.cuda.Stream):
+        dev = stream.device if isinstance(stream, torch.Tensor) else stream
+        raise ValueError(f'hold_stream holds a stream of a GPU, not {dev!r}')
+    cycles = int(spin_cycles_per_ms() * float(ms))
+    with torch.cuda.stream(stream):
+        torch.cuda._sleep(cycles)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+    return StreamHold(ev, float(ms))
+
+
+def check_under_hold(*holds):
+    """call it right behind the last launch of the call under test, before any synchronisation: every hold must still be pending"""
+    assert holds and all(h.still_held() for h in holds), HOLD_TOO_SHORT
+
+
+def same_bits(got, want, what=''):
+    """two dicts of tensors (or lists of tensors) with the same keys, bit for bit (fp32 as int32 patterns: a NaN equals only the same NaN);
+    -> the number of elements compared"""
+    assert set(got) == set(want), f'{what}: {sorted(set(got) ^ set(want))}'
+    n, bad = 0, []
+    for k in sorted(got):
+        gs, ws = (list(x) if isinstance(x, (list, tuple)) else [x] for x in (got[k], want[k]))
+        assert len(gs) == len(ws), f'{what}: {k}: {len(gs)} tensors against {len(ws)}'
+        for i, (g, w) in enumerate(zip(gs, ws)):
+            if g is None or w is None:
+                assert g is None and w is None, f'{what}: {k}[{i}] is missing on one side'
+                continue
+            a, b = _bits(g), _bits(w)
+            if a.shape != b.shape or not torch.equal(a, b):
+                nd = int((a != b).sum()) if a.shape == b.shape else -1
+                nn_ = int(torch.isnan(g.detach().float()).sum()) if g.dtype.is_floating_point else 0
+                bad.append(f'{k}[{i}]: {nd} of {a.numel()} elements differ ({nn_} NaN)')
+            n += a.numel()
+    assert not bad, f'{what}: ' + '; '.join(bad[:10])
+    return n
